@@ -2,9 +2,14 @@
 (BASELINE.json configs[1]) on N GPUs of one node, one process per GPU, batch sharded data-parallel with
 an RCCL gradient average.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus 1] [--steps 30] [--warmup 5] [--workload c2|c4]
+    python bench.py [--gpus 1] [--steps 30] [--warmup 5] [--workload c2|c4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly --steps steps, writes the last step's outputs if --dump-outputs is given and
+prints the line.  --full adds everything else: the timed block repeated for --min-seconds (median block reported),
+per-entry-point HIP-event times, the roofline objects, the head product against the vendor GEMM, the CPU baseline and,
+at N > 1, the per-phase step breakdown.
 """
 import argparse
 import json
@@ -126,6 +131,45 @@ def cpu_baseline(B, N, k, classes, budget_s=12.0, max_steps=8):
                       f"oracle/ref_cpu.DGCNNSeg fwd+CE+GDL+bwd+Adam, {dt:.2f} s/step"}
 
 
+def _detached(o):
+    if isinstance(o, torch.Tensor):
+        return o.detach()
+    if isinstance(o, (tuple, list)):
+        return type(o)(_detached(v) for v in o)
+    if isinstance(o, dict):
+        return {n: _detached(v) for n, v in o.items()}
+    return o
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20
+
+
+def dump_outputs(path, arrays):
+    """arrays {name: tensor} -> path/<name>.npy, float32 (float64 stays float64).  The files hold at most DUMP_BUDGET_BYTES
+    together: an array over its equal share of the budget is written as a sample -- the flattened array at sorted indices
+    drawn without replacement by numpy's default_rng(0), so the same shape always gives the same indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        cap = share // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _named_outputs(o, name="output"):
+    """the model's output as {name: tensor}: one tensor -> "output", a tuple / list / dict -> "output_<i or key>" """
+    if isinstance(o, torch.Tensor):
+        return {name: o}
+    items = o.items() if isinstance(o, dict) else enumerate(o)
+    out = {}
+    for n, v in items:
+        out.update(_named_outputs(v, f"{name}_{n}"))
+    return out
+
+
 def _dump_memmap(path, net, opt):
     """address ranges of the step's long-lived buffers and of every allocator segment (with its graph pool), written
     before the first replay: a GPU memory fault names an address, this names its owner"""
@@ -158,9 +202,18 @@ def main():
     ap.add_argument("--dtype", default=None, choices=["f32", "bf16"],
                     help="MFMA operand type of the dense contractions (functional.set_mfma_operands); default: what "
                          "BASELINE names: fp32 for config 2, bf16 for configs 3 and 4; config 5 has no bf16 kernel and runs fp32")
-    ap.add_argument("--min-seconds", type=float, default=3.0,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: repeated timed blocks (--min-seconds), "
+                         "per-entry-point times, rooflines, the vendor GEMM comparison, the CPU baseline, the N > 1 step "
+                         "breakdown")
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="repeat the timed block of --steps steps until the GPU has been busy this long; the MEDIAN block is "
-                         "reported (ms_per_step, value), every block is bracketed by barrier + synchronize")
+                         "reported (ms_per_step, value), every block is bracketed by barrier + synchronize (default: 3 "
+                         "with --full, else 0: one block of exactly --steps steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (loss, model output, updated "
+                         "parameters, gradient) as DIR/<name>.npy, float32; arrays above the size budget are a fixed "
+                         "seeded sample")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python instead of replaying a hipGraph")
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam over the separate tensors instead of FlatAdam")
     ap.add_argument("--grad-sync", default="flat", choices=["flat", "bucketed"],
@@ -171,6 +224,8 @@ def main():
                          "averaged gradient to this .npz (tests/test_gpu_parity.py compares it with the oracle's mean of "
                          "shard gradients)")
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 3.0 if args.full else 0.0
 
     torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)  # warm-up and capture use side streams
     rank, world, device = D.init_from_env()
@@ -237,12 +292,18 @@ def main():
     if args.workload == "c5":     # train_pc_ae.py:172-185: reconstruct the input cloud, Chamfer loss (target = input)
         chamfer = ChamferLoss()
 
+    # the model output of the latest step, detached (its storage only, not its autograd graph); under replay the captured
+    # tensor, rewritten by every replay
+    last_out = [None]
+
     def fwd_bwd():
         averager.zero_grad()
+        out = net(x)
+        last_out[0] = _detached(out)
         if args.workload == "c5":
-            loss = chamfer(net(x), x)
+            loss = chamfer(out, x)
         else:
-            loss, _parts = criterion(net(x), y)
+            loss, _parts = criterion(out, y)
         loss.backward()
         return loss
 
@@ -316,8 +377,8 @@ def main():
             def graph_step():
                 if flat_sync:     # graph 1 -> in-place all-reduce of flat.grad on the replay stream -> graph 2
                     step_no[0] += 1
-                    D.flat_sync_step(g1.replay, opt.flat.grad, g2.replay,
-                                     probe=breakdown if step_no[0] % 10 == 0 else None)   # HIP events every 10th step
+                    D.flat_sync_step(g1.replay, opt.flat.grad, g2.replay,     # --full: HIP events every 10th step
+                                     probe=breakdown if args.full and step_no[0] % 10 == 0 else None)
                     return static_loss
                 g1.replay()
                 if world > 1:
@@ -350,13 +411,22 @@ def main():
     for _ in range(int(nblocks.item()) - 1):
         dt, loss = timed_block()
         blocks.append(dt)
-    # per-kernel durations: HIP events around every C-ABI call in a few EAGER steps of the same workload (events cannot
-    # be read back from inside a replayed graph); the rocprofv3 summary under profiles/ covers the replayed region
-    _lib.start_timing()
-    n_timed = 5
-    for _ in range(n_timed):
-        eager_step()
-    kernel_ms = _lib.stop_timing()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, before anything below runs another step: its loss and model output, the
+        # parameters it updated and the gradient it applied (N > 1: the averaged one)
+        grads = opt.flat.grad if isinstance(opt, FlatAdam) else \
+            torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in net.parameters()])
+        dump_outputs(args.dump_outputs, {"loss": loss, **_named_outputs(last_out[0]),
+                                         "params": torch.cat([p.detach().reshape(-1) for p in net.parameters()]),
+                                         "grads": grads})
+    # --full: per-kernel durations: HIP events around every C-ABI call in a few EAGER steps of the same workload (events
+    # cannot be read back from inside a replayed graph); the rocprofv3 summary under profiles/ covers the replayed region
+    kernel_ms, n_timed = {}, 5
+    if args.full:
+        _lib.start_timing()
+        for _ in range(n_timed):
+            eager_step()
+        kernel_ms = _lib.stop_timing()
     # the headline kernel group (forward graph build + neighbour gather of the three EdgeConv layers) on its own: captured
     # into a hipGraph and replayed between two HIP events, so the time carries no Python launch gaps -- exactly what runs
     # inside the replayed training step
@@ -380,8 +450,8 @@ def main():
 
     group_us, knn64_us, knn_prepared, knn_nominees = None, None, False, None
     try:
-        if not dgcnn:
-            raise LookupError("no EdgeConv group in this workload")
+        if not dgcnn or not args.full:
+            raise LookupError("no EdgeConv group in this workload, or not asked for (--full)")
 
         def group():     # the three EdgeConv layers exactly as DGCNNSeg.forward runs them (DGCNNSeg.edge_levels)
             with torch.no_grad():
@@ -427,7 +497,7 @@ def main():
     except Exception as e:
         print(f"[bench] group timing by graph replay failed ({type(e).__name__}: {e})", file=sys.stderr)
     head_us, vendor_us = None, None
-    if dgcnn and rank == 0:
+    if args.full and dgcnn and rank == 0:
         # the widest product of the fused point-wise head on its own (levels (B N, 192) x [W_global ; W0_levels]^T (1280, 192),
         # csrc/pointwise.hip): plain member of the kernel family, same tile and loop as inside the step
         try:
@@ -471,7 +541,7 @@ def main():
                      grad_sync="flat" if flat_sync else "bucketed")
     # N > 1: where the step's time goes (HIP events around graph 1 / the all-reduce / graph 2 on every 10th step), max over ranks
     breakdown_us = None
-    if world > 1:
+    if world > 1 and args.full:
         torch.cuda.synchronize()
         mean = breakdown.mean_us()
         bt = torch.tensor([mean[n] for n in D.StepBreakdown.NAMES] if mean else [0.0, 0.0, 0.0], dtype=torch.float64, device=device)
@@ -493,7 +563,7 @@ def main():
             per_kernel[name] = {"launches_per_step": len(vals) / n_timed, "avg_us": 1e3 * sum(vals) / len(vals)}
         traffic_all = {}
         tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tpath):
+        if args.full and os.path.exists(tpath):
             with open(tpath) as f:
                 traffic_all = json.load(f)
         roofline, roofline_group = None, None
@@ -576,7 +646,7 @@ def main():
                         "avg_us": round(1e3 * avg_ms, 1), "launches_per_step": per_step,
                         "candidates_per_s": round(B * N * N / t_s, 1),
                         "timed_as": timed_as}
-        if dgcnn:
+        if dgcnn and args.full:
             # the north-star HBM view of the forward "kNN + gather" group, against BOTH byte counts of SURVEY 8(d)
             grp = ["fsg_knn_dense_ws_f32", "fsg_knn_dense_ws_pq_f32", "fsg_knn_dense_prepared_f32", "fsg_edge_gather_fwd_f32",
                    "fsg_edgeconv1_fwd_f32", "fsg_edgeconv2_fwd_f32", "fsg_edgeconv2_fwd_bf16", "fsg_edgeconv_apply_f32",
@@ -658,7 +728,9 @@ def main():
                           "step_breakdown_us": breakdown_us},
                "timing": {"blocks": len(blocks), "steps_per_block": args.steps, "reported": "median block",
                           "block_ms_min_median_max": [round(1e3 * blocks[0], 3), round(1e3 * elapsed, 3), round(1e3 * blocks[-1], 3)],
-                          "gpu_busy_s": round(sum(blocks), 2)},
+                          "gpu_busy_s": round(sum(blocks), 2)}}
+        if args.full:
+            out.update({
                "roofline": roofline, "roofline_group_hbm": roofline_group,
                "roofline_head_product": None if head_us is None else {
                    "bound": "mfma", "unit": "TFLOP/s", "peak": 2500.0,
@@ -672,11 +744,11 @@ def main():
                    "vendor_fp32_gemm_same_shape_tflops": None if vendor_us is None else
                    round(2.0 * B * N * 1280 * 192 / (vendor_us * 1e-6) / 1e12, 1),
                    "vendor_fp32_gemm_timed_as": "torch.mm(a, w^T) at (B N, 192) x (192, 1280), hipGraph replay, this run"},
-               "entry_points": {n: {k2: round(v, 2) for k2, v in d.items()} for n, d in sorted(per_kernel.items())}}
+               "entry_points": {n: {k2: round(v, 2) for k2, v in d.items()} for n, d in sorted(per_kernel.items())}})
         if not dgcnn:
             out["config"]["step"] = ("fwd + cross-entropy + generalised Dice + bwd + Adam" if args.workload in ("c3", "c3f", "c3b")
                                      else "fwd + Chamfer(reconstruction, input) + bwd + Adam")
-        if world == 1 and not args.no_cpu_baseline and dgcnn and args.workload != "c2s":
+        if args.full and world == 1 and not args.no_cpu_baseline and dgcnn and args.workload != "c2s":
             # (N = 8192: one cloud per CPU step -- a step of the oracle materialises (B,N,N) and (B,2C,N,k) tensors)
             out["cpu_baseline"] = cpu_baseline(B if N <= 2048 else 1, N, k, classes, budget_s=12.0 if N <= 2048 else 20.0,
                                                max_steps=8 if N <= 2048 else 3)

@@ -2266,14 +2266,14 @@ def test_flat_adam_is_a_drop_in_for_the_trainer(fsg, device):
 @pytest.mark.parametrize("workload,dtype,roof", [("c2", "f32", True), ("c3", "bf16", True), ("c3", "f32", True), ("c4", "bf16", True),
                                                  ("c5", "f32", True), ("c2s", "f32", False)])
 def test_bench_line_contract(workload, dtype, roof):
-    """`python bench.py --workload W` (3 replayed steps, no CPU leg) prints ONE JSON line with the contract's keys, the workload's
-    stated arithmetic type as the default dtype, a finite positive rate, whole-job throughput = clouds x points x steps / time,
-    and -- for the workloads with a priced dominant kernel -- a roofline object whose fraction lies in (0, 1]."""
+    """`python bench.py --full --workload W` (3 replayed steps, no CPU leg) prints ONE JSON line with the contract's keys, the
+    workload's stated arithmetic type as the default dtype, a finite positive rate, whole-job throughput = clouds x points x steps /
+    time, and -- for the workloads with a priced dominant kernel -- a roofline object whose fraction lies in (0, 1]."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1", "--min-seconds", "0",
-           "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--workload", workload, "--steps", "3", "--warmup", "1",
+           "--min-seconds", "0", "--no-cpu-baseline"]
     if (workload, dtype) == ("c3", "f32"):
         cmd += ["--dtype", "f32"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
@@ -2294,6 +2294,39 @@ def test_bench_line_contract(workload, dtype, roof):
     if roof:
         rl = d["roofline"]
         assert rl is not None and rl["bound"] in ("hbm", "mfma", "l2") and 0.0 < rl["frac"] <= 1.0 and rl["peak"] > 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `python bench.py --steps 2 --dump-outputs DIR` times exactly one block of the 2 steps, leaves the --full
+    measurements out of its line, and writes the last timed step's outputs: float32 files within 64 MB, the logits of the
+    training batch whose loss the oracle reproduces from them, and one parameter and one gradient per model parameter."""
+    import subprocess
+    import sys
+    from bench import synthetic_batch
+    from fissure_segmentation_amd.models.dgcnn import DGCNNSeg
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)],
+                       cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["timing"]["blocks"] == 1 and d["config"]["launch"] == "hipGraph replay"
+    assert d["dtype"] == "f32" and d["higher_is_better"] is True and d["unit"] == "points/s" and d["ms_per_step"] > 0
+    for key in ("roofline", "roofline_group_hbm", "roofline_head_product", "entry_points", "cpu_baseline"):
+        assert key not in d, key
+    files = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+    assert set(files) == {"loss", "output", "params", "grads"}
+    assert sum(f.stat().st_size for f in dump.glob("*.npy")) <= 64e6
+    for name, a in files.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+    n_params = sum(p.numel() for p in DGCNNSeg(k=20, in_features=3, num_classes=4).parameters())
+    assert files["params"].shape == files["grads"].shape == (n_params,)
+    assert files["output"].shape == (8, 4, 2048) and np.abs(files["grads"]).max() > 0
+    _x, y = synthetic_batch(8, 2048, 4, 1234, "cpu")
+    want = ref_cpu.nnu_loss(torch.from_numpy(files["output"]).double(), y, torch.tensor([0.4, 1.2, 1.2, 1.2]))[0]
+    assert abs(float(files["loss"]) - float(want)) <= 1e-5 * abs(float(want))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

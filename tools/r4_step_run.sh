@@ -5,10 +5,11 @@ TAG=$1; KEXPR=${2:-"edgeconv or dgcnn or reproducible or seg_head or knn_gather 
 cd $GRAFT_REPO_ROOT
 timeout -k 10 700 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "$KEXPR" > gpurun_out/${TAG}_tests.log 2>&1 || echo "TESTS FAILED"
 tail -4 gpurun_out/${TAG}_tests.log
-python bench.py --steps 30 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || (tail -5 gpurun_out/${TAG}_bench.err; exit 1)
+BENCH=$(mktemp -d)/${TAG}_bench
+python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $BENCH.json 2> $BENCH.err || (tail -5 $BENCH.err; exit 1)
 python - <<PY
 import json
-d=json.load(open("gpurun_out/${TAG}_bench.json"))
+d=json.load(open("$BENCH.json"))
 print("ms_per_step", d["ms_per_step"], "value", d["value"])
 print("roofline", {k:d["roofline"][k] for k in ("bound","frac","ceilings","avg_us","nominees_per_query")})
 g=d["roofline_group_hbm"]; print("group us", g["us_per_step_hip_events"], g["us_per_step_graph_replay"], "frac", g["frac_vs_reference_bytes"])

@@ -6,21 +6,21 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/refresh
 rm -rf $out; mkdir -p $out
 cd $R
-python3 bench.py > $out/bench_c2.json 2> $out/bench_c2.err
+python3 bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err
 # config 4 WITH its CPU baseline beside it (one 8192-point cloud per CPU step: bench.py says so in `sample`)
-python3 bench.py --workload c4 --steps 20 --warmup 3 >> $out/bench_other.jsonl 2>> $out/bench_other.err
-for w in c3 c5 c2s c3f c3b; do python3 bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err; done
-python3 bench.py --steps 20 --warmup 3 --inputs surface --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err
-python3 bench.py --workload c4 --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err
-python3 bench.py --workload c3 --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err
+python3 bench.py --full --workload c4 --steps 20 --warmup 3 >> $out/bench_other.jsonl 2>> $out/bench_other.err
+for w in c3 c5 c2s c3f c3b; do python3 bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err; done
+python3 bench.py --full --steps 20 --warmup 3 --inputs surface --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err
+python3 bench.py --full --workload c4 --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err
+python3 bench.py --full --workload c3 --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline >> $out/bench_other.jsonl 2>> $out/bench_other.err
 python3 tools/bench_infer.py >> $out/bench_other.jsonl 2>> $out/bench_other.err
 cd /tmp; export TMPDIR=/tmp
 # (the raw traces are hundreds of MB and gpurun copies at most 64 MiB back: only the statistics are kept)
 slim() { find $1 -type f ! -name "*kernel_stats.csv" ! -name "*counter_collection.csv" -delete; }
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --min-seconds 0.1 > $out/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --min-seconds 0.1 > $out/stats.log 2>&1
 slim $out/stats
 for w in c3 c4 c5; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$w -- python3 $R/bench.py --workload $w --steps 50 --warmup 5 --no-cpu-baseline --min-seconds 0.1 > $out/stats_$w.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$w -- python3 $R/bench.py --full --workload $w --steps 50 --warmup 5 --no-cpu-baseline --min-seconds 0.1 > $out/stats_$w.log 2>&1
   slim $out/stats_$w
 done
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 $R/bench.py --steps 5 --warmup 3 --eager --no-cpu-baseline --min-seconds 0 > $out/pmc_fetch.log 2>&1

@@ -14,7 +14,7 @@ line = [l for l in open(os.path.join(src, "stats.log")) if '"ms_per_step"' in l]
 prof_ms = json.loads(line)["ms_per_step"]
 bench = json.loads([l for l in open(os.path.join(src, "bench_c2.json")) if l.startswith("{")][-1])
 with open(os.path.join(prof, f"{tag}_bench_c2_kernel_stats.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline\n")
+    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 100 --warmup 5 --no-cpu-baseline\n")
     f.write("# BASELINE config 2 (DGCNN-seg N=2048 k=20, 8 clouds, fp32, CE + generalised Dice, FlatAdam), training step replayed as a\n")
     f.write("# hipGraph; 100 timed replays + warm-up/capture steps + 5 eager steps for the per-entry-point HIP-event timing + 25 replays\n")
     f.write(f"# of the forward kNN+gather group; {prof_ms} ms/step under the profiler, {bench['ms_per_step']} ms/step un-profiled\n")
@@ -33,7 +33,7 @@ for w in ("c3", "c4", "c5"):
         continue
     ln = [l for l in open(os.path.join(src, f"stats_{w}.log")) if '"ms_per_step"' in l][-1]
     with open(os.path.join(prof, f"{tag}_bench_{w}_kernel_stats.csv"), "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload {w} --steps 50 --warmup 5 --no-cpu-baseline --min-seconds 0.1\n")
+        f.write(f"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --workload {w} --steps 50 --warmup 5 --no-cpu-baseline --min-seconds 0.1\n")
         f.write(f"# {json.loads(ln)['config']['workload']}; {json.loads(ln)['ms_per_step']} ms/step under the profiler (warm-up, capture and the eager\n")
         f.write("# per-entry-point timing steps are part of the trace: divide Calls by the fsg adam_flat_kernel row for per-step counts)\n")
         f.write(open(st).read())
