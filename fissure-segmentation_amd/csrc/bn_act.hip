@@ -257,6 +257,121 @@ __global__ __launch_bounds__(256) void bnmax_bwd_kernel(const float *__restrict_
     }
 }
 
+// ---- BatchNorm + LeakyReLU + [max | mean] over the points of each cloud (the global feature of the upstream DGCNN,
+// models/dgcnn_opensrc.py:158-164: conv5 -> cat(adaptive_max_pool1d, adaptive_avg_pool1d)).  The max comes from the
+// selection of bnmax_stats_kernel; the mean needs the activation of every row: one more pass over y with the final
+// mean / invstd sums it per (cloud, tile, channel), bnmaxavg_finish_kernel folds the tiles in ascending order.
+__global__ __launch_bounds__(256) void bnavg_sum_kernel(const float *__restrict__ y, const float *__restrict__ gamma,
+                                                         const float *__restrict__ beta, const float *__restrict__ mean,
+                                                         const float *__restrict__ invstd, int N, int C, float slope,
+                                                         float *__restrict__ sum_part) {
+    __shared__ float red[4][64];
+    const int cg = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = cg * 64 + lane;
+    const int tiles = (N + ROWS - 1) / ROWS;
+    const int b = blockIdx.y / tiles, tile = blockIdx.y - b * tiles;
+    const int n0 = tile * ROWS, n1 = min(N, n0 + ROWS);
+    const float *yb = y + (long)b * N * C;
+    const float a = gamma[c] * invstd[c], bb = beta[c] - mean[c] * a;
+    float s = 0.f;
+#pragma unroll 4
+    for (int n = n0 + wave; n < n1; n += 4) s += lrelu(__builtin_fmaf(yb[(long)n * C + c], a, bb), slope);
+    red[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0) sum_part[(long)blockIdx.y * C + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+
+__global__ __launch_bounds__(256) void bnmaxavg_finish_kernel(const float *__restrict__ sel_val, const int *__restrict__ sel_arg,
+                                                               const float *__restrict__ sum_part,
+                                                               const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                               const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                               int N, int tiles, int C, float slope, float *__restrict__ out,
+                                                               int *__restrict__ arg) {
+    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float bv = -INFINITY, s = 0.f;
+    int ba = 0;
+    for (int t = 0; t < tiles; ++t) {
+        const long o = ((long)b * tiles + t) * C + c;
+        const float v = sel_val[o];
+        const int a = sel_arg[o];
+        if (v > bv || (v == bv && a < ba)) { bv = v; ba = a; }
+        s += sum_part[o];
+    }
+    const float sgn = gamma[c] >= 0.f ? 1.f : -1.f;
+    const float a1 = gamma[c] * invstd[c];
+    arg[(long)b * C + c] = ba;
+    out[(long)b * 2 * C + c] = lrelu(__builtin_fmaf(sgn * bv, a1, beta[c] - mean[c] * a1), slope);
+    out[(long)b * 2 * C + C + c] = s / (float)N;
+}
+
+// dz(b,n,c) = f'(u) (g_max [n = arg] + g_avg / N): the gradient reaching the BatchNorm output, recomputed from y by both passes
+__device__ __forceinline__ float maxavg_dz(float u, float slope, int n, int an, float gmax, float gavg_n) {
+    return (u > 0.f ? 1.f : slope) * ((n == an ? gmax : 0.f) + gavg_n);
+}
+
+// per-(cloud, tile) partial sums of dz and dz * yhat per channel (records of 2C floats, summed by fsg_ec_sum_launch)
+__global__ __launch_bounds__(256) void bnmaxavg_bwd_reduce_kernel(const float *__restrict__ gout, const float *__restrict__ y,
+                                                                   const int *__restrict__ arg, const float *__restrict__ gamma,
+                                                                   const float *__restrict__ beta, const float *__restrict__ mean,
+                                                                   const float *__restrict__ invstd, int N, int C, float slope,
+                                                                   float *__restrict__ partials) {
+    __shared__ float red[2][4][64];
+    const int cg = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = cg * 64 + lane;
+    const int tiles = (N + ROWS - 1) / ROWS;
+    const int b = blockIdx.y / tiles, tile = blockIdx.y - b * tiles;
+    const int n0 = tile * ROWS, n1 = min(N, n0 + ROWS);
+    const float r = invstd[c], mu = mean[c], a = gamma[c] * r, bb = beta[c] - mu * a;
+    const float gmax = gout[(long)b * 2 * C + c], gavg_n = gout[(long)b * 2 * C + C + c] / (float)N;
+    const int an = arg[(long)b * C + c];
+    const float *yb = y + (long)b * N * C;
+    float sb = 0.f, sg = 0.f;
+#pragma unroll 4
+    for (int n = n0 + wave; n < n1; n += 4) {
+        const float yv = yb[(long)n * C + c];
+        const float dz = maxavg_dz(__builtin_fmaf(yv, a, bb), slope, n, an, gmax, gavg_n);
+        sb += dz;
+        sg = __builtin_fmaf(dz, (yv - mu) * r, sg);
+    }
+    red[0][wave][lane] = sb;
+    red[1][wave][lane] = sg;
+    __syncthreads();
+    if (wave == 0) {
+        float *pr = partials + (long)blockIdx.y * 2 * C;
+        pr[c] = (red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane]);
+        pr[C + c] = (red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane]);
+    }
+}
+
+// dy = a (dz - dbeta/M - yhat dgamma/M)   (eval: a dz)
+__global__ __launch_bounds__(256) void bnmaxavg_bwd_apply_kernel(const float *__restrict__ gout, const float *__restrict__ y,
+                                                                  const int *__restrict__ arg, const float *__restrict__ gamma,
+                                                                  const float *__restrict__ beta, const float *__restrict__ mean,
+                                                                  const float *__restrict__ invstd,
+                                                                  const float *__restrict__ dbeta,
+                                                                  const float *__restrict__ dgamma, int B, int N, int C,
+                                                                  int training, float slope, float *__restrict__ gy) {
+    const int cg = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = cg * 64 + lane;
+    const int tiles = (N + ROWS - 1) / ROWS;
+    const int b = blockIdx.y / tiles, tile = blockIdx.y - b * tiles;
+    const int n0 = tile * ROWS, n1 = min(N, n0 + ROWS);
+    const float r = invstd[c], mu = mean[c], a = gamma[c] * r, bb = beta[c] - mu * a;
+    const float gmax = gout[(long)b * 2 * C + c], gavg_n = gout[(long)b * 2 * C + C + c] / (float)N;
+    const int an = arg[(long)b * C + c];
+    const float invM = 1.0f / ((float)B * (float)N);
+    const float db = training ? dbeta[c] * invM : 0.f, dg = training ? dgamma[c] * invM * r : 0.f;
+    const float *yb = y + (long)b * N * C;
+    float *gb = gy + (long)b * N * C;
+#pragma unroll 4
+    for (int n = n0 + wave; n < n1; n += 4) {
+        const float yv = yb[(long)n * C + c];
+        const float dz = maxavg_dz(__builtin_fmaf(yv, a, bb), slope, n, an, gmax, gavg_n);
+        gb[(long)n * C + c] = a * (dz - db - (yv - mu) * dg);
+    }
+}
+
 }  // namespace
 
 extern "C" size_t fsg_bn_act_workspace_bytes(long M, int C) {
@@ -347,5 +462,60 @@ extern "C" int fsg_bn_act_max_bwd_f32(const float *grad_out, const float *y, con
     hipLaunchKernelGGL(bnmax_bwd_kernel, dim3(C / 64, B * tiles), dim3(256), 0, (hipStream_t)stream, grad_out, y, ysel, arg,
                        gamma, beta, mean, invstd, B, N, C, training, slope, grad_y, grad_gamma, grad_beta);
     FSG_CHECK_LAUNCH("fsg_bn_act_max_bwd_f32");
+    return FSG_OK;
+}
+
+extern "C" size_t fsg_bn_act_maxavg_workspace_bytes(int B, int N, int C) {
+    const size_t rec = (size_t)B * fsg_cdiv(N, ROWS);
+    // forward: statistics records + stage, per-tile selection (value, index) and per-tile activation sums; backward: 2C per record
+    return sizeof(float) * (rec * 6 * (size_t)C + fsg_ec_finalize_stage_floats(C));
+}
+
+extern "C" int fsg_bn_act_maxavg_fwd_f32(const float *y, const float *gamma, const float *beta, float *running_mean,
+                                         float *running_var, int B, int N, int C, int training, float momentum, float eps,
+                                         float slope, float *out, int32_t *arg, float *mean, float *invstd, float *workspace,
+                                         fsg_stream_t stream) {
+    FSG_REQUIRE(y && gamma && beta && out && arg && mean && invstd && workspace, "fsg_bn_act_maxavg_fwd_f32: NULL pointer");
+    FSG_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0 && (long)B * fsg_cdiv(N, ROWS) <= 65535,
+                "fsg_bn_act_maxavg_fwd_f32: bad shape B=%d N=%d C=%d (C must be a multiple of 64)", B, N, C);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = fsg_cdiv(N, ROWS), R = B * tiles;
+    float *partials = workspace;
+    float *sel_val = partials + (size_t)R * 3 * C + fsg_ec_finalize_stage_floats(C);
+    int *sel_arg = (int *)(sel_val + (size_t)R * C);
+    float *sum_part = sel_val + (size_t)R * 2 * C;
+    hipLaunchKernelGGL(bnmax_stats_kernel, dim3(C / 64, R), dim3(256), 0, st, y, gamma, N, C, training, partials, sel_val,
+                       sel_arg);
+    FSG_CHECK_LAUNCH("fsg_bn_act_maxavg_fwd_f32/stats");
+    if (training) {
+        const int rc = fsg_ec_finalize_launch(partials, R, C, eps, momentum, mean, invstd, running_mean, running_var, st);
+        if (rc != FSG_OK) return rc;
+    }
+    hipLaunchKernelGGL(bnavg_sum_kernel, dim3(C / 64, R), dim3(256), 0, st, y, gamma, beta, mean, invstd, N, C, slope, sum_part);
+    FSG_CHECK_LAUNCH("fsg_bn_act_maxavg_fwd_f32/sum");
+    hipLaunchKernelGGL(bnmaxavg_finish_kernel, dim3(fsg_cdiv(C, 256), B), dim3(256), 0, st, sel_val, sel_arg, sum_part, gamma,
+                       beta, mean, invstd, N, tiles, C, slope, out, arg);
+    FSG_CHECK_LAUNCH("fsg_bn_act_maxavg_fwd_f32/finish");
+    return FSG_OK;
+}
+
+extern "C" int fsg_bn_act_maxavg_bwd_f32(const float *grad_out, const float *y, const int32_t *arg, const float *gamma,
+                                         const float *beta, const float *mean, const float *invstd, int B, int N, int C,
+                                         int training, float slope, float *grad_y, float *grad_gamma, float *grad_beta,
+                                         float *workspace, fsg_stream_t stream) {
+    FSG_REQUIRE(grad_out && y && arg && gamma && beta && mean && invstd && grad_y && grad_gamma && grad_beta && workspace,
+                "fsg_bn_act_maxavg_bwd_f32: NULL pointer");
+    FSG_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0 && (long)B * fsg_cdiv(N, ROWS) <= 65535,
+                "fsg_bn_act_maxavg_bwd_f32: bad shape B=%d N=%d C=%d (C must be a multiple of 64)", B, N, C);
+    hipStream_t st = (hipStream_t)stream;
+    const int R = B * fsg_cdiv(N, ROWS);
+    hipLaunchKernelGGL(bnmaxavg_bwd_reduce_kernel, dim3(C / 64, R), dim3(256), 0, st, grad_out, y, arg, gamma, beta, mean, invstd,
+                       N, C, slope, workspace);
+    FSG_CHECK_LAUNCH("fsg_bn_act_maxavg_bwd_f32/reduce");
+    const int rc = fsg_ec_sum_launch(workspace, R, C, 2, grad_beta, grad_gamma, st);
+    if (rc != FSG_OK) return rc;
+    hipLaunchKernelGGL(bnmaxavg_bwd_apply_kernel, dim3(C / 64, R), dim3(256), 0, st, grad_out, y, arg, gamma, beta, mean, invstd,
+                       grad_beta, grad_gamma, B, N, C, training, slope, grad_y);
+    FSG_CHECK_LAUNCH("fsg_bn_act_maxavg_bwd_f32/apply");
     return FSG_OK;
 }

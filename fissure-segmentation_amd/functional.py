@@ -1654,6 +1654,55 @@ def bn_act_max(y, bn, slope):
                            float(slope))
 
 
+class _BNActMaxAvg(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, y, gamma, beta, rm, rv, training, momentum, eps, slope):
+        y, gamma, beta = _f32c(y), _f32c(gamma), _f32c(beta)
+        B, N, C = y.shape
+        dev = y.device
+        out = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)
+        arg = torch.empty(B, C, dtype=torch.int32, device=dev)
+        if training:
+            mean = torch.empty(C, dtype=torch.float32, device=dev)
+            invstd = torch.empty(C, dtype=torch.float32, device=dev)
+        else:
+            mean, invstd = rm.detach().float().contiguous(), torch.rsqrt(rv.detach().float() + eps).contiguous()
+        ws = torch.empty(_lib.lib.fsg_bn_act_maxavg_workspace_bytes(B, N, C) // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("fsg_bn_act_maxavg_fwd_f32", _p(y), _p(gamma), _p(beta), _p(rm if training else None),
+                      _p(rv if training else None), B, N, C, int(training), momentum, eps, slope, _p(out), _p(arg),
+                      _p(mean), _p(invstd), _p(ws), _stream())
+        ctx.save_for_backward(y, gamma, beta, mean, invstd, arg)
+        ctx.meta = (B, N, C, bool(training), slope)
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g):
+        y, gamma, beta, mean, invstd, arg = ctx.saved_tensors
+        B, N, C, training, slope = ctx.meta
+        g = _f32c(g)
+        gy = torch.empty_like(y)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        ws = torch.empty(_lib.lib.fsg_bn_act_maxavg_workspace_bytes(B, N, C) // 4, dtype=torch.float32, device=y.device)
+        with torch.cuda.device(y.device):
+            _lib.call("fsg_bn_act_maxavg_bwd_f32", _p(g), _p(y), _p(arg), _p(gamma), _p(beta), _p(mean), _p(invstd),
+                      B, N, C, int(training), slope, _p(gy), _p(dgamma), _p(dbeta), _p(ws), _stream())
+        return gy, dgamma, dbeta, None, None, None, None, None, None
+
+
+def bn_act_maxavg(y, bn, slope):
+    """cat(max, mean) over dim 1 of LeakyReLU(slope)(BatchNorm(y)) for y (B, N, C) -> (B, 2C), without the (B,N,C)
+    activation (models/dgcnn_opensrc.py:158-164)."""
+    _need_gpu(y)
+    training, momentum = _bn_step(bn)
+    track = training and bn.track_running_stats
+    return _BNActMaxAvg.apply(y, bn.weight, bn.bias, bn.running_mean if (track or not training) else None,
+                              bn.running_var if (track or not training) else None, training, momentum, float(bn.eps),
+                              float(slope))
+
+
 def bn_act_supported(y, bn):
     return y.is_cuda and y.dim() == 2 and y.shape[1] % 64 == 0 and bn.affine
 

@@ -9,7 +9,7 @@ from .. import functional as F_hip
 from ..shapes.shape_constructor import get_gaussian, get_plane, get_plane_mesh, get_sphere
 from ..norm import BatchNorm1d, BatchNorm2d
 from .dgcnn import SharedFullyConnected
-from .dgcnn_opensrc import get_graph_feature
+from .dgcnn_opensrc import edgeconv_encoder
 from .modelio import LoadableModel, store_config_args
 
 SHAPE_TYPES = ['sphere', 'gaussian', 'plane']
@@ -35,22 +35,10 @@ class DGCNN_Cls_Encoder(LoadableModel):
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("PC-AE encoder (HIP path) needs its input on the GPU")
-        graph = F_hip.knn_graph(x, self.k, c_knn=3, fix_diag=False) if self.static else None
-        B, _, N = x.shape
-        feats, x_pm = [], None
-        for block in (self.conv1, self.conv2, self.conv3, self.conv4):
-            conv, bn, act = block
-            if F_hip.edgeconv1_supported(conv.out_channels, self.k):  # fused gather+conv+BN+LeakyReLU+max
-                idx = graph if graph is not None else F_hip.knn_graph(x, self.k, fix_diag=False)
-                # the point-major output has two consumers (next block, concatenation): hand the concatenation an alias so
-                # that the two gradients reach the backward kernel separately (summed there, the slice taken by stride)
-                x, x_pm, x_cat = F_hip.edgeconv1(x, idx, conv.weight, bn, act.negative_slope, x_pm=x_pm, both="twice")
-            else:
-                x = block(get_graph_feature(x, k=self.k, idx=graph)).max(dim=-1)[0]
-                x_pm = x_cat = x.transpose(1, 2).contiguous()
-            feats.append(x_cat)
+        B, N = x.shape[0], x.shape[2]
         conv5, bn5, act5 = self.conv5
-        y = F_hip.linear_pm(torch.cat(feats, dim=2).view(B * N, -1), conv5.weight.view(conv5.out_channels, -1))
+        y = F_hip.linear_pm(edgeconv_encoder((self.conv1, self.conv2, self.conv3, self.conv4), x, self.k, self.static),
+                            conv5.weight.view(conv5.out_channels, -1))
         if conv5.out_channels % 64 == 0:   # BN + LeakyReLU + max over the points, activation never materialised
             code = F_hip.bn_act_max(y.view(B, N, -1), bn5, act5.negative_slope)
         else:

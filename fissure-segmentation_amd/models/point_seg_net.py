@@ -8,6 +8,19 @@ import torch
 from .modelio import LoadableModel, store_config_args
 
 
+def ensemble_batchable(net, pc):
+    """The runs of a test-time ensembling are independent clouds iff nothing couples the samples of a batch: eval mode with
+    every BatchNorm on its running statistics and every dropout off.  Under autograd the sequential form is kept too."""
+    if net.training or torch.is_grad_enabled() or not pc.is_cuda or pc.dim() != 3 or pc.dtype != torch.float32:
+        return False
+    for m in net.modules():
+        if isinstance(m, torch.nn.modules.batchnorm._NormBase) and (m.training or m.running_mean is None):
+            return False
+        if isinstance(m, torch.nn.modules.dropout._DropoutNd) and m.training:
+            return False
+    return True
+
+
 class PointSegmentationModelBase(LoadableModel, ABC):
     @store_config_args
     def __init__(self, in_features, num_classes, **kwargs):
@@ -23,18 +36,7 @@ class PointSegmentationModelBase(LoadableModel, ABC):
     ensemble_max_clouds = 64
 
     def _ensemble_batchable(self, pc):
-        """The runs of the ensembling are independent clouds iff nothing couples the samples of a batch: eval mode with
-        every BatchNorm on its running statistics.  Under autograd the sequential form is kept too."""
-        if self.training or torch.is_grad_enabled() or not pc.is_cuda or pc.dim() != 3 or pc.dtype != torch.float32:
-            return False
-        if self.num_classes > 32:
-            return False
-        for m in self.modules():
-            if isinstance(m, torch.nn.modules.batchnorm._NormBase) and (m.training or m.running_mean is None):
-                return False
-            if isinstance(m, torch.nn.modules.dropout._DropoutNd) and m.training:
-                return False
-        return True
+        return self.num_classes <= 32 and ensemble_batchable(self, pc)
 
     def _ensemble_pass(self, pc, pts, acc):
         """acc[..., pts[r]] += softmax(self(pc[..., pts[r]])) for all runs r, in run order: the subsets go through the net

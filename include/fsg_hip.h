@@ -281,6 +281,26 @@ int fsg_bn_act_max_bwd_f32(const float *grad_out, const float *y, const float *y
                            fsg_stream_t stream);
 
 /*
+ * BatchNorm + LeakyReLU + [max | mean] over the N points of each cloud: the global feature of the upstream DGCNN
+ * (models/dgcnn_opensrc.py:158-164: conv5 = Conv1d -> BatchNorm1d -> LeakyReLU, then
+ * cat(adaptive_max_pool1d, adaptive_avg_pool1d)).  y (B,N,C) pre-norm rows, C % 64 == 0 -> out (B,2C) =
+ * [max_n a | mean_n a], a = LeakyReLU(BN(y)); saved: arg (B,C) the point of the max (lowest index on ties).
+ * mean/invstd are outputs when training (batch statistics over B*N rows, running statistics updated in place with
+ * momentum), inputs otherwise.  Two reads of y; the activation is never written.
+ * Backward: grad_out (B,2C) -> grad_y (B,N,C) = BN-backward of f'(u) (g_max [n = arg] + g_avg / N), grad_gamma,
+ * grad_beta (fixed-order sums, no atomics).  workspace: fsg_bn_act_maxavg_workspace_bytes(B, N, C) bytes, both passes.
+ */
+size_t fsg_bn_act_maxavg_workspace_bytes(int B, int N, int C);
+int fsg_bn_act_maxavg_fwd_f32(const float *y, const float *gamma, const float *beta, float *running_mean,
+                              float *running_var, int B, int N, int C, int training, float momentum, float eps,
+                              float slope, float *out, int32_t *arg, float *mean, float *invstd, float *workspace,
+                              fsg_stream_t stream);
+int fsg_bn_act_maxavg_bwd_f32(const float *grad_out, const float *y, const int32_t *arg, const float *gamma,
+                              const float *beta, const float *mean, const float *invstd, int B, int N, int C,
+                              int training, float slope, float *grad_y, float *grad_gamma, float *grad_beta,
+                              float *workspace, fsg_stream_t stream);
+
+/*
  * Chamfer nearest neighbour, one direction: replaces the pytorch3d.loss.chamfer_distance call of
  * losses/chamfer_loss.py:19 (and losses/mesh_loss.py:29-31, train_pc_ae.py:88).
  *   x (B,N,3), y (B,M,3) fp32 -> dist (B,N) = min_j |x_i - y_j|^2, arg (B,N) int32 (lowest j on ties)

@@ -75,3 +75,25 @@ if "chamfer" in which:
         a = torch.rand(B, N, 3, device=dev); b = torch.rand(B, N, 3, device=dev)
         med, mn = timeit(lambda: F.chamfer_nn(a, b))
         print(f"chamfer_nn B={B} N={N}: median {med:8.1f} us min {mn:8.1f}")
+if "maxavg" in which:   # conv5's BatchNorm + LeakyReLU + [max | mean] pooling at the DG-SSM shape: fused vs torch composition
+    from fissure_segmentation_amd.norm import BatchNorm1d
+    B, N, C = 32, 1024, 1024
+    nbytes = B * N * C * 4
+    bn = BatchNorm1d(C).to(dev).train()
+    y = torch.randn(B, N, C, device=dev).requires_grad_(True)
+    g = torch.randn(B, 2 * C, device=dev)
+
+    def torch_form(y):
+        a = torch.nn.functional.leaky_relu(bn(y.view(B * N, C)), 0.2).view(B, N, C)
+        return torch.cat((a.max(dim=1)[0], a.mean(dim=1)), 1)
+    for name, fn, fwd_bytes, bwd_bytes in (("fused fsg_bn_act_maxavg", lambda y: F.bn_act_maxavg(y, bn, 0.2), 2 * nbytes, 3 * nbytes),
+                                           ("torch BN+LeakyReLU+max+mean", torch_form, None, None)):
+        med_f, _ = timeit(lambda: fn(y))
+        out = fn(y)
+        med_fb, _ = timeit(lambda: torch.autograd.grad(fn(y), y, g))
+        med_b = med_fb - med_f
+        line = f"maxavg B={B} N={N} C={C} {name:30s}: fwd {med_f:8.1f} us  bwd {med_b:8.1f} us (fwd+bwd {med_fb:8.1f})"
+        if fwd_bytes:
+            line += (f"  fwd {fwd_bytes / med_f / 1e3:6.0f} GB/s ({fwd_bytes / med_f / 8e6:.0%} of 8 TB/s)"
+                     f"  bwd {bwd_bytes / med_b / 1e3:6.0f} GB/s ({bwd_bytes / med_b / 8e6:.0%})")
+        print(line)

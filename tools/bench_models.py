@@ -39,7 +39,7 @@ def run(name, net, x, lossfn, steps=10, warm=3):
     pts = x.shape[0] * x.shape[2]
     print(f"{name:55s} {1e3*dt:9.2f} ms/step  {pts/dt/1e6:7.3f} M points/s  loss {float(l):.4f}")
 
-which = sys.argv[1:] or ["pt", "ae", "c4"]
+which = sys.argv[1:] or ["pt", "ae", "c4", "dgssm"]
 torch.manual_seed(0)
 if "pt" in which:
     for B in (8,):
@@ -53,3 +53,9 @@ if "ae" in which:
 if "c4" in which:
     x = torch.rand(4, 3, 8192, device=dev) * 2 - 1; y = torch.randint(0, 4, (4, 8192), device=dev)
     run("C4 shape DGCNN-seg N=8192 k=40 B=4/GPU (eager, fp32)", DGCNNSeg(k=40, in_features=3, num_classes=4).to(dev).train(), x, lambda o: F.cross_entropy(o, y))
+if "dgssm" in which:   # DG-SSM backbone at its defaults (cli/cli_args.py:15,80,81; dg_ssm.py:107-112)
+    from types import SimpleNamespace
+    from fissure_segmentation_amd.models.dgcnn_opensrc import DGCNN
+    x = torch.rand(32, 3, 1024, device=dev) * 2 - 1; target = torch.randn(32, 12, device=dev)
+    net = DGCNN(SimpleNamespace(k=20, emb_dims=1024, dropout=0., static=False), 3, 12).to(dev).train()
+    run("DG-SSM upstream DGCNN B=32 N=1024 k=20 emb=1024 MSE (eager)", net, x, lambda o: F.mse_loss(o.squeeze(-1), target))
