@@ -1816,6 +1816,66 @@ def chamfer_nn(x, y):
     return _ChamferNN.apply(x, y)
 
 
+# ------------------------------------------------------------------ DG-SSM: shape-model decode + similarity transform
+SSM_MAX_MODES = 64
+
+
+class _SSMDecodeAffine(torch.autograd.Function):
+    """shape_model/ssm.py:74-83 + models/dg_ssm.py:133-135 (compose_transform, transform_points): one launch forward, two
+    backward; the decoded shape is recomputed in the backward, mean and eigenvectors are frozen (ssm.py:33)"""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, w, mean, evec, v, s, tr):
+        wc, mc, ec = _f32c(w), _f32c(mean), _f32c(evec)
+        B, M = wc.shape
+        P = mc.numel() // 3
+        affine = v is not None
+        vc, sc, tc = (_f32c(v), _f32c(s), _f32c(tr)) if affine else (None, None, None)
+        out = torch.empty(B, P, 3, dtype=torch.float32, device=w.device)
+        with torch.cuda.device(w.device):
+            _lib.call("fsg_ssm_decode_fwd_f32", _p(wc), _p(mc), _p(ec), _p(vc), _p(sc), _p(tc), B, P, M, _p(out), _stream())
+        ctx.save_for_backward(wc, mc, ec, vc, sc)
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g):
+        wc, mc, ec, vc, sc = ctx.saved_tensors
+        B, M = wc.shape
+        P = mc.numel() // 3
+        dev = wc.device
+        dw = torch.empty_like(wc)
+        dv, ds, dt = (torch.empty(B, 3, dtype=torch.float32, device=dev) for _ in range(3)) if vc is not None else (None,) * 3
+        nbytes = _lib.lib.fsg_ssm_decode_bwd_workspace_bytes(B, P, M)
+        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("fsg_ssm_decode_bwd_f32", _p(_f32c(g)), _p(wc), _p(mc), _p(ec), _p(vc), _p(sc), B, P, M, _p(dw), _p(dv),
+                      _p(ds), _p(dt), _p(ws), nbytes, _stream())
+        return dw, None, None, dv, ds, dt
+
+
+def ssm_decode_affine(w, mean, evec, v=None, s=None, tr=None):
+    """w (B,M) mode weights, mean (3P) [or (1,3P)], evec (3P,M) [or (1,3P,M)] -> (B,P,3): the decoded shapes
+    mean + evec w, moved -- when v, s, tr (B,3) are given -- by x -> (x R(v)) * s + tr with R = so3_exp_map(v) in the
+    row-vector convention of augmentations.Transform3d.  Differentiable in w, v, s, tr; s may be (B,1)."""
+    _need_gpu(w, mean, evec, v, s, tr)
+    evec = evec.reshape(-1, evec.shape[-1])
+    mean = mean.reshape(-1)
+    if w.dim() != 2 or w.shape[1] != evec.shape[1] or mean.numel() != evec.shape[0] or mean.numel() % 3 != 0:
+        raise ValueError(f"expected w (B,M), mean (3P), evec (3P,M), got {tuple(w.shape)}, {tuple(mean.shape)}, "
+                         f"{tuple(evec.shape)}")
+    if (v is None) != (s is None) or (v is None) != (tr is None):
+        raise ValueError("v, s and tr come together (all or none)")
+    if v is not None:
+        B = w.shape[0]
+        if tuple(v.shape) != (B, 3) or tuple(tr.shape) != (B, 3) or s.dim() != 2 or s.shape[0] != B or s.shape[1] not in (1, 3):
+            raise ValueError(f"expected v, tr (B,3) and s (B,3) or (B,1), got {tuple(v.shape)}, {tuple(tr.shape)}, "
+                             f"{tuple(s.shape)}")
+        s = s.expand(B, 3)
+    return _SSMDecodeAffine.apply(w, mean, evec, v, s, tr)
+
+
 # ------------------------------------------------------------------ segmentation loss (losses/nnu_loss.py:6-19)
 class _NNULoss(torch.autograd.Function):
     @staticmethod

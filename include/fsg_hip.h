@@ -548,6 +548,29 @@ int fsg_sample_transform_f32(const float *x, int B, int C, int64_t N, const int6
                              float *out, fsg_stream_t stream);
 
 /*
+ * Shape-model decode + similarity transform, DG-SSM's step behind its backbone: replaces shape_model/ssm.py:74-83
+ * (SSM.decode: mean + eigenvectors x weights, vector2shape) and, with v / s / tr, models/dg_ssm.py:133-135
+ * (augmentations.py:78-88 compose_transform: so3_exp_map, rotate, scale, translate; :103-113 transform_points) in ONE launch:
+ *   w (B,M) mode weights;  mean (3P);  evec (3P,M) row-major;  v, s, tr (B,3) axis-angle rotation, scaling, translation
+ *   x[b,p,:]   = mean[p,:] + sum_m evec[3p..3p+2, m] w[b,m]
+ *   R_b        = I + a K + b K^2,  K = hat(v_b),  t = sqrt(max(|v_b|^2, 1e-4)),  a = sin t / t,  b = (1 - cos t) / t^2
+ *   out[b,p,:] = (x[b,p,:] R_b) * s_b + tr_b            (B,P,3), row-vector convention
+ *   v == NULL (then s == tr == NULL): out = x, the decode alone (predict_affine_params=False).
+ * _bwd (two launches): grad_out (B,P,3) -> grad_w (B,M), grad_v, grad_s, grad_tr (B,3), all overwritten; x is recomputed;
+ *   grad_v is the closed-form derivative of R_b, with t constant where |v_b|^2 < 1e-4 (as torch.clamp makes it); v == NULL:
+ *   grad_w only (s and the three small gradients NULL).  mean and evec get no gradient (shape_model/ssm.py:33).  Every sum
+ *   over the points runs in a fixed order without atomics.  workspace: the _workspace_bytes query, 4-byte aligned.
+ * Limits: P >= 1, B <= 65535, 1 <= M <= FSG_SSM_MAX_MODES (FSG_ERR_UNSUPPORTED above).
+ */
+#define FSG_SSM_MAX_MODES 64
+size_t fsg_ssm_decode_bwd_workspace_bytes(int B, int P, int M);
+int fsg_ssm_decode_fwd_f32(const float *w, const float *mean, const float *evec, const float *v, const float *s,
+                           const float *tr, int B, int P, int M, float *out, fsg_stream_t stream);
+int fsg_ssm_decode_bwd_f32(const float *grad_out, const float *w, const float *mean, const float *evec, const float *v,
+                           const float *s, int B, int P, int M, float *grad_w, float *grad_v, float *grad_s, float *grad_tr,
+                           void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+
+/*
  * Column sums of a narrow row-major matrix: out[c] = sum_m x[m*C + c], C a power of two <= 32 -- the bias gradient of the
  * last point-wise layer (models/dgcnn.py:146, Conv1d(128, num_classes) with bias) over B*N rows.  One workgroup, fixed
  * summation order.

@@ -75,6 +75,23 @@ if "chamfer" in which:
         a = torch.rand(B, N, 3, device=dev); b = torch.rand(B, N, 3, device=dev)
         med, mn = timeit(lambda: F.chamfer_nn(a, b))
         print(f"chamfer_nn B={B} N={N}: median {med:8.1f} us min {mn:8.1f}")
+if "ssmdec" in which:   # DG-SSM's decode + similarity transform: fused stage vs the torch composition of the same math
+    from fissure_segmentation_amd.augmentations import so3_exp_map
+    for (B, P, M) in [(32, 2048, 20), (32, 2048, 32), (4, 4097, 64)]:
+        mean, evec = torch.rand(3 * P, device=dev) * 2 - 1, torch.randn(3 * P, M, device=dev) / M ** 0.5
+        w, v, s, tr = (t.requires_grad_(True) for t in (torch.randn(B, M, device=dev), 0.5 * torch.randn(B, 3, device=dev),
+                                                        torch.rand(B, 3, device=dev) + 0.5, torch.randn(B, 3, device=dev)))
+        g = torch.randn(B, P, 3, device=dev)
+
+        def torch_form():   # SSM.decode + compose_transform + transform_points without the 4x4 detour (fewer launches than the reference)
+            x = (mean[None] + torch.matmul(evec[None], w[:, :, None]).squeeze(-1)).unflatten(-1, (P, 3))
+            return torch.bmm(x, so3_exp_map(v)) * s[:, None, :] + tr[:, None, :]
+        for name, fn in (("fused fsg_ssm_decode", lambda: F.ssm_decode_affine(w, mean, evec, v, s, tr)), ("torch composition", torch_form)):
+            med_f, min_f = timeit(fn, iters=100, warm=10)
+            out = fn()
+            med_b, min_b = timeit(lambda: torch.autograd.grad(out, (w, v, s, tr), g, retain_graph=True), iters=100, warm=10)
+            print(f"ssmdec B={B} P={P} M={M} {name:22s}: fwd median {med_f:7.1f} us (min {min_f:7.1f})  "
+                  f"bwd median {med_b:7.1f} us (min {min_b:7.1f})")
 if "maxavg" in which:   # conv5's BatchNorm + LeakyReLU + [max | mean] pooling at the DG-SSM shape: fused vs torch composition
     from fissure_segmentation_amd.norm import BatchNorm1d
     B, N, C = 32, 1024, 1024

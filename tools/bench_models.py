@@ -13,8 +13,12 @@ dev = torch.device("cuda:0")
 GRAPH = "--graph" in sys.argv
 if GRAPH: sys.argv.remove("--graph")
 
-def run(name, net, x, lossfn, steps=10, warm=3):
-    opt = torch.optim.Adam(net.parameters(), lr=1e-3, capturable=GRAPH, fused=True)
+def run(name, net, x, lossfn, steps=10, warm=3, flat_adam=False):
+    if flat_adam:
+        from fissure_segmentation_amd.optim import FlatAdam
+        opt = FlatAdam(net.parameters(), lr=1e-3, capturable=GRAPH)
+    else:
+        opt = torch.optim.Adam(net.parameters(), lr=1e-3, capturable=GRAPH, fused=True)
     def step():
         opt.zero_grad(set_to_none=True); l = lossfn(net(x)); l.backward(); opt.step(); return l
     if GRAPH:   # static shapes: capture fwd + loss + bwd + Adam once, replay
@@ -59,3 +63,19 @@ if "dgssm" in which:   # DG-SSM backbone at its defaults (cli/cli_args.py:15,80,
     x = torch.rand(32, 3, 1024, device=dev) * 2 - 1; target = torch.randn(32, 12, device=dev)
     net = DGCNN(SimpleNamespace(k=20, emb_dims=1024, dropout=0., static=False), 3, 12).to(dev).train()
     run("DG-SSM upstream DGCNN B=32 N=1024 k=20 emb=1024 MSE (eager)", net, x, lambda o: F.mse_loss(o.squeeze(-1), target))
+if "dgssm_full" in which:   # the whole DG-SSM step: backbone + three heads + fused decode/transform + DGSSMLoss + FlatAdam
+    from fissure_segmentation_amd.losses.dgssm_loss import DGSSMLoss
+    from fissure_segmentation_amd.models.dg_ssm import DGSSM
+    B, P, M = 32, 2048, 20
+    net = DGSSM(k=20, in_features=3, ssm_modes=M)
+    evec = torch.linalg.qr(torch.randn(3 * P, M))[0]
+    net.ssm.register_parameters_from_state_dict({"num_modes": torch.tensor(M), "percent_of_variance": torch.tensor(0.95),
+                                                 "mean_shape": torch.rand(1, 3 * P) * 2 - 1,
+                                                 "eigenvalues": 1.2 ** -torch.arange(M, dtype=torch.float32)[None], "eigenvectors": evec[None]})
+    net = net.to(dev).train()
+    x = torch.rand(B, 3, 1024, device=dev) * 2 - 1
+    with torch.no_grad():
+        tw = net.ssm.random_samples(B)
+        target = (net.ssm.decode(tw), tw, torch.cat([0.1 * torch.randn(B, 6, device=dev), 1 - 0.1 * torch.rand(B, 3, device=dev)], 1))
+    crit = DGSSMLoss()
+    run(f"DG-SSM full step B={B} N=1024 k=20 P={P} M={M} DGSSMLoss FlatAdam (eager)", net, x, lambda o: crit(o, target)[0], flat_adam=True)
