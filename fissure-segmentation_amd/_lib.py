@@ -126,6 +126,9 @@ for _name, (_args, _res) in SIGNATURES.items():
     _fn.argtypes, _fn.restype = _args, _res
 
 KNN_FIX_DIAG, KNN_DROP_FIRST, KNN_FORCE_ROWS, KNN_FORCE_MFMA, KNN_MAX_K = 1, 2, 4, 8, 64
+# debug / cross-check bits of the kNN `flags` (csrc/knn_internal.h has the meanings; any other bit is rejected by the library)
+KNN_DBG_HALF_CHUNKS, KNN_DBG_TWO_PHASE, KNN_DBG_ALL_SLOW, KNN_DBG_STATS = 1 << 11, 1 << 21, 1 << 22, 1 << 25
+KNN_DBG_STAMPS, KNN_DBG_ONE_LAUNCH, KNN_DBG_BF16 = 1 << 28, 1 << 29, 1 << 30
 
 
 _timing = None  # {entry point: [(start_event, end_event), ...]} while bench.py measures kernel durations

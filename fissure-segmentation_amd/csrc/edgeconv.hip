@@ -24,7 +24,7 @@
 // cloud's P rows.
 #include <type_traits>
 
-#include "fsg_common.h"
+#include "knn_internal.h"
 
 size_t fsg_ec_finalize_stage_floats(int Co);
 int fsg_ec_finalize_launch(const float *partials, int R, int Co, float eps, float momentum, float *mean, float *invstd,
@@ -872,9 +872,6 @@ int fsg_ec_finalize_launch(const float *partials, int R, int Co, float eps, floa
     FSG_CHECK_LAUNCH("edgeconv/finalize");
     return FSG_OK;
 }
-
-int fsg_knn_split_ws_pointers(void *ws, size_t ws_bytes, int B, int N, int c_knn, float **xx, float **xs, void **cand,
-                              float **cscale);       // knn_split.hip
 
 // apply + the next graph build's prep (out_pm required, Co == 64, N % 64 == 0, N inside the coarse-sweep kernel's envelope)
 int fsg_ec_apply_prep_launch(const float *ysel, const float *gamma, const float *beta, const float *mean, const float *invstd,

@@ -14,7 +14,9 @@
 
 #include <stdlib.h>
 
-#include "fsg_common.h"
+#include <type_traits>
+
+#include "knn_internal.h"
 
 namespace {
 
@@ -113,12 +115,6 @@ __global__ __launch_bounds__(BLOCK) void knn_dense_rows_kernel(
 
 }  // namespace
 
-int fsg_knn_rows_mfma_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k,
-                             int flags, int32_t *idx_out, float *dist_out, float *xx_scratch, hipStream_t st);
-size_t fsg_knn_split_workspace_bytes(int B, int N, int c_knn);
-int fsg_knn_split_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
-                         int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st);
-
 extern "C" size_t fsg_knn_dense_workspace_bytes(int B, int N, int c_knn) {
     if (B <= 0 || N <= 0 || c_knn <= 0) return 0;
     const size_t xxb = sizeof(float) * (size_t)B * N, sp = fsg_knn_split_workspace_bytes(B, N, c_knn);
@@ -126,12 +122,13 @@ extern "C" size_t fsg_knn_dense_workspace_bytes(int B, int N, int c_knn) {
 }
 
 // Same contract as fsg_knn_dense_f32 with a caller-owned workspace of fsg_knn_dense_workspace_bytes(B, N, c_knn) bytes:
-// inside its envelope the coarse-sweep + exact-refine kernel (knn_split.hip) builds the graph, everything else (and
-// flag 2097152, A/B timing and cross-checks) goes to fsg_knn_dense_f32 with the workspace as its squared-norm scratch.
+// inside its envelope the coarse-sweep + exact-refine kernel (knn_split.hip) builds the graph, everything else (and the
+// KNN_BYPASS_SPLIT bits: cross-checks) goes to fsg_knn_dense_f32 with the workspace as its squared-norm scratch.
 extern "C" int fsg_knn_dense_ws_f32(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k,
                                     int flags, int32_t *idx_out, float *dist_out, void *workspace,
                                     size_t workspace_bytes, fsg_stream_t stream) {
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;
+    FSG_KNN_REQUIRE_FLAGS("fsg_knn_dense_ws_f32", flags);
     FSG_REQUIRE(x && idx_out, "fsg_knn_dense_ws_f32: NULL pointer");
     FSG_REQUIRE(B >= 0 && N > 0 && c_knn > 0, "fsg_knn_dense_ws_f32: bad shape B=%d N=%d c_knn=%d", B, N, c_knn);
     FSG_REQUIRE(k >= 1 && k + drop <= N && k + drop <= FSG_KNN_MAX_K,
@@ -139,22 +136,14 @@ extern "C" int fsg_knn_dense_ws_f32(const float *x, int B, int N, int64_t stride
     FSG_REQUIRE(workspace == nullptr || workspace_bytes >= sizeof(float) * (size_t)B * N,
                 "fsg_knn_dense_ws_f32: workspace of %zu bytes is smaller than the (B,N) squared norms", workspace_bytes);
     if (B == 0) return FSG_OK;
-    if (workspace && !(flags & (2097152 | FSG_KNN_FORCE_ROWS | FSG_KNN_FORCE_MFMA | 4096 | 16384 | 131072 | 2048 | 8192))) {
+    if (workspace && !(flags & KNN_BYPASS_SPLIT)) {
         const int rc = fsg_knn_split_launch(x, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, workspace,
                                             workspace_bytes, (hipStream_t)stream);
         if (rc != FSG_ERR_UNSUPPORTED) return rc;
     }
-    return fsg_knn_dense_f32(x, B, N, stride_b, stride_c, c_knn, k, flags & ~2097152, idx_out, dist_out,
+    return fsg_knn_dense_f32(x, B, N, stride_b, stride_c, c_knn, k, flags & ~KNN_DBG_TWO_PHASE, idx_out, dist_out,
                              static_cast<float *>(workspace), stream);
 }
-
-int fsg_knn_split_launch_ex(const float *x, const float *prepared_xt, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn,
-                            int k, int flags, int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st);
-int fsg_knn_split_launch_pq(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
-                            int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st, const float *pq_w,
-                            int pq_rows, float *pq_out, bool *fused);
-int fsg_knn_pq_rows_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, const float *pq_w,
-                           int pq_rows, float *pq_out, hipStream_t st);
 
 // fsg_knn_dense_ws_f32 over points of up to four channels PLUS their per-point product with a small weight:
 // pq_out (B, N, rows_pq) = x^T w_pq^T, w_pq (rows_pq, c_knn) row-major -- the "one plain GEMM" of the FIRST EdgeConv's contract
@@ -164,6 +153,7 @@ int fsg_knn_pq_rows_launch(const float *x, int B, int N, int64_t stride_b, int64
 extern "C" int fsg_knn_dense_ws_pq_f32(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k,
                                        int flags, int32_t *idx_out, float *dist_out, void *workspace, size_t workspace_bytes,
                                        const float *w_pq, int rows_pq, float *pq_out, fsg_stream_t stream) {
+    FSG_KNN_REQUIRE_FLAGS("fsg_knn_dense_ws_pq_f32", flags);
     FSG_REQUIRE(x && idx_out && w_pq && pq_out, "fsg_knn_dense_ws_pq_f32: NULL pointer");
     FSG_REQUIRE(c_knn >= 1 && c_knn <= 4 && rows_pq >= 1 && 256 % rows_pq == 0,
                 "fsg_knn_dense_ws_pq_f32: needs 1 <= c_knn <= 4 and rows_pq dividing 256; got c_knn=%d rows_pq=%d", c_knn, rows_pq);
@@ -172,10 +162,12 @@ extern "C" int fsg_knn_dense_ws_pq_f32(const float *x, int B, int N, int64_t str
                 B, N, k);
     if (B == 0) return FSG_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (workspace && !(flags & (2097152 | FSG_KNN_FORCE_ROWS | FSG_KNN_FORCE_MFMA | 4096 | 16384 | 131072 | 2048 | 8192))) {
+    if (workspace && !(flags & KNN_BYPASS_SPLIT)) {
         bool fused = false;
-        const int rc = fsg_knn_split_launch_pq(x, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, workspace,
-                                               workspace_bytes, st, w_pq, rows_pq, pq_out, &fused);
+        KnnSplitOpts o;
+        o.pq_w = w_pq, o.pq_rows = rows_pq, o.pq_out = pq_out, o.pq_fused = &fused;
+        const int rc = fsg_knn_split_launch(x, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, workspace, workspace_bytes,
+                                            st, o);
         if (rc == FSG_OK) return fused ? FSG_OK : fsg_knn_pq_rows_launch(x, B, N, stride_b, stride_c, c_knn, w_pq, rows_pq, pq_out, st);
         if (rc != FSG_ERR_UNSUPPORTED) return rc;
     }
@@ -192,11 +184,14 @@ extern "C" int fsg_knn_dense_ws_pq_f32(const float *x, int B, int N, int64_t str
 extern "C" int fsg_knn_dense_prepared_f32(const float *x_pm, int B, int N, int c_knn, int k, int flags, int32_t *idx_out,
                                           float *dist_out, void *workspace, size_t workspace_bytes, fsg_stream_t stream) {
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;
+    FSG_KNN_REQUIRE_FLAGS("fsg_knn_dense_prepared_f32", flags);
     FSG_REQUIRE(x_pm && idx_out && workspace, "fsg_knn_dense_prepared_f32: NULL pointer");
     FSG_REQUIRE(B > 0 && N > 0 && c_knn > 0 && k >= 1 && k + drop <= N && k + drop <= FSG_KNN_MAX_K,
                 "fsg_knn_dense_prepared_f32: bad shape B=%d N=%d c_knn=%d k=%d", B, N, c_knn, k);
-    const int rc = fsg_knn_split_launch_ex(nullptr, x_pm, B, N, 0, 0, c_knn, k, flags, idx_out, dist_out, workspace, workspace_bytes,
-                                           (hipStream_t)stream);
+    KnnSplitOpts o;
+    o.prepared_xt = x_pm;
+    const int rc = fsg_knn_split_launch(nullptr, B, N, 0, 0, c_knn, k, flags, idx_out, dist_out, workspace, workspace_bytes,
+                                        (hipStream_t)stream, o);
     if (rc == FSG_ERR_UNSUPPORTED) fsg_set_error("fsg_knn_dense_prepared_f32: shape outside the prepared path's envelope");
     return rc;
 }
@@ -205,6 +200,7 @@ extern "C" int fsg_knn_dense_f32(const float *x, int B, int N, int64_t stride_b,
                                  int c_knn, int k, int flags, int32_t *idx_out, float *dist_out,
                                  float *xx_scratch, fsg_stream_t stream) {
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;
+    FSG_KNN_REQUIRE_FLAGS("fsg_knn_dense_f32", flags);
     FSG_REQUIRE(x && idx_out, "fsg_knn_dense_f32: NULL pointer");
     FSG_REQUIRE(B >= 0 && N > 0 && c_knn > 0, "fsg_knn_dense_f32: bad shape B=%d N=%d c_knn=%d", B, N, c_knn);
     FSG_REQUIRE(k >= 1 && k + drop <= N && k + drop <= FSG_KNN_MAX_K,
@@ -212,9 +208,9 @@ extern "C" int fsg_knn_dense_f32(const float *x, int B, int N, int64_t stride_b,
     FSG_REQUIRE(N <= 32768, "fsg_knn_dense_f32: N=%d > 32768 unsupported", N);
     if (B == 0) return FSG_OK;
     hipStream_t st = (hipStream_t)stream;
-    // The superseded design kept as a cross-check (first matrix-core kernel, flag 8; 4096 / 16384 were the removed pipeline / filter) is
-    // test / benchmark infrastructure and live in libfsg_hip_experiments.so (csrc/knn_experiments.hip), not in the product.
-    FSG_REQUIRE(!(flags & (FSG_KNN_FORCE_MFMA | 4096 | 16384)),
+    // The superseded design kept as a cross-check (first matrix-core kernel, FSG_KNN_FORCE_MFMA) is test / benchmark
+    // infrastructure and lives in libfsg_hip_experiments.so (csrc/knn_experiments.hip), not in the product.
+    FSG_REQUIRE(!(flags & FSG_KNN_FORCE_MFMA),
                 "fsg_knn_dense_f32: flags %d select an experimental kernel: call fsg_knn_experiment_f32 of "
                 "libfsg_hip_experiments.so", flags);
     if (!(flags & FSG_KNN_FORCE_ROWS)) {  // production path
@@ -222,13 +218,15 @@ extern "C" int fsg_knn_dense_f32(const float *x, int B, int N, int64_t stride_b,
         if (rc != FSG_ERR_UNSUPPORTED) return rc;
     }
     const int Npad = (N + 255) & ~255;
-    auto launch = [&](auto kern, int QB) -> int {
+    auto launch = [&](auto qb) -> int {
+        constexpr int QB = decltype(qb)::value;
+        const auto kern = knn_dense_rows_kernel<QB>;
         const size_t lds = sizeof(float) * ((((size_t)c_knn * QB + QB + 3) & ~(size_t)3) + (size_t)QB * Npad);
         if (lds > 160 * 1024) {
             fsg_set_error("fsg_knn_dense_f32: LDS need %zu B > 160 KiB (N=%d c_knn=%d)", lds, N, c_knn);
             return FSG_ERR_UNSUPPORTED;
         }
-        static FsgLdsGrant grant;  // per instantiation (the lambda is instantiated per kernel)
+        static FsgLdsGrant grant;  // per QB (the lambda's call operator is instantiated per type of qb)
         if (!grant.raise((const void *)kern, lds)) {
             fsg_set_error("fsg_knn_dense_f32: cannot raise dynamic LDS to %zu", lds);
             return FSG_ERR_HIP;
@@ -239,8 +237,8 @@ extern "C" int fsg_knn_dense_f32(const float *x, int B, int N, int64_t stride_b,
         FSG_CHECK_LAUNCH("fsg_knn_dense_f32");
         return FSG_OK;
     };
-    if (N <= 4096) return launch(knn_dense_rows_kernel<8>, 8);
-    if (N <= 8192) return launch(knn_dense_rows_kernel<4>, 4);
-    if (N <= 16384) return launch(knn_dense_rows_kernel<2>, 2);
-    return launch(knn_dense_rows_kernel<1>, 1);
+    if (N <= 4096) return launch(std::integral_constant<int, 8>{});
+    if (N <= 8192) return launch(std::integral_constant<int, 4>{});
+    if (N <= 16384) return launch(std::integral_constant<int, 2>{});
+    return launch(std::integral_constant<int, 1>{});
 }

@@ -6,14 +6,12 @@
 // (round 3 removed the wave-specialised pipeline knn_pipe.hip and the threshold filter knn_filter.hip from the tree; their
 // measurements are in DESIGN.md "What did not work", their code in the history up to round 2.)
 // Same arguments and results as fsg_knn_dense_f32 (include/fsg_hip.h).
-#include "fsg_common.h"
-
-int fsg_knn_mfma_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
-                        int32_t *idx_out, float *dist_out, float *xx_scratch, hipStream_t st);    // knn_mfma.hip
+#include "knn_internal.h"
 
 extern "C" int fsg_knn_experiment_f32(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k,
                                       int flags, int32_t *idx_out, float *dist_out, float *xx_scratch, fsg_stream_t stream) {
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;
+    FSG_KNN_REQUIRE_FLAGS("fsg_knn_experiment_f32", flags);
     FSG_REQUIRE(x && idx_out && xx_scratch, "fsg_knn_experiment_f32: NULL pointer");
     FSG_REQUIRE(B > 0 && N > 0 && c_knn > 0 && k >= 1 && k + drop <= N && k + drop <= FSG_KNN_MAX_K && N <= 32768,
                 "fsg_knn_experiment_f32: bad shape B=%d N=%d c_knn=%d k=%d", B, N, c_knn, k);

@@ -16,7 +16,7 @@
 //   * merge: the 8 sorted partial lists of a query (4 waves x 2 lane halves) are merged by one lane.
 // Keys: distance bits mapped to an order-preserving uint32 (hi) and the candidate index (lo) in one uint64, so
 // ties go to the lower index exactly like the oracle.
-#include "fsg_common.h"
+#include "knn_internal.h"
 
 namespace {
 
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const float *__restrict__
 #pragma unroll
         for (int s = 0; s < CAP; ++s)
             v[s] = (s < cnt) ? (((u64)bkey[s * 64 + lane] << 32) | bidx[s * 64 + lane]) : ~0ull;
-        if (!(flags & 256)) sort64(v);
+        sort64(v);
         const int had = cnt;
         cnt = min(cnt, KK);
 #pragma unroll
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const float *__restrict__
                 float d = tt + xj;
                 if (diag && j == q) d = 0.f;
                 const unsigned key = f2o(d);
-                if (j < N && key <= tau && !(flags & 1024)) {
+                if (j < N && key <= tau) {
                     bkey[cnt * 64 + lane] = key;
                     bidx[cnt * 64 + lane] = (unsigned short)j;
                     ++cnt;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const float *__restrict__
     __syncthreads();
 
     // ---- merge the 8 partial lists of each query (4 waves x 2 halves); one lane per query
-    if (wave == 0 && lane < 32 && q < N && !(flags & 512)) {
+    if (wave == 0 && lane < 32 && q < N) {
         int head[8], len[8];
         u64 cur[8];
 #pragma unroll
@@ -203,7 +203,6 @@ __global__ __launch_bounds__(256) void knn_mfma_kernel(const float *__restrict__
 
 }  // namespace
 
-// returns FSG_ERR_UNSUPPORTED when the shape is outside this kernel's envelope (caller falls back)
 int fsg_knn_mfma_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
                         int32_t *idx_out, float *dist_out, float *xx_scratch, hipStream_t st) {
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;

@@ -1,4 +1,5 @@
-// Dense kNN graph build, production kernel behind fsg_knn_dense_f32 (c_knn <= 128, N <= 65535, k+drop <= 64).
+// Dense kNN graph build, the two-phase kernel: production kernel behind fsg_knn_dense_f32 (c_knn <= 128, N <= 65535, k+drop <= 64),
+// cross-check of the split kernel behind fsg_knn_dense_ws_f32 (KNN_DBG_TWO_PHASE; KNN_DBG_HALF_CHUNKS: its 512-candidate chunks).
 //
 // A 512-thread workgroup owns 32 query points of one cloud and sweeps the candidates in chunks of 1024:
 //   phase A  the 32 x 1024 distance block of the chunk is produced on the matrix cores
@@ -17,21 +18,7 @@
 //            Rows with more than 128 survivors (massive ties) take a slow exact path (K rounds of wave arg-min).
 // Keys: order-preserving uint32 image of the fp32 distance in the high word, candidate index in the low word, so
 // ties go to the lower index exactly like oracle/fsg_oracle.c.
-#include "fsg_common.h"
-
-#ifdef FSG_KNN_STATS
-__device__ unsigned long long fsg_knn_stats[8];
-extern "C" int fsg_debug_knn_stats(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(fsg_knn_stats), sizeof(fsg_knn_stats)) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(fsg_knn_stats), z, sizeof(z)) != hipSuccess) return 1; }
-    return 0;
-}
-#define KSTAT(i, v) atomicAdd(&fsg_knn_stats[i], (unsigned long long)(v))
-#define KSTATMAX(i, v) atomicMax(&fsg_knn_stats[i], (unsigned long long)(v))
-#else
-#define KSTAT(i, v) ((void)0)
-#define KSTATMAX(i, v) ((void)0)
-#endif
+#include "knn_internal.h"
 
 namespace {
 
@@ -147,7 +134,7 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: scalar
     const int l15 = lane & 15, l4 = lane >> 4;
     int b = blockIdx.y, q0 = blockIdx.x * QB;
-    if (!SEG && !(flags & 65536)) {   // flag 65536: plain placement (A/B timing)
+    if (!SEG) {
         // XCD-aware placement: workgroups go to the 8 XCDs round-robin by linear id, so consecutive ids of one cloud
         // would spread every cloud over all eight L2s.  Renumber so that XCD x owns a contiguous 1/8 of the (cloud, tile)
         // space: with 8 clouds each L2 holds exactly one cloud's features.
@@ -321,8 +308,7 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
     // tile tl of the chunk at c0: distances into the LDS block
     auto tile = [&](const float (&bt)[KS], float xc, int c0, int tl) {
         float *dst = rows + (l4 * 4) * STRIDE + tl * 16 + l15;
-        if (c0 + tl * 16 >= N || (flags & 512)) {   // tile beyond the cloud (wave-uniform): nothing to compute
-                                                    // (flag 512: timing ablation of phase A)
+        if (c0 + tl * 16 >= N) {   // tile beyond the cloud (wave-uniform): nothing to compute
 #pragma unroll
             for (int r = 0; r < 8; ++r) dst[((r >> 2) * 16 + (r & 3)) * STRIDE] = INFINITY;
             return;
@@ -358,13 +344,13 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
         }
     };
     // WIDE operand loads (two-phase chunks, N % 4 == 0): the 1024 loads of four bytes per lane that a workgroup issued per
-    // chunk kept the texture path busy for as long as the matrix cores (in-kernel cycle stamps, tools/knn_phase_cycles.py:
+    // chunk kept the texture path busy for as long as the matrix cores (in-kernel cycle stamps:
     // phase A took 2.8x its MFMA time, and with the products switched off the loads alone cost the same again).  A wave
     // now owns 64 consecutive candidates per group: lane (l4, l15) loads channel 4s + l4 of the FOUR candidates
     // 4 l15 .. 4 l15 + 3 with one 16-byte load (full 256-byte row segments), and the four "virtual tiles" u = 0..3 (candidate
     // 4 l15 + u in lane l15) reuse the loaded registers -- a quarter of the load instructions.  No software pipelining: the
     // other three waves of the SIMD keep the matrix pipe busy while one waits for its loads.
-    const bool wide = !SEG && (N & 3) == 0 && !(flags & 1048576);   // flag 1048576: the four-byte loads (A/B timing)
+    const bool wide = !SEG && (N & 3) == 0;
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(xxb), 0, SEG ? 0 : N * 4, 0x00020000);
     auto ld4 = [&](f32x4 (&bt)[KS], f32x4 &xt, unsigned col) {
@@ -378,7 +364,7 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
     auto gtile = [&](const float (&bt)[KS], float xc, int c0, int cb, int u) {
         const int colrel = cb + 4 * l15 + u;
         float *dst = rows + (l4 * 4) * STRIDE + colrel;
-        if (c0 + cb >= N || (flags & 512)) {   // group beyond the cloud (wave-uniform) / timing ablation of phase A
+        if (c0 + cb >= N) {   // group beyond the cloud (wave-uniform)
 #pragma unroll
             for (int r = 0; r < 8; ++r) dst[((r >> 2) * 16 + (r & 3)) * STRIDE] = INFINITY;
             return;
@@ -465,7 +451,7 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
     // the expected number of survivors per row and epoch stays about K -- one small merge per row and epoch.
     int done = 0;
     while (done < nch) {
-        const bool stream_ok = STREAM && !SEG && done > 0 && !(flags & 1024);   // flag 1024: every chunk through LDS
+        const bool stream_ok = STREAM && !SEG && done > 0;
         // epoch length: as many chunks as were seen before (survivors per row ~ K), or more while the expected number of
         // survivors K * span / done stays well inside the list (factor 1.5 of headroom)
         const int span = stream_ok ? min(nch - done, done) : 1;
@@ -557,14 +543,12 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
                     // -------------------------------------------------------- streamed epoch: small merge per row, or redo
                     const int mine_l = tid < QB ? lcount[tid] : 0;
                     redo = __syncthreads_or(mine_l > LCAP) != 0;
-                    if (tid == 0) { KSTAT(0, 1); KSTAT(1, redo ? 1 : 0); KSTAT(5, span); }
-                    if (tid < QB) { KSTAT(2, mine_l); KSTAT(3, 1); KSTATMAX(4, mine_l); }
                     if (redo) {
                         if (tid < QB) lcount[tid] = 0;
                         break;   // attempt 1 (the barrier above orders the list reads before the block is rewritten)
                     }
                     for (int qi = wave; qi < QB; qi += WAVES) {
-                        if (q0 + qi >= NQ || (flags & 256)) break;
+                        if (q0 + qi >= NQ) break;
                         const int lc = lcount[qi];
                         if (lc > 0) {
                             u64 *sv = reinterpret_cast<u64 *>(rows + qi * STRIDE);
@@ -599,7 +583,7 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
                 // 560 vs 543 us at N=8192 k=40: the selection is not bound by the latency of one chain.)
                 // ---------------------------------------------------------------- phase B: exact selection, one wave per row
                 for (int qi = wave; qi < QB; qi += WAVES) {
-                    if (q0 + qi >= NQ || (flags & 256)) break;  // flag 256: timing ablation of phase B
+                    if (q0 + qi >= NQ) break;
                     const float *row = rows + qi * STRIDE;
                     float v[VPL];
         #pragma unroll
@@ -747,7 +731,6 @@ __global__ __launch_bounds__(256) void knn_sqnorm2_kernel(const float *__restric
 
 }  // namespace
 
-// returns FSG_ERR_UNSUPPORTED when the shape is outside this kernel's envelope (caller falls back)
 int fsg_knn_rows_mfma_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
                              int32_t *idx_out, float *dist_out, float *xx_scratch, hipStream_t st) {
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;
@@ -774,32 +757,28 @@ int fsg_knn_rows_mfma_launch(const float *x, int B, int N, int64_t stride_b, int
     } while (0)
     const bool small_k = k + drop <= 32;                      // carried list fits 32 slots
     // 512-candidate chunks fit two workgroups per CU in LDS but not in registers (241 VGPRs -> 2 waves/SIMD): measured
-    // 148 us against 136 us for the 1024-candidate chunks at C=64, so they are opt-in (flag 2048, tests)
-    const bool half = small_k && (flags & 2048);
-    // 16 waves per workgroup wherever the registers allow (both phases are latency-bound); flag 8192: the 8-wave variants
-    const bool w8 = (flags & 8192) != 0;
-    // streamed selection (STREAM = true, 512-candidate chunks, 16 waves), formerly flag 131072.  Exact (same parity suite) but
-    // MEASURED SLOWER than the two-phase kernel and therefore opt-in: B=8 N=2048 k=20 C=64 101 vs 88 us, C=3 70 vs 52 us;
-    // B=4 N=8192 k=40 C=64 567 vs 542 us (tools/knn_ablate_phases.py, eager timing incl. the squared-norm launch).  What the
-    // instrumented build (-DFSG_KNN_STATS; the statistics script went with the streamed variant in round 3) showed: the filter works as designed -- 57 survivors
-    // per row for a 1536-candidate epoch (expected 60), 3.7 % of the workgroups redo an epoch -- but a streamed epoch costs
-    // as much as the distance block + full selection it replaces: with 2-6 tiles per wave and epoch the operand-load
-    // latency, the two barriers and the rank-by-counting merge (which dominates the selection either way) are all exposed,
-    // and 512-candidate chunks are 14 us slower than 1024-candidate ones for the same reason.  Two co-resident 8-wave
-    // workgroups per CU (flag 262144: 256-candidate first chunk, 50 KB of LDS, 101 VGPRs) change nothing: 101 us.
-    // (round 3: the streamed instantiations are no longer built into the library -- the STREAM template paths above are kept as
-    // the record of the design; re-enable by dispatching FSG_KNN_RMQS(..., true) on a flag here)
-    if (c_knn <= 4) { if (!w8) FSG_KNN_RM(1, 16, 128, 1024, 64); else FSG_KNN_RM(1, 8, 128, 1024, 64); }
-    else if (c_knn <= 16) { if (!w8) FSG_KNN_RM(4, 16, 128, 1024, 64); else FSG_KNN_RM(4, 8, 128, 1024, 64); }
+    // 148 us against 136 us for the 1024-candidate chunks at C=64, so they are opt-in (KNN_DBG_HALF_CHUNKS, tests)
+    const bool half = small_k && (flags & KNN_DBG_HALF_CHUNKS);
+    // 16 waves per workgroup wherever the registers allow (both phases are latency-bound).
+    // Streamed selection (STREAM = true, 512-candidate chunks, 16 waves) is exact (same parity suite) but MEASURED SLOWER than
+    // the two-phase kernel: B=8 N=2048 k=20 C=64 101 vs 88 us, C=3 70 vs 52 us; B=4 N=8192 k=40 C=64 567 vs 542 us (eager
+    // timing incl. the squared-norm launch).  The filter works as designed -- 57 survivors per row for a 1536-candidate epoch
+    // (expected 60), 3.7 % of the workgroups redo an epoch -- but a streamed epoch costs as much as the distance block + full
+    // selection it replaces: with 2-6 tiles per wave and epoch the operand-load latency, the two barriers and the
+    // rank-by-counting merge (which dominates the selection either way) are all exposed, and 512-candidate chunks are 14 us
+    // slower than 1024-candidate ones for the same reason.  Two co-resident 8-wave workgroups per CU (256-candidate first
+    // chunk, 50 KB of LDS, 101 VGPRs) change nothing: 101 us.  The streamed instantiations are not built into the library --
+    // the STREAM template paths above are kept as the record of the design (FSG_KNN_RMQS(..., true) would dispatch them).
+    if (c_knn <= 4) FSG_KNN_RM(1, 16, 128, 1024, 64);
+    else if (c_knn <= 16) FSG_KNN_RM(4, 16, 128, 1024, 64);
     else if (c_knn <= 64) {
         if (half) FSG_KNN_RM(16, 8, 64, 512, 32);
-        else if (w8) FSG_KNN_RM(16, 8, 128, 1024, 64);
         else if (small_k) FSG_KNN_RMQ(16, 16, 128, 1024, 32, true);
         else FSG_KNN_RMQ(16, 16, 128, 1024, 64, true);   // 131.6 KB rows + 16 KB best lists + 8 KB query operand
     }
     else {
         if (half) FSG_KNN_RM(32, 8, 64, 512, 32);
-        else if (!w8 && small_k) FSG_KNN_RMQ(32, 16, 128, 1024, 32, true);   // 131.6 KB rows + 8 KB lists + 16 KB query operand
+        else if (small_k) FSG_KNN_RMQ(32, 16, 128, 1024, 32, true);   // 131.6 KB rows + 8 KB lists + 16 KB query operand
         else FSG_KNN_RM(32, 8, 128, 1024, 64);
     }
 #undef FSG_KNN_RM
@@ -809,7 +788,7 @@ int fsg_knn_rows_mfma_launch(const float *x, int B, int N, int64_t stride_b, int
     return FSG_OK;
 }
 
-// packed-segment query on the same selection machinery; FSG_ERR_UNSUPPORTED -> caller keeps its scalar kernel
+// packed-segment query on the same selection machinery (FSG_ERR_UNSUPPORTED: the caller keeps its scalar kernel)
 int fsg_knn_segment_rows_launch(const float *xyz, const float *new_xyz, const int32_t *offset, const int32_t *new_offset,
                                 int b, int n, int m, int nsample, int32_t *idx, float *dist2, hipStream_t st) {
     if (nsample > 32 || b > 4096) return FSG_ERR_UNSUPPORTED;

@@ -6,7 +6,7 @@
 //
 // Since round 4 the build is TWO launches (knn_nominate_kernel + knn_refine_kernel, second half of this file: read its header
 // first); the one-launch kernel of rounds 2-3 (knn_split_kernel, first half) is kept for the one shape class where it is still
-// ahead (k + drop > 32 at N > 4096 on 64+ channels: BASELINE config 4) and as an independent cross-check (flag 536870912).
+// ahead (k + drop > 32 at N > 4096 on 64+ channels: BASELINE config 4) and as an independent cross-check (KNN_DBG_ONE_LAUNCH).
 // The algorithm, common to both:
 //
 //   prep    one pass over the cloud: squared norms (the oracle's chain), a point-major fp32 copy (rows for the refine) and
@@ -15,7 +15,7 @@
 //           * above 4 channels: ONE fp16 image of the points centred on a sampled mean and scaled by a power of two (both the
 //             same for every workgroup of a cloud); points outside the fp16 range are marked and send their cloud down the
 //             exact slow path;
-//           * up to 4 channels (and flag 1073741824): two bf16 pieces x = hi + lo + r, |r| <= 2^-16 |x| (round-to-nearest-
+//           * up to 4 channels (and KNN_DBG_BF16): two bf16 pieces x = hi + lo + r, |r| <= 2^-16 |x| (round-to-nearest-
 //             even in integer arithmetic) of the points as they are, three products -- which share ONE k-step at <= 4 channels.
 //           A query operand is the same image times -2 (one exponent step, done in the main kernel).
 //           (Feature-space builds of DGCNN-seg: emitted by the EdgeConv pass that produces the points, edgeconv.hip; the
@@ -42,17 +42,13 @@
 //   fp32 accumulation of 193 terms in the matrix core, any order, truncation allowed          -> 2.6e-5 (R^2 + 2.1 n_i R)
 //   the oracle's own fp32 chains against real arithmetic (dot, both norms, two roundings)     -> 9.2e-6 (n_i + R)^2
 //
-// Debug / measurement flags (bits of `flags`; tools/knn_split_check.py, tools/knn_nominate_stamps.py, tools/knn_split_stamps.py):
-// 65536 plain workgroup placement; 4194304 every query through the slow path; 1073741824 the bf16 form above 4 channels;
-// 33554432 statistics (fsg_debug_knn_split_stats); 268435456 cycle stamps (fsg_debug_knn_split_stamps / _refine_stamps; forces
-// the two-launch form unless 536870912 is set too); 536870912 the one-launch kernel; 134217728 two-launch form without resident
-// operand tiles; 67108864 two-launch form with the prep launch where the no-prep path would run (A/B) -- and, one-launch kernel
-// only: 67108864 / 8388608 / 16777216 return after the setup / sweep 1 / sweep 2 (timing ablations: the outputs are NOT written).
+// Debug / cross-check bits of `flags`: the KNN_DBG_* list of knn_internal.h (tools/knn_split_check.py,
+// tools/knn_nominate_stamps.py, tools/knn_split_stamps.py).
 #include <type_traits>
 
-#include "fsg_common.h"
+#include "knn_internal.h"
 
-// debug statistics (flag 33554432): [0] queries refined, [1] their listed candidates, [2] queries on the slow path,
+// debug statistics (KNN_DBG_STATS): [0] queries refined, [1] their listed candidates, [2] queries on the slow path,
 // [3] largest list total
 __device__ unsigned long long fsg_knn_split_stats[4];
 extern "C" int fsg_debug_knn_split_stats(unsigned long long *out, int reset) {
@@ -64,7 +60,7 @@ extern "C" int fsg_debug_knn_split_stats(unsigned long long *out, int reset) {
     return 0;
 }
 
-// cycle stamps (flag 268435456): [workgroup (first 256)][wave][16] shader-clock ticks at the phase boundaries
+// cycle stamps (KNN_DBG_STAMPS): [workgroup (first 256)][wave][16] shader-clock ticks at the phase boundaries
 __device__ unsigned long long fsg_knn_split_stamps[256 * 8 * 16];
 extern "C" int fsg_debug_knn_split_stamps(unsigned long long *out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(fsg_knn_split_stamps), sizeof(fsg_knn_split_stamps)) != hipSuccess;
@@ -343,19 +339,13 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31, h = lane >> 5;
-    const bool stamps = (flags & 268435456) != 0;
-    auto stamp = [&](int i) {
-        if (stamps) {
-            const unsigned wg = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (wg < 256 && lane == 0) fsg_knn_split_stamps[(wg * 8 + wave) * 16 + i] = t;
-        }
-    };
+    const bool stamps = (flags & KNN_DBG_STAMPS) != 0;
+    auto stamp = [&](int i) { knn_stamp<256, WAVES, 16>(fsg_knn_split_stamps, stamps, wave, lane, i); };
     stamp(0);
     int b = blockIdx.y, q0 = blockIdx.x * QB;
     {   // XCD-aware placement (as knn_rows_mfma.hip): XCD x owns a contiguous eighth of the (cloud, tile) space
         const unsigned L = blockIdx.x + gridDim.x * blockIdx.y, total = gridDim.x * gridDim.y;
-        if ((total & 7u) == 0 && !(flags & 65536)) {
+        if ((total & 7u) == 0) {
             const unsigned V = (L & 7u) * (total >> 3) + (L >> 3);
             b = (int)(V / gridDim.x);
             q0 = (int)(V % gridDim.x) * QB;
@@ -538,7 +528,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
     stamp(1);
     __syncthreads();   // xs, red, qrow
     stamp(2);
-    if (flags & 67108864) return;   // timing ablation: setup only
 
     // ---------------------------------------------------------------- sweep 1: group minima
     {
@@ -559,7 +548,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
     stamp(3);
     __syncthreads();
     stamp(4);
-    if (flags & 8388608) return;    // timing ablation: setup + sweep 1
 
     // ---------------------------------------------------------------- tau and the acceptance bound per query
     {
@@ -610,7 +598,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
         float thr;
         if (q0 + q >= N) {
             thr = -INFINITY;                                   // no such query
-        } else if ((flags & 4194304) || any_outlier) {   // flag / a marked outlier in the cloud: straight to the slow path
+        } else if ((flags & KNN_DBG_ALL_SLOW) || any_outlier) {   // flag / a marked outlier in the cloud: straight to the slow path
             thr = -INFINITY;
             if ((lane & 7) == 0) slowq[q] = 1;
         } else if (tau >= 0xFF800000u) {                 // fewer than K finite minima: every finite candidate is a nominee
@@ -667,7 +655,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
     stamp(7);
     __syncthreads();
     stamp(8);
-    if (flags & 16777216) return;   // timing ablation: ... + tau + sweep 2
 
     // ---------------------------------------------------------------- refine: the oracle's distances, ranked by counting
     // lane-per-candidate form (slow path): rows straight from the point-major copy
@@ -721,7 +708,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
             tot[u] = __builtin_amdgcn_readlane(incl[u], 63);
             const bool exists = q0 + qbase + u < N;
             const bool bad = exists && (tot[u] > PC || tot[u] < KK);   // too many (ties) / too few (cannot happen): slow path
-            if ((flags & 33554432) && lane == 0 && exists) {
+            if ((flags & KNN_DBG_STATS) && lane == 0 && exists) {
                 atomicAdd(&fsg_knn_split_stats[0], 1ull);
                 atomicAdd(&fsg_knn_split_stats[1], (unsigned long long)tot[u]);
                 atomicMax(&fsg_knn_split_stats[3], (unsigned long long)tot[u]);
@@ -924,7 +911,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
 //   knn_nominate_kernel   setup, sweep 1, tau, sweep 2 (the scores, the acceptance rule and its error bound are the ones above),
 //                         then every wave counts the survivors of its eight queries and copies their bitmap rows to the
 //                         workspace ((B, Np, Np / 32) words).  A query outside the refine kernel's envelope (more than PCAP
-//                         survivors: massive ties; a marked outlier in the cloud; flag 4194304) is served HERE by the exact slow
+//                         survivors: massive ties; a marked outlier in the cloud; KNN_DBG_ALL_SLOW) is served HERE by the exact slow
 //                         path and its row is zeroed.  LDS: norms + bitmaps only (25 KB at N = 2048).  Differences to the
 //                         monolithic kernel: (1) RES -- up to 64 candidate tiles: a wave's eight operand tiles are loaded ONCE
 //                         and stay in registers for both sweeps (no loads, no waits inside the sweeps); (2) tau is the EXACT
@@ -1018,19 +1005,13 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_nominate_kernel(const float
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31, h = lane >> 5;
-    const bool stamps = (flags & 268435456) != 0;
-    auto stamp = [&](int i) {
-        if (stamps) {
-            const unsigned wg = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (wg < 256 && lane == 0) fsg_knn_split_stamps[(wg * 8 + wave) * 16 + i] = t;
-        }
-    };
+    const bool stamps = (flags & KNN_DBG_STAMPS) != 0;
+    auto stamp = [&](int i) { knn_stamp<256, WAVES, 16>(fsg_knn_split_stamps, stamps, wave, lane, i); };
     stamp(0);
     int b = blockIdx.y, q0 = blockIdx.x * QB;
     {
         const unsigned L = blockIdx.x + gridDim.x * blockIdx.y, total = gridDim.x * gridDim.y;
-        if ((total & 7u) == 0 && !(flags & 65536)) {
+        if ((total & 7u) == 0) {
             const unsigned V = (L & 7u) * (total >> 3) + (L >> 3);
             b = (int)(V / gridDim.x);
             q0 = (int)(V % gridDim.x) * QB;
@@ -1390,7 +1371,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_nominate_kernel(const float
         float thr;
         if (q0 + q >= N) {
             thr = -INFINITY;
-        } else if ((flags & 4194304) || any_outlier) {
+        } else if ((flags & KNN_DBG_ALL_SLOW) || any_outlier) {
             thr = -INFINITY;
             if (l8 == 0) atomicOr(&slowm[q >> 5], 1u << (q & 31));
         } else if (!(td < INFINITY)) {     // fewer than K finite minima: every finite candidate is a nominee
@@ -1463,7 +1444,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_nominate_kernel(const float
             const int tot = __builtin_amdgcn_readlane(c[u], 63);
             const bool exists = q0 + qbase + u < N;
             const bool bad = exists && (tot > PCAP || tot < KK);
-            if ((flags & 33554432) && lane == 0 && exists) {
+            if ((flags & KNN_DBG_STATS) && lane == 0 && exists) {
                 atomicAdd(&fsg_knn_split_stats[0], 1ull);
                 atomicAdd(&fsg_knn_split_stats[1], (unsigned long long)tot);
                 atomicMax(&fsg_knn_split_stats[3], (unsigned long long)tot);
@@ -1592,19 +1573,13 @@ __global__ __launch_bounds__(128) void knn_refine_kernel(const float *__restrict
     float *qrows = stg + (STAGE ? 64 * CSQ : 0);                                 // [QW][CPQ]: query row, then its squared norm
     int *seg = reinterpret_cast<int *>(qrows + QW * CPQ);                        // [QW][2] segment bounds, then a dump slot
     unsigned *dump = reinterpret_cast<unsigned *>(seg + 2 * QW);                 // where the decode's predicated-off stores go
-    const bool stamps = (flags & 268435456) != 0;
-    auto stamp = [&](int i) {
-        if (stamps) {
-            const unsigned wg = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (wg < 512 && lane == 0) fsg_knn_refine_stamps[(wg * 2 + wave) * 8 + i] = t;
-        }
-    };
+    const bool stamps = (flags & KNN_DBG_STAMPS) != 0;
+    auto stamp = [&](int i) { knn_stamp<512, RW, 8>(fsg_knn_refine_stamps, stamps, wave, lane, i); };
     stamp(0);
     int b = blockIdx.y, qw0 = blockIdx.x * RW * QW;
     {
         const unsigned L = blockIdx.x + gridDim.x * blockIdx.y, total = gridDim.x * gridDim.y;
-        if ((total & 7u) == 0 && !(flags & 65536)) {
+        if ((total & 7u) == 0) {
             const unsigned V = (L & 7u) * (total >> 3) + (L >> 3);
             b = (int)(V / gridDim.x);
             qw0 = (int)(V % gridDim.x) * RW * QW;
@@ -1922,11 +1897,37 @@ int fsg_knn_split_ws_pointers(void *ws, size_t ws_bytes, int B, int N, int c_knn
 }
 
 
-// the round-2/3 monolithic kernel (flag 536870912): A/B timing and an independent cross-check of the two-launch form
-static int launch_monolithic(const SplitPlan &p, const float *x, const float *prepared_xt, int B, int N, int64_t stride_b,
-                             int64_t stride_c, int c_knn, int k, int flags, int32_t *idx_out, float *dist_out, float *xx,
-                             float *xt, u32x4 *cand, float *xs, float *cscale, hipStream_t st) {
-    const dim3 pgrid(p.Np / 32, B), grid(p.Np / 64, B);
+namespace {
+
+// what every launch of one build passes on
+struct SplitArgs {
+    SplitPlan p;
+    const float *x;          // (B, C, N) points; not read when `prepared`
+    bool prepared;           // the producer of the points has written the prep products: no prep launch
+    int B, N;
+    long sb, sc;
+    int c_knn, k, flags;
+    int32_t *idx_out;
+    float *dist_out;
+    float *xx, *xt;          // workspace: squared norms, point-major rows (or the producer's copy)
+    u32x4 *cand;             //            operand image
+    float *xs, *cscale;      //            centred norms and scale (fp16 form)
+    unsigned *bmg;           //            survivor bitmaps (two-launch form)
+    hipStream_t st;
+};
+
+template <int KS, bool PK, bool HF>
+void launch_prep(const SplitArgs &a) {
+    if (a.prepared) return;
+    hipLaunchKernelGGL((knn_split_prep_kernel<KS, PK, HF>), dim3(a.p.Np / 32, a.B), dim3(256), 0, a.st, a.x, a.N, a.p.Np, a.sb, a.sc,
+                       a.c_knn, a.xx, a.xt, a.cand, a.xs, a.cscale);
+}
+
+// the round-2/3 one-launch kernel: k + drop > 32 at N > 4096 on 64+ channels, and KNN_DBG_ONE_LAUNCH (an independent cross-check
+// of the two-launch form)
+template <int KS, bool PK, bool HF>
+int launch_monolithic(const SplitArgs &a) {
+    const SplitPlan &p = a.p;
     const size_t T = p.Np / 32, CPQ = p.CP + 4, PR = p.CP > 64 ? 16 : 48;
     size_t bmb = 4 * ((QB * (T + 1) + 1) & ~(size_t)1);
     if (bmb < (size_t)4 * QB * NMIN) bmb = (size_t)4 * QB * NMIN;
@@ -1939,70 +1940,71 @@ static int launch_monolithic(const SplitPlan &p, const float *x, const float *pr
     while (PC >= 256 && fixed + 8 * (size_t)WAVES * PC > 160 * 1024) PC /= 2;
     if (PC < 256) return FSG_ERR_UNSUPPORTED;
     const size_t lds = fixed + 8 * (size_t)WAVES * PC;
-    if (p.KS == 8 && (flags & 1073741824)) return FSG_ERR_UNSUPPORTED;   // 128 channels: fp16 image only
-#define FSG_KNN_MONO(KSV, PK, HF)                                                                                      \
-    do {                                                                                                               \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)knn_split_kernel<KSV, PK, HF>, 160 * 1024)) {                                  \
-            fsg_set_error("fsg_knn_dense_ws_f32: cannot raise dynamic LDS");                                          \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
-        if (!prepared_xt)                                                                                              \
-            hipLaunchKernelGGL((knn_split_prep_kernel<KSV, PK, HF>), pgrid, dim3(256), 0, st, x, N, p.Np,              \
-                               (long)stride_b, (long)stride_c, c_knn, xx, xt, cand, xs, cscale);                       \
-        hipLaunchKernelGGL((knn_split_kernel<KSV, PK, HF>), grid, dim3(WAVES * 64), lds, st, xx, xt, cand, xs, cscale,  \
-                           N, p.Np, k, flags, PC, idx_out, dist_out);                                                  \
-    } while (0)
-    if (lds > 160 * 1024) return FSG_ERR_UNSUPPORTED;
-    // default above 4 channels: ONE fp16 product on the centred, scaled points; flag 1073741824: three bf16 products on the
-    // points as they are
-    // (the first form of this kernel: A/B timing, cross-check of the centred path)
-    if ((flags & 1073741824) || p.pack) {   // up to 4 channels the three bf16 products share ONE k-step: nothing to gain
-        if (p.pack) FSG_KNN_MONO(1, true, false);
-        else if (p.KS == 1) FSG_KNN_MONO(1, false, false);
-        else if (p.KS == 2) FSG_KNN_MONO(2, false, false);
-        else FSG_KNN_MONO(4, false, false);
-    } else {
-        if (p.KS == 1) FSG_KNN_MONO(1, false, true);
-        else if (p.KS == 2) FSG_KNN_MONO(2, false, true);
-        else if (p.KS == 4) FSG_KNN_MONO(4, false, true);
-        else FSG_KNN_MONO(8, false, true);
+    static FsgLdsGrant grant;   // per instantiation
+    if (!grant.raise((const void *)knn_split_kernel<KS, PK, HF>, 160 * 1024)) {
+        fsg_set_error("fsg_knn_dense_ws_f32: cannot raise dynamic LDS");
+        return FSG_ERR_HIP;
     }
-#undef FSG_KNN_MONO
+    launch_prep<KS, PK, HF>(a);
+    hipLaunchKernelGGL((knn_split_kernel<KS, PK, HF>), dim3(p.Np / 64, a.B), dim3(WAVES * 64), lds, a.st, a.xx, a.xt, a.cand, a.xs,
+                       a.cscale, a.N, p.Np, a.k, a.flags, PC, a.idx_out, a.dist_out);
+    FSG_CHECK_LAUNCH("fsg_knn_dense_ws_f32/split-monolithic");
     return FSG_OK;
 }
 
-// returns FSG_ERR_UNSUPPORTED when the shape is outside this kernel's envelope (caller falls back)
-int fsg_knn_split_launch_ex(const float *x, const float *prepared_xt, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn,
-                            int k, int flags, int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st);
-
-int fsg_knn_split_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
-                         int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st) {
-    return fsg_knn_split_launch_ex(x, nullptr, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, ws, ws_bytes, st);
+template <int KS, bool PK, bool HF, bool RES, bool RAW>
+int launch_nominate(const SplitArgs &a, size_t lds, int PCAP, int TS, const RawPoints &raw) {
+    static FsgLdsGrant grant;   // per instantiation: the one that is launched
+    if (!grant.raise((const void *)knn_nominate_kernel<KS, PK, HF, RES, RAW>, lds)) {
+        fsg_set_error("fsg_knn_dense_ws_f32: cannot raise dynamic LDS to %zu", lds);
+        return FSG_ERR_HIP;
+    }
+    hipLaunchKernelGGL((knn_nominate_kernel<KS, PK, HF, RES, RAW>), dim3(a.p.Np / 64, a.B), dim3(WAVES * 64), lds, a.st, a.xx, a.xt,
+                       a.cand, a.xs, a.cscale, a.N, a.p.Np, a.k, a.flags, PCAP, a.bmg, TS, a.idx_out, a.dist_out, raw);
+    return FSG_OK;
 }
 
-// prepared_xt != NULL: the workspace already holds the prep products (squared norms, centred norms, fp16 image, scale: written
-// by the producer of the points, ec1_apply_prep_kernel) and prepared_xt is the point-major (B, N, c_knn) copy of the points
-// (c_knn == 16 KS, N % 64 == 0): the prep kernel is skipped
-static int knn_split_launch_impl(const float *x, const float *prepared_xt, int B, int N, int64_t stride_b, int64_t stride_c,
-                                 int c_knn, int k, int flags, int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes,
-                                 hipStream_t st, const float *pq_w, int pq_rows, float *pq_out, bool *pq_fused);
-
-int fsg_knn_split_launch_ex(const float *x, const float *prepared_xt, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn,
-                            int k, int flags, int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st) {
-    return knn_split_launch_impl(x, prepared_xt, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, ws, ws_bytes, st, nullptr,
-                                 0, nullptr, nullptr);
+// the two-launch form: [prep,] nominate, refine
+template <int KS, bool PK, bool HF>
+int launch_pair(const SplitArgs &a, const KnnSplitOpts &o) {
+    const SplitPlan &p = a.p;
+    const size_t T = p.Np / 32, CPQ = p.CP + 4;
+    // ---- nominate: norms + bitmaps (or group minima) + per-query scalars
+    size_t bmw = (QB * (T + 1) + 3) & ~(size_t)3;
+    if (bmw < (size_t)QB * NMIN) bmw = (size_t)QB * NMIN;
+    const size_t lds1 = sizeof(float) * 32 * WAVES * ((T + WAVES - 1) / WAVES) + 4 * bmw + sizeof(float) * QB + sizeof(unsigned) * 4 + sizeof(float) * 24;
+    // ---- refine: two waves, each with its candidate / key list and its row stage
+    const int PCAP = 256, TS = (int)((T + 7) & ~(size_t)7);
+    const size_t CS = p.CP > 32 ? 32 : p.CP;
+    const size_t lds2 = 2 * ((size_t)8 * RECAP + (p.CP > 4 ? 4 * 64 * (CS + 4) : 0) + 4 * (size_t)RQW * CPQ + 128);
+    if (lds1 > 160 * 1024 || lds2 > 64 * 1024) return FSG_ERR_UNSUPPORTED;
+    const bool res = T == 64;                        // a wave's 8 operand tiles stay in registers
+    constexpr bool RES_OK = (HF && KS <= 4) || PK;   // ... where the register budget has room for them
+    // <= 4 channels at 64 tiles, points directly addressable in 16-byte pieces: no prep launch (RAW, see the kernel)
+    const bool raw_ok = PK && res && !a.prepared && p.Np == a.N && a.sb % 4 == 0 && a.sc % 4 == 0 &&
+                        (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
+    int rc;
+    if constexpr (PK) {
+        if (raw_ok) {
+            if (o.pq_out && (WAVES * 64) % o.pq_rows != 0) return FSG_ERR_UNSUPPORTED;
+            if (o.pq_fused) *o.pq_fused = o.pq_out != nullptr;
+            const RawPoints raw{a.x, a.sb, a.sc, a.c_knn, a.xx, a.xt, o.pq_w, o.pq_rows, o.pq_out};
+            rc = launch_nominate<1, true, false, true, true>(a, lds1, PCAP, TS, raw);
+        }
+    }
+    if (!raw_ok) {
+        launch_prep<KS, PK, HF>(a);
+        rc = res && RES_OK ? launch_nominate<KS, PK, HF, RES_OK, false>(a, lds1, PCAP, TS, RawPoints{})
+                           : launch_nominate<KS, PK, HF, false, false>(a, lds1, PCAP, TS, RawPoints{});
+    }
+    if (rc != FSG_OK) return rc;
+    hipLaunchKernelGGL((knn_refine_kernel<(PK ? 4 : 16 * KS)>), dim3(p.Np / (2 * RQW), a.B), dim3(128), lds2, a.st, a.xx, a.xt, a.bmg,
+                       a.N, p.Np, TS, a.k, a.flags, PCAP, a.idx_out, a.dist_out);
+    FSG_CHECK_LAUNCH("fsg_knn_dense_ws_f32/split");
+    return FSG_OK;
 }
 
-// graph build + the per-point product pq_out (B, N, pq_rows) = x^T pq_w^T (c_knn <= 4 channels): fused into the nominate launch
-// where the RAW path runs (*fused = true), otherwise the caller launches fsg_knn_pq_rows_launch itself
-int fsg_knn_split_launch_pq(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
-                            int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st, const float *pq_w,
-                            int pq_rows, float *pq_out, bool *fused) {
-    *fused = false;
-    return knn_split_launch_impl(x, nullptr, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, ws, ws_bytes, st, pq_w,
-                                 pq_rows, pq_out, fused);
-}
+}  // namespace
 
 int fsg_knn_pq_rows_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, const float *pq_w,
                            int pq_rows, float *pq_out, hipStream_t st) {
@@ -2013,91 +2015,46 @@ int fsg_knn_pq_rows_launch(const float *x, int B, int N, int64_t stride_b, int64
     return FSG_OK;
 }
 
-static int knn_split_launch_impl(const float *x, const float *prepared_xt, int B, int N, int64_t stride_b, int64_t stride_c,
-                                 int c_knn, int k, int flags, int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes,
-                                 hipStream_t st, const float *pq_w, int pq_rows, float *pq_out, bool *pq_fused) {
+int fsg_knn_split_launch(const float *x, int B, int N, int64_t stride_b, int64_t stride_c, int c_knn, int k, int flags,
+                         int32_t *idx_out, float *dist_out, void *ws, size_t ws_bytes, hipStream_t st, const KnnSplitOpts &o) {
+    if (o.pq_fused) *o.pq_fused = false;
     const int drop = (flags & FSG_KNN_DROP_FIRST) ? 1 : 0;
+    const bool bf16 = (flags & KNN_DBG_BF16) != 0;
     const SplitPlan p = plan(B, N, c_knn);
     if (!p.ok || k + drop > 64 || ws == nullptr || ws_bytes < p.total) return FSG_ERR_UNSUPPORTED;
-    if (prepared_xt && (p.pack || p.CP != c_knn || p.Np != N || (flags & 1073741824))) return FSG_ERR_UNSUPPORTED;
+    if (o.prepared_xt && (p.pack || p.CP != c_knn || p.Np != N || bf16)) return FSG_ERR_UNSUPPORTED;
+    if (p.KS == 8 && bf16) return FSG_ERR_UNSUPPORTED;   // 128 channels: fp16 image only
     unsigned char *w = static_cast<unsigned char *>(ws);
-    float *xx = reinterpret_cast<float *>(w + p.off_xx);
-    float *xt = prepared_xt ? const_cast<float *>(prepared_xt) : reinterpret_cast<float *>(w + p.off_xt);
-    u32x4 *cand = reinterpret_cast<u32x4 *>(w + p.off_cand);
-    float *xs = reinterpret_cast<float *>(w + p.off_xs);
-    float *cscale = reinterpret_cast<float *>(w + p.off_scale);
+    const SplitArgs a{p, x, o.prepared_xt != nullptr, B, N, (long)stride_b, (long)stride_c, c_knn, k, flags, idx_out, dist_out,
+                      reinterpret_cast<float *>(w + p.off_xx),
+                      o.prepared_xt ? const_cast<float *>(o.prepared_xt) : reinterpret_cast<float *>(w + p.off_xt),
+                      reinterpret_cast<u32x4 *>(w + p.off_cand), reinterpret_cast<float *>(w + p.off_xs),
+                      reinterpret_cast<float *>(w + p.off_scale), reinterpret_cast<unsigned *>(w + p.off_bm), st};
     // One launch or two.  The two-launch form wins wherever the refine's batches of eight queries fit one sub-batch of 256
     // entries; at k + drop > 32 on 64 and more channels with N > 4096 (BASELINE config 4: ~77 nominees per query, three
     // sub-batches per wave, 2 x 32 KB of bitmaps per wave and sweep) the monolithic kernel is still ahead (4 x 8192, k = 40,
-    // 64 channels: 209 vs 241 us; every other measured shape: 0 - 35 % in favour of two launches).  Flag 536870912 forces the
-    // monolithic kernel, flag 268435456 (cycle stamps of the two-launch form) the two-launch form.
-    const bool big_k = k + drop > 32 && p.CP >= 64 && N > 4096 && !(flags & 268435456);
-    if ((flags & 536870912) || big_k) {
-        const int rc = launch_monolithic(p, x, prepared_xt, B, N, stride_b, stride_c, c_knn, k, flags, idx_out, dist_out, xx, xt, cand, xs, cscale, st);
-        if (rc != FSG_OK) return rc;
-        FSG_CHECK_LAUNCH("fsg_knn_dense_ws_f32/split-monolithic");
-        return FSG_OK;
+    // 64 channels: 209 vs 241 us; every other measured shape: 0 - 35 % in favour of two launches).  KNN_DBG_ONE_LAUNCH forces
+    // the monolithic kernel, KNN_DBG_STAMPS alone (cycle stamps of the two-launch form) the two-launch form.
+    const bool mono = (flags & KNN_DBG_ONE_LAUNCH) || (k + drop > 32 && p.CP >= 64 && N > 4096 && !(flags & KNN_DBG_STAMPS));
+    auto form = [&](auto ks, auto pk, auto hf) {
+        constexpr int KS = decltype(ks)::value;
+        constexpr bool PK = decltype(pk)::value, HF = decltype(hf)::value;
+        return mono ? launch_monolithic<KS, PK, HF>(a) : launch_pair<KS, PK, HF>(a, o);
+    };
+    using std::integral_constant;
+    const std::true_type yes;
+    const std::false_type no;
+    // up to 4 channels: two bf16 pieces whose three products share ONE k-step.  Above: ONE fp16 product on the centred, scaled
+    // points; KNN_DBG_BF16: three bf16 products on the points as they are (the first form of this kernel: a cross-check of
+    // the centred path)
+    if (p.pack) return form(integral_constant<int, 1>{}, yes, no);
+    if (bf16) {
+        if (p.KS == 1) return form(integral_constant<int, 1>{}, no, no);
+        if (p.KS == 2) return form(integral_constant<int, 2>{}, no, no);
+        return form(integral_constant<int, 4>{}, no, no);
     }
-    const dim3 pgrid(p.Np / 32, B), grid(p.Np / 64, B);
-    const size_t T = p.Np / 32, CPQ = p.CP + 4;
-    if (p.KS == 8 && (flags & 1073741824)) return FSG_ERR_UNSUPPORTED;   // 128 channels: fp16 image only
-    unsigned *bmg = reinterpret_cast<unsigned *>(w + p.off_bm);
-    // ---- nominate: norms + bitmaps (or group minima) + per-query scalars
-    size_t bmw = (QB * (T + 1) + 3) & ~(size_t)3;
-    if (bmw < (size_t)QB * NMIN) bmw = (size_t)QB * NMIN;
-    const size_t lds1 = sizeof(float) * 32 * WAVES * ((T + WAVES - 1) / WAVES) + 4 * bmw + sizeof(float) * QB + sizeof(unsigned) * 4 + sizeof(float) * 24;
-    // ---- refine: four waves, each with its candidate / key list and its row stage
-    const int PCAP = 256, TS = (int)((T + 7) & ~(size_t)7);
-    const size_t CS = p.CP > 32 ? 32 : p.CP;
-    const size_t lds2 = 2 * ((size_t)8 * RECAP + (p.CP > 4 ? 4 * 64 * (CS + 4) : 0) + 4 * (size_t)RQW * CPQ + 128);
-    const bool res = T == 64 && !(flags & 134217728);   // a wave's <= 8 operand tiles stay in registers (flag: A/B timing)
-    if (lds1 > 160 * 1024 || lds2 > 64 * 1024) return FSG_ERR_UNSUPPORTED;
-    const dim3 rgrid(p.Np / (2 * RQW), B);
-#define FSG_KNN_SPLIT(KSV, PK, HF)                                                                                      \
-    do {                                                                                                               \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)knn_nominate_kernel<KSV, PK, HF, false, false>, 160 * 1024)) {                        \
-            fsg_set_error("fsg_knn_dense_ws_f32: cannot raise dynamic LDS");                                          \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
-        if (!prepared_xt)                                                                                              \
-            hipLaunchKernelGGL((knn_split_prep_kernel<KSV, PK, HF>), pgrid, dim3(256), 0, st, x, N, p.Np,              \
-                               (long)stride_b, (long)stride_c, c_knn, xx, xt, cand, xs, cscale);                       \
-        if (res && ((HF && KSV <= 4) || PK))                                                                           \
-            hipLaunchKernelGGL((knn_nominate_kernel<KSV, PK, HF, ((HF && KSV <= 4) || PK), false>), grid,              \
-                               dim3(WAVES * 64), lds1, st, xx, xt, cand, xs, cscale, N, p.Np, k, flags, PCAP, bmg, TS,  \
-                               idx_out, dist_out, RawPoints{});                                                        \
-        else                                                                                                           \
-            hipLaunchKernelGGL((knn_nominate_kernel<KSV, PK, HF, false, false>), grid, dim3(WAVES * 64), lds1, st, xx, \
-                               xt, cand, xs, cscale, N, p.Np, k, flags, PCAP, bmg, TS, idx_out, dist_out, RawPoints{}); \
-        hipLaunchKernelGGL((knn_refine_kernel<(PK ? 4 : 16 * KSV)>), rgrid, dim3(128), lds2, st, xx, xt, bmg, N, p.Np,  \
-                           TS, k, flags, PCAP, idx_out, dist_out);                                                     \
-    } while (0)
-    // default above 4 channels: ONE fp16 product on the centred, scaled points; flag 1073741824: three bf16 products on the
-    // points as they are (the first form of this kernel: A/B timing, cross-check of the centred path)
-    // <= 4 channels at 64 tiles, points directly addressable in 16-byte pieces: no prep launch (RAW, see the kernel)
-    const bool raw_ok = p.pack && res && !prepared_xt && p.Np == N && !(flags & 67108864) && stride_b % 4 == 0 &&
-                        stride_c % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    if (raw_ok) {
-        const RawPoints raw{x, (long)stride_b, (long)stride_c, c_knn, xx, xt, pq_w, pq_rows, pq_out};
-        if (pq_fused) *pq_fused = pq_out != nullptr && (WAVES * 64) % pq_rows == 0;
-        if (pq_out && (WAVES * 64) % pq_rows != 0) return FSG_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL((knn_nominate_kernel<1, true, false, true, true>), grid, dim3(WAVES * 64), lds1, st, xx, xt, cand, xs,
-                           cscale, N, p.Np, k, flags, PCAP, bmg, TS, idx_out, dist_out, raw);
-        hipLaunchKernelGGL((knn_refine_kernel<4>), rgrid, dim3(128), lds2, st, xx, xt, bmg, N, p.Np, TS, k, flags, PCAP, idx_out,
-                           dist_out);
-    } else if ((flags & 1073741824) || p.pack) {   // up to 4 channels the three bf16 products share ONE k-step: nothing to gain
-        if (p.pack) FSG_KNN_SPLIT(1, true, false);
-        else if (p.KS == 1) FSG_KNN_SPLIT(1, false, false);
-        else if (p.KS == 2) FSG_KNN_SPLIT(2, false, false);
-        else FSG_KNN_SPLIT(4, false, false);
-    } else {
-        if (p.KS == 1) FSG_KNN_SPLIT(1, false, true);
-        else if (p.KS == 2) FSG_KNN_SPLIT(2, false, true);
-        else if (p.KS == 4) FSG_KNN_SPLIT(4, false, true);
-        else FSG_KNN_SPLIT(8, false, true);
-    }
-#undef FSG_KNN_SPLIT
-    FSG_CHECK_LAUNCH("fsg_knn_dense_ws_f32/split");
-    return FSG_OK;
+    if (p.KS == 1) return form(integral_constant<int, 1>{}, no, yes);
+    if (p.KS == 2) return form(integral_constant<int, 2>{}, no, yes);
+    if (p.KS == 4) return form(integral_constant<int, 4>{}, no, yes);
+    return form(integral_constant<int, 8>{}, no, yes);
 }

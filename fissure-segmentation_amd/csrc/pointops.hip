@@ -5,11 +5,8 @@
 //
 // v0: one lane per query (kNN), one workgroup per cloud (FPS), lanes along channels (gather /
 // aggregate).  Distances use the direct form d = fma(dz,dz, fma(dy,dy, dx*dx)) like oracle/fsg_oracle.c.
-#include "fsg_common.h"
+#include "knn_internal.h"
 #include <stdlib.h>
-
-int fsg_knn_segment_rows_launch(const float *xyz, const float *new_xyz, const int32_t *offset, const int32_t *new_offset,
-                                int b, int n, int m, int nsample, int32_t *idx, float *dist2, hipStream_t st);
 
 namespace {
 

@@ -132,9 +132,6 @@ def deterministic():
 
 
 # ------------------------------------------------------------------ dense kNN (utils/general_utils.py:315)
-_KNN_EXPERIMENT_FLAGS = 8   # the first MFMA design (libfsg_hip_experiments.so): independent cross-check for tests / tools
-
-
 def knn_graph(x, k, c_knn=None, fix_diag=True, drop_first=False, return_dist=False, force_rows_kernel=False,
               _debug_flags=0, out=None, prepared=None, pq_weight=None):
     """x: (B,C,N) -> idx (B,N,k) int32 [, dist (B,N,k) fp32].  Channel slices are passed by stride.  `out`: a contiguous
@@ -144,7 +141,9 @@ def knn_graph(x, k, c_knn=None, fix_diag=True, drop_first=False, return_dist=Fal
     copy (B,N,C): the build starts at its main kernel (include/fsg_hip.h: fsg_knn_dense_prepared_f32).
     `pq_weight` (rows, C) with C = c_knn <= 4 (the [W_rel ; W_ctr - W_rel] weight of the FIRST EdgeConv's first conv): the build
     also emits that block's per-point rows pq (B, N, rows) = x^T pq_weight^T (fsg_knn_dense_ws_pq_f32) -> returns (idx, pq); pq is
-    None when the shape does not qualify (then the caller runs the product itself)."""
+    None when the shape does not qualify (then the caller runs the product itself).
+    `_debug_flags`: _lib.KNN_DBG_* bits, and _lib.KNN_FORCE_MFMA for the first MFMA design of libfsg_hip_experiments.so (an
+    independent cross-check for tests / tools)."""
     _need_gpu(x)
     if x.dim() != 3:
         raise ValueError(f"expected (B,C,N), got {tuple(x.shape)}")
@@ -175,24 +174,23 @@ def knn_graph(x, k, c_knn=None, fix_diag=True, drop_first=False, return_dist=Fal
     if pq_weight is not None:
         rows = pq_weight.shape[0]
         if (C == c_knn and c_knn <= 4 and tuple(pq_weight.shape) == (rows, C) and 256 % rows == 0 and not return_dist and
-                not (_debug_flags & _KNN_EXPERIMENT_FLAGS)):
+                not (_debug_flags & _lib.KNN_FORCE_MFMA)):
             pq = torch.empty(B, N, rows, dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
                 _lib.call("fsg_knn_dense_ws_pq_f32", _p(x), B, N, x.stride(0), x.stride(1), c_knn, k, flags, _p(idx), None, _p(xx),
                           ws_bytes, _p(_f32c(pq_weight.detach())), rows, _p(pq), _stream())
             return idx, pq
     with torch.cuda.device(x.device):
-        if _debug_flags & _KNN_EXPERIMENT_FLAGS:   # superseded designs (tests / tools): libfsg_hip_experiments.so
+        rc = 3   # FSG_ERR_UNSUPPORTED (also: a shape outside the experimental kernel's envelope) -> the production kernel
+        if flags & _lib.KNN_FORCE_MFMA:
             xl = _lib.experiments()
             rc = xl.fsg_knn_experiment_f32(_p(x), B, N, x.stride(0), x.stride(1), c_knn, k, flags, _p(idx), _p(dist), _p(xx),
                                            _stream())
-            if rc == 0:
-                return (idx, dist) if return_dist else idx
-            if rc != 3:   # FSG_ERR_UNSUPPORTED: shape outside that kernel's envelope -> the production kernel below
+            if rc not in (0, 3):
                 raise RuntimeError(xl.fsg_last_error().decode())
-            flags &= ~_KNN_EXPERIMENT_FLAGS
-        _lib.call("fsg_knn_dense_ws_f32", _p(x), B, N, x.stride(0), x.stride(1), c_knn, k, flags, _p(idx), _p(dist), _p(xx),
-                  ws_bytes, _stream())
+        if rc == 3:
+            _lib.call("fsg_knn_dense_ws_f32", _p(x), B, N, x.stride(0), x.stride(1), c_knn, k, flags & ~_lib.KNN_FORCE_MFMA, _p(idx),
+                      _p(dist), _p(xx), ws_bytes, _stream())
     if pq_weight is not None:
         return idx, None
     return (idx, dist) if return_dist else idx

@@ -33,6 +33,8 @@ extern "C" {
 #define FSG_KNN_FORCE_ROWS 4 /* use the general "rows in LDS" kernel even where the MFMA kernel applies (tests) */
 
 #define FSG_KNN_FORCE_MFMA 8 /* (experimental kernels: libfsg_hip_experiments.so only; rejected by libfsg_hip.so)     */
+/* Higher bits of `flags` are debug / cross-check selectors for tests and tools (csrc/knn_internal.h lists them, _lib.py mirrors the
+ * names); a bit that list does not know is FSG_ERR_ARG. */
 
 #define FSG_KNN_MAX_K 64
 

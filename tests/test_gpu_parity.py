@@ -244,6 +244,8 @@ def test_knn_dense_errors(fsg, device):
         fsg.functional.knn_graph(x, 16, drop_first=True)
     with pytest.raises(RuntimeError):
         fsg.functional.knn_graph(torch.zeros(1, 3, 16), 4)  # CPU tensor: no fallback
+    with pytest.raises(RuntimeError, match="256"):
+        fsg.functional.knn_graph(x, 4, _debug_flags=256)    # a removed debug bit: rejected, and named in the message
 
 
 KNN_FIXTURES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "knn_s*.npz")))

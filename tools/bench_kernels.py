@@ -26,22 +26,10 @@ if "knn" in which:
     for (B, C, N, k) in [(8, 3, 2048, 20), (8, 64, 2048, 20), (4, 3, 8192, 40), (4, 64, 8192, 40), (8, 128, 2048, 20), (8, 64, 4096, 20),
                          (8, 128, 4096, 20), (8, 3, 4096, 20)]:
         x = torch.from_numpy(cloud(1, B, C, N)).to(dev)
-        for name, rows, dbg in (("rows_mfma(v2)", False, 0), ("rows_mfma 8 waves", False, 8192), ("mfma(v1)", False, 8), ("rows(v0)", True, 0)):
+        for name, rows, dbg in (("split (default)", False, 0), ("two-phase", False, fsg._lib.KNN_DBG_TWO_PHASE),
+                                ("mfma(v1)", False, fsg._lib.KNN_FORCE_MFMA), ("rows(v0)", True, 0)):
             med, mn = timeit(lambda: F.knn_graph(x, k, force_rows_kernel=rows, _debug_flags=dbg))
-            print(f"knn B={B} C={C} N={N} k={k} {name:14s}: median {med:8.1f} us  min {mn:8.1f} us")
-if "knn2ablate" in which:
-    for (B, C, N, k) in [(8, 3, 2048, 20), (8, 64, 2048, 20)]:
-        x = torch.from_numpy(cloud(1, B, C, N)).to(dev)
-        for name, fl in [("full", 0), ("no phase B", 256), ("no phase A", 512), ("neither", 768)]:
-            med, mn = timeit(lambda: F.knn_graph(x, k, _debug_flags=fl))
-            print(f"knn v2 C={C} {name:12s}: median {med:8.1f} us")
-if "knnablate" in which:
-    for (B, C, N, k) in [(8, 3, 2048, 20), (8, 64, 2048, 20)]:
-        x = torch.from_numpy(cloud(1, B, C, N)).to(dev)
-        for name, fl in [("full", 0), ("nosort", 256), ("nomerge", 512), ("nofilter", 1024), ("nosort+nomerge", 768),
-                         ("none", 256 + 512 + 1024)]:
-            med, mn = timeit(lambda: F.knn_graph(x, k, _debug_flags=fl | 8))
-            print(f"knn C={C} {name:16s}: median {med:8.1f} us")
+            print(f"knn B={B} C={C} N={N} k={k} {name:15s}: median {med:8.1f} us  min {mn:8.1f} us")
 if "edgeconv" in which:
     from fissure_segmentation_amd.models.dgcnn import EdgeConv
     for (B, C, N, k, couts) in [(8, 64, 2048, 20, [64]), (8, 3, 2048, 20, [64, 64]), (4, 64, 8192, 40, [64]), (4, 3, 8192, 40, [64, 64])]:

@@ -1,4 +1,4 @@
-"""In-kernel cycle stamps of the two-launch graph build (flag 268435456): knn_nominate_kernel per phase, knn_refine_kernel
+"""In-kernel cycle stamps of the two-launch graph build (KNN_DBG_STAMPS): knn_nominate_kernel per phase, knn_refine_kernel
 prologue / query loop, mean and max over the first 256 workgroups.  python3 tools/knn_nominate_stamps.py B C N k [flags]"""
 import ctypes
 import os
@@ -18,7 +18,7 @@ p = torch.rand(B, 3, N, generator=g)
 w = torch.randn(C, 3, generator=g)
 x = (torch.tanh(torch.einsum("cd,bdn->bcn", w, p)) + 1.0).contiguous().cuda() if C > 3 else (p * 2 - 1).cuda()
 for _ in range(3):
-    F.knn_graph(x, k, _debug_flags=268435456 | extra)
+    F.knn_graph(x, k, _debug_flags=fsg._lib.KNN_DBG_STAMPS | extra)
 torch.cuda.synchronize()
 lib = fsg._lib.lib
 buf = (ctypes.c_ulonglong * (256 * 8 * 16))()

@@ -1,4 +1,4 @@
-"""fsg_knn_dense_ws_f32 (coarse sweep + exact refine, csrc/knn_split.hip) against the two-phase kernel (flag 2097152) and the
+"""fsg_knn_dense_ws_f32 (coarse sweep + exact refine, csrc/knn_split.hip) against the two-phase kernel (KNN_DBG_TWO_PHASE) and the
 C oracle: indices and distance bits, then graph-replayed timings.  python tools/knn_split_check.py [--time-only]"""
 import os
 import sys
@@ -11,8 +11,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fissure_segmentation_amd as fsg  # noqa: E402
 from fissure_segmentation_amd import functional as F  # noqa: E402
 
-OLD = 2097152
-MONO = 536870912   # the monolithic coarse-sweep kernel of rounds 2-3 (one launch)
+OLD = fsg._lib.KNN_DBG_TWO_PHASE
+MONO = fsg._lib.KNN_DBG_ONE_LAUNCH   # the monolithic coarse-sweep kernel of rounds 2-3 (one launch)
+SLOW, BF16 = fsg._lib.KNN_DBG_ALL_SLOW, fsg._lib.KNN_DBG_BF16
 dev = torch.device("cuda:0")
 
 
@@ -102,12 +103,12 @@ if __name__ == "__main__":
         ok &= check(2, 3, 1024, 20, "dups")
         ok &= check(2, 128, 2048, 20, "lowdim", oracle=True)     # 8 k-steps: the PC-AE encoder's last graph
         ok &= check(2, 100, 4096, 33, "biased", drop=True)
-        ok &= check(1, 128, 1024, 20, "uniform", flags=4194304)
+        ok &= check(1, 128, 1024, 20, "uniform", flags=SLOW)
         ok &= check(1, 16, 1024, 8, "const")
-        ok &= check(2, 64, 2048, 20, "uniform", flags=4194304)   # everything through the slow path
+        ok &= check(2, 64, 2048, 20, "uniform", flags=SLOW)      # everything through the slow path
         ok &= check(2, 16, 1024, 20, "outlier", oracle=True)
         ok &= check(2, 16, 1024, 20, "tiny", oracle=True)
-        for fl in (1073741824,):                                 # the three-product bf16 form
+        for fl in (BF16,):                                       # the three-product bf16 form
             ok &= check(2, 64, 2048, 20, "biased", flags=fl)
             ok &= check(2, 3, 2048, 20, "uniform", flags=fl, oracle=True)
             ok &= check(1, 33, 4096, 63, "biased", drop=True, flags=fl)
@@ -122,17 +123,15 @@ if __name__ == "__main__":
                                (4, 8, 1100, 60, "uniform")]:
         x = feats(7, B, C, N, kind).to(dev)
         lib.fsg_debug_knn_split_stats(st, 1)
-        F.knn_graph(x, k, _debug_flags=33554432)
+        F.knn_graph(x, k, _debug_flags=fsg._lib.KNN_DBG_STATS)
         torch.cuda.synchronize()
         lib.fsg_debug_knn_split_stats(st, 0)
         print(f"stats B={B} C={C} N={N} k={k} {kind:8s}: {st[1] / max(st[0], 1):.1f} listed per query, max {st[3]}, slow {st[2]} of {st[0]}", flush=True)
-        for nm, fl in (("setup", 67108864), ("setup+sweep1", 8388608), ("..+tau+sweep2", 16777216)):
-            print(f"   monolithic kernel, {nm}: {timeit(B, C, N, k, kind, fl | MONO):.1f} us", flush=True)
     for (B, C, N, k, kind) in [(8, 64, 2048, 20, "biased"), (8, 64, 2048, 20, "lowdim"), (8, 64, 2048, 20, "uniform"),
                                (8, 3, 2048, 20, "uniform"), (4, 64, 8192, 40, "lowdim"), (4, 3, 8192, 40, "uniform"),
                                (32, 3, 2048, 40, "uniform"), (8, 3, 4096, 20, "uniform"), (8, 64, 4096, 20, "lowdim"),
                                (8, 128, 4096, 20, "lowdim")]:
-        tn, tb, to = timeit(B, C, N, k, kind, 0), timeit(B, C, N, k, kind, 1073741824), timeit(B, C, N, k, kind, OLD)
+        tn, tb, to = timeit(B, C, N, k, kind, 0), timeit(B, C, N, k, kind, BF16), timeit(B, C, N, k, kind, OLD)
         tm = timeit(B, C, N, k, kind, MONO)
         print(f"time B={B} C={C} N={N} k={k} {kind:8s}: nominate + refine {tn:8.1f} us   (3 x bf16 form {tb:8.1f} us)   monolithic {tm:8.1f} us   two-phase {to:8.1f} us", flush=True)
     sys.exit(0 if ok else 1)

@@ -1,4 +1,5 @@
-"""kNN at config-2 shape, 64 channels; FSG_PROF_FLAGS selects the ablation (256: phase A only, 512: phase B only)."""
+"""kNN at config-2 shape, 64 channels; the rocprofv3 target of tools/pmc_knn.sh.  FSG_PROF_FLAGS: _debug_flags of
+knn_graph (e.g. 2097152 = KNN_DBG_TWO_PHASE for the two-phase kernel instead of the split kernel), FSG_PROF_C: channels."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
