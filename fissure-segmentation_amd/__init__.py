@@ -28,7 +28,7 @@ def install_reference_aliases():
         "losses.chamfer_loss": ".losses.chamfer_loss", "losses.nnu_loss": ".losses.nnu_loss",
         "losses.access_losses": ".losses.access_losses", "losses.mesh_loss": ".losses.mesh_loss",
         "losses.dgssm_loss": ".losses.dgssm_loss", "models.dg_ssm": ".models.dg_ssm",
-        "shape_model": ".shape_model", "shape_model.ssm": ".shape_model.ssm",
+        "shape_model": ".shape_model", "shape_model.ssm": ".shape_model.ssm", "metrics": ".metrics",
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)

@@ -1814,6 +1814,74 @@ def chamfer_nn(x, y):
     return _ChamferNN.apply(x, y)
 
 
+# ------------------------------------------------------------------ point-to-mesh distance (metrics.py:11-25)
+_faces_checked = {}   # (storage, data_ptr, version, shape, strides, dtype) -> (weak storage reference, lowest, highest index)
+
+
+def _faces_range(faces):
+    """(lowest, highest) index of a faces tensor: one reduction and one synchronisation per tensor, remembered by storage,
+    address and version counter (an in-place write bumps the version, so a modified list is looked at again).  The entry
+    holds a weak reference to the storage: an address alone says nothing once the tensor is gone and the allocator has handed
+    its memory to another one."""
+    from torch.multiprocessing.reductions import StorageWeakRef
+    storage = faces.untyped_storage()
+    key = (storage._cdata, faces.data_ptr(), faces._version, tuple(faces.shape), faces.stride(), faces.dtype)
+    got = _faces_checked.get(key)
+    if got is None or got[0].expired():
+        for k in [k for k, v in _faces_checked.items() if v[0].expired()]:
+            del _faces_checked[k]
+        if len(_faces_checked) >= 64:
+            _faces_checked.clear()
+        lo, hi = torch.aminmax(faces)
+        got = _faces_checked[key] = (StorageWeakRef(storage), int(lo), int(hi))
+    return got[1], got[2]
+
+
+def point_mesh_distance(points, verts, faces, return_face=False, return_closest=False, validate=True):
+    """Unsigned Euclidean distance from every point to a triangle mesh (fsg_point_mesh_dist_f32; the square root is torch's).
+
+    points (B,P,3), verts (B,V,3), faces (F,3) shared by all meshes or (B,F,3) -> dist (B,P) fp32
+    [, face (B,P) int32: a face that attains it, the lowest index on ties][, closest (B,P,3): the closest point on it].
+    Faces without area are legal (distance to their longest edge, or to the point).  `validate` checks the face indices
+    against V once per faces tensor; the kernel itself does not.  P == 0 gives empty results, F == 0 (or V == 0) NaN
+    distances, face -1 and NaN closest points; no kernel is launched then.
+
+    An evaluation primitive, NOT differentiable: it runs under torch.no_grad and its outputs never require grad.  A
+    point-to-surface loss (the gradient with respect to points and vertices) is not part of this package yet."""
+    _need_gpu(points, verts, faces)
+    if (points.dim() != 3 or verts.dim() != 3 or points.shape[2] != 3 or verts.shape[2] != 3 or points.shape[0] != verts.shape[0]
+            or faces.dim() not in (2, 3) or faces.shape[-1] != 3 or (faces.dim() == 3 and faces.shape[0] != verts.shape[0])):
+        raise ValueError(f"expected points (B,P,3), verts (B,V,3) and faces (F,3) or (B,F,3), got {tuple(points.shape)}, "
+                         f"{tuple(verts.shape)} and {tuple(faces.shape)}")
+    if faces.is_floating_point() or faces.dtype == torch.bool:
+        raise ValueError(f"faces must hold integer vertex indices, got {faces.dtype}")
+    with torch.no_grad():
+        pc, vc = _f32c(points), _f32c(verts)
+        B, P, _ = pc.shape
+        V, F = vc.shape[1], faces.shape[-2]
+        dev = pc.device
+        if P == 0 or F == 0 or V == 0 or B == 0:
+            out = [torch.full((B, P), float("nan"), dtype=torch.float32, device=dev)]
+            if return_face:
+                out.append(torch.full((B, P), -1, dtype=torch.int32, device=dev))
+            if return_closest:
+                out.append(torch.full((B, P, 3), float("nan"), dtype=torch.float32, device=dev))
+            return out[0] if len(out) == 1 else tuple(out)
+        if validate:
+            lo, hi = _faces_range(faces)
+            if lo < 0 or hi >= V:
+                raise ValueError(f"face indices span [{lo}, {hi}] but the mesh has {V} vertices")
+        fc = faces.detach().to(torch.int32).contiguous()
+        d2 = torch.empty(B, P, dtype=torch.float32, device=dev)
+        face = torch.empty(B, P, dtype=torch.int32, device=dev) if return_face else None
+        closest = torch.empty(B, P, 3, dtype=torch.float32, device=dev) if return_closest else None
+        with torch.cuda.device(dev):
+            _lib.call("fsg_point_mesh_dist_f32", _p(pc), _p(vc), _p(fc), B, P, V, F, B if fc.dim() == 3 else 1, _p(d2), _p(face),
+                      _p(closest), _stream())
+        out = [d2.sqrt_()] + [t for t in (face, closest) if t is not None]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 # ------------------------------------------------------------------ DG-SSM: shape-model decode + similarity transform
 SSM_MAX_MODES = 64
 

@@ -319,6 +319,20 @@ int fsg_chamfer_nn_bwd_f32(const float *x, const float *y, const int32_t *arg, c
                            fsg_stream_t stream);
 
 /*
+ * Unsigned point-to-triangle-mesh distance: replaces the open3d RaycastingScene.compute_distance call of metrics.py:20-24
+ * (under assd / batch_assd / pseudo_symmetric_point_to_mesh_distance).  Brute force over all faces, exact in the
+ * seven-region sense: the closest point lies in the face interior, on an edge or at a vertex.
+ *   pts (B,P,3), verts (B,V,3) fp32, faces (Bf,F,3) int32 with Bf == 1 (one face list shared by all meshes) or Bf == B
+ *   -> dist2 (B,P) = min over faces of the squared distance (lowest face index on ties),
+ *      face (B,P) int32 a face that attains it (NULL: not written), closest (B,P,3) that closest point (NULL: not written)
+ * Faces without area are legal: they yield the distance to their longest edge, or to the point if all three vertices coincide;
+ * never NaN or Inf for finite input.  Face indices are NOT checked against V (the caller validates them once per face list).
+ * P, V, F > 0.  One launch, no workspace.
+ */
+int fsg_point_mesh_dist_f32(const float *pts, const float *verts, const int32_t *faces, int B, int P, int V, int F,
+                            int Bf, float *dist2, int32_t *face, float *closest, fsg_stream_t stream);
+
+/*
  * Segmentation loss, value and gradient: replaces losses/nnu_loss.py:6-19, i.e.
  * nn.CrossEntropyLoss(class_weights) + GDL(softmax over dim 1, batch_dice=True, do_bg=True, smooth=1, weights 1/volume)
  * of losses/dice_loss.py:24-96 (the criterion train.py:38 builds for the default --loss nnunet).

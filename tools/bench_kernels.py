@@ -102,3 +102,31 @@ if "maxavg" in which:   # conv5's BatchNorm + LeakyReLU + [max | mean] pooling a
             line += (f"  fwd {fwd_bytes / med_f / 1e3:6.0f} GB/s ({fwd_bytes / med_f / 8e6:.0%} of 8 TB/s)"
                      f"  bwd {bwd_bytes / med_b / 1e3:6.0f} GB/s ({bwd_bytes / med_b / 8e6:.0%})")
         print(line)
+if "pmdist" in which:   # point-to-mesh distance: the kernel, a torch composition of the same math on the device, the fp64 CPU oracle
+    import time
+    import metrics_oracle as mo
+    FLOP_PER_PAIR, PEAK = 110, 157.3e12   # nominal: ~65 VALU issues per pair evaluation, ~45 of them fma; fp32 vector peak of the guide
+    torch.set_num_threads(16)
+
+    def torch_form(p, v, f, chunk_pairs=8_000_000):   # the oracle's formula in fp32 on the device, chunked over queries
+        tri = v[f.long()]
+        step = max(1, chunk_pairs // len(tri))
+        return torch.cat([mo.tri_dist2(p[i:i + step, None, :], tri[None, :, 0], tri[None, :, 1], tri[None, :, 2]).min(1).values
+                          for i in range(0, len(p), step)]).sqrt()
+    for name, B, P, s in (("pcae", 2, 2025, 45), ("grid64", 1, 20000, 64), ("odd", 3, 131, 3), ("eval", 1, 100000, 159)):
+        verts, faces = mo.height_field_mesh(1, B, s)
+        if name == "odd":
+            faces = faces[:7]
+        pts = mo.height_field_points(2, B, P) if name != "pcae" else verts + 0.01
+        p, v, f = (torch.from_numpy(a).to(dev) for a in (pts.astype("float32"), verts, faces))
+        Fn, pairs = len(faces), B * P * len(faces)
+        med, mn = timeit(lambda: F.point_mesh_distance(p, v, f))
+        med_all, _ = timeit(lambda: F.point_mesh_distance(p, v, f, return_face=True, return_closest=True))
+        med_t, _ = timeit(lambda: [torch_form(p[b], v[b], f) for b in range(B)], iters=5, warm=1)
+        nq = min(P, 500)   # the CPU oracle is timed on a slice of the queries of mesh 0 and scaled to all of them
+        t0 = time.perf_counter()
+        mo.point_mesh_dist2(pts[0][:nq], verts[0], faces)
+        cpu_us = (time.perf_counter() - t0) * 1e6 * B * P / nq
+        print(f"pmdist {name} B={B} P={P} F={Fn}: kernel median {med:9.1f} us (min {mn:9.1f}; with face+closest {med_all:9.1f})  "
+              f"{pairs / med / 1e3:8.1f} G pair/s  {pairs * FLOP_PER_PAIR / (med * 1e-6) / PEAK:6.1%} of fp32 vector peak (nominal)  "
+              f"torch composition {med_t:10.1f} us  fp64 CPU oracle, 16 threads ~{cpu_us:12.0f} us (scaled from {nq} queries)")
