@@ -29,6 +29,9 @@ def install_reference_aliases():
         "losses.access_losses": ".losses.access_losses", "losses.mesh_loss": ".losses.mesh_loss",
         "losses.dgssm_loss": ".losses.dgssm_loss", "models.dg_ssm": ".models.dg_ssm",
         "shape_model": ".shape_model", "shape_model.ssm": ".shape_model.ssm", "metrics": ".metrics",
+        "data_processing.foerstner": ".data_processing.foerstner", "data_processing.point_features": ".data_processing.point_features",
+        "data_processing.keypoint_extraction": ".data_processing.keypoint_extraction",
+        "utils.image_utils": ".utils.image_utils", "utils.general_utils": ".utils.general_utils",
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)

@@ -121,6 +121,12 @@ SIGNATURES = {
     "fsg_pw_scatter_rows_workspace_bytes": ([_I, _I], ctypes.c_size_t),
     "fsg_pw_scatter_rows_f32": ([_P, _P, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P], _I),
     "fsg_pw_gf_dw_f32": ([_P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P], _I),
+    "fsg_foerstner_dist_f32": ([_P, _I, _I, _I, _I, _P, _I, _P, _P], _I),
+    "fsg_nms_keypoints": ([_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P], _I),
+    "fsg_mind_stats_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
+    "fsg_mind_stats_f32": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P], _I),
+    "fsg_mind_eval_f32": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P], _I),
+    "fsg_mind_eval_kp_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

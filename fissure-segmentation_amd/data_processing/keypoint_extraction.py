@@ -1,0 +1,50 @@
+"""From a volume and a lung mask to the point cloud of the point networks (the tensor part of the reference's
+data_processing/keypoint_extraction.py and point_features.py:163-203), tensors in, tensors out: no SimpleITK, no files."""
+import torch
+
+from ..utils.general_utils import ALIGN_CORNERS, kpts_to_grid
+from . import foerstner
+from .point_features import image_patch_features, mind_at_keypoints
+
+MAX_KPTS = 20000            # the reference's cap on the size of a cloud
+FEATURE_MODES = (None, 'mind', 'mind_ssc', 'image')
+HU_AIR, HU_WATER = -1000.0, 0.0   # 'image' patches are scaled so that air is -1 and water +1 (reference: normalize_img, max_val=0)
+
+
+def limit_keypoints(kp, max_num_kpts=MAX_KPTS):
+    """-> (kp, index): at most `max_num_kpts` rows of kp, drawn without replacement when there are more, and the row
+    indices that were kept (on kp's device when drawn; all rows, in order, otherwise)"""
+    n = kp.shape[0]
+    if n <= max_num_kpts:
+        return kp, torch.arange(n)
+    index = torch.randperm(n, device=kp.device)[:max_num_kpts]
+    return kp[index], index
+
+
+def foerstner_point_cloud(img, mask, spacing=(1, 1, 1), sigma=0.5, threshold=1e-8, nms_kernel=5, feature_mode=None):
+    """img, mask (1, 1, D, H, W) on the GPU, spacing (z, y, x) -> (C, K) fp32: rows 0..2 the keypoints in grid coordinates
+    (x, y, z) in [-1, 1], then the features of `feature_mode` (None: none, 'mind': 6, 'mind_ssc': 12, 'image': the 125
+    voxels of a 5^3 patch, intensities mapped linearly so that -1000 HU is -1 and 0 HU is +1 as the reference does for this
+    mode).  At most MAX_KPTS keypoints (a random subset beyond that).  The result, with a batch axis in front, is what
+    `predict_full_pointcloud` takes."""
+    if feature_mode not in FEATURE_MODES:
+        raise ValueError(f'unknown feature_mode {feature_mode!r}: expected one of {FEATURE_MODES}')
+    kp = foerstner.foerstner_kpts(img, mask, sigma=sigma, d=nms_kernel, thresh=threshold)
+    kp, _ = limit_keypoints(kp)
+    points = keypoints_to_grid(kp, img.shape[2:], spacing)
+    if feature_mode is None:
+        return points.contiguous()
+    if feature_mode == 'image':
+        feat = image_patch_features(img.float(), points.transpose(0, 1), patch_size=5)
+        feat = (feat - HU_AIR) / (HU_WATER - HU_AIR) * 2 - 1
+    else:
+        feat = mind_at_keypoints(img, kp, dilation=1, sigma=0.8, ssc=feature_mode == 'mind_ssc')
+    return torch.cat([points, feat], dim=0).contiguous()
+
+
+def keypoints_to_grid(kp, shape, spacing=(1, 1, 1)):
+    """voxel indices kp (K, 3) (z, y, x) of a volume with `shape` (D, H, W) and voxel `spacing` (z, y, x) -> (3, K) grid
+    coordinates (x, y, z): physical positions over the physical extent, as the reference stores its coordinate features"""
+    sp = torch.tensor(spacing, dtype=torch.float32, device=kp.device)
+    extent = torch.tensor(tuple(shape), device=kp.device) * sp
+    return kpts_to_grid((kp * sp).flip(-1), extent, align_corners=ALIGN_CORNERS).transpose(0, 1)

@@ -2413,3 +2413,143 @@ def pt_attn(p, idx, qkv, linear_p, linear_w):
     params = tuple(t if t.is_contiguous() else t.contiguous() for t in params)
     p = p if p.dtype == torch.float32 and p.is_contiguous() else p.float().contiguous()
     return _PTAttn.apply(p, idx.to(torch.int32).contiguous(), qkv.contiguous(), (bnp, bn1, bn2), *params)
+
+
+# ------------------------------------------------------------------ image front end: Foerstner keypoints, MIND (csrc/volume.hip)
+def gaussian_taps(sigma):
+    """the taps of utils/image_utils.py:25-29 (N = 2 ceil(1.5 sigma) + 1, normalised in fp32), computed the same way, on the
+    host -> (N,) fp32 CPU tensor"""
+    s = torch.tensor([float(sigma)])
+    n = int(torch.ceil(s * 3.0 / 2.0).long().item()) * 2 + 1
+    w = torch.exp(-torch.pow(torch.linspace(-(n // 2), n // 2, n), 2) / (2 * torch.pow(s, 2)))
+    w /= w.sum()
+    return w
+
+
+def _host_floats(t):
+    vals = [float(v) for v in t.tolist()]
+    return (ctypes.c_float * len(vals))(*vals), len(vals)
+
+
+def _host_ints(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int * len(vals))(*vals)
+
+
+def _volume(img, what="img"):
+    """(B, 1, D, H, W) -> contiguous fp32 and its four sizes"""
+    if img.dim() != 5 or img.shape[1] != 1:
+        raise ValueError(f"expected {what} (B, 1, D, H, W), got {tuple(img.shape)}")
+    v = _f32c(img)
+    return v, (v.shape[0], v.shape[2], v.shape[3], v.shape[4])
+
+
+def foerstner_distinctiveness(img, sigma):
+    """data_processing/foerstner.py:62-73 in one launch (fsg_foerstner_dist_f32): img (B, 1, D, H, W) -> (B, 1, D, H, W).
+    NaN where the smoothed structure tensor is singular, like the reference."""
+    _need_gpu(img)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(img)
+        w, n = _host_floats(gaussian_taps(sigma))
+        out = torch.empty_like(v)
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_foerstner_dist_f32", _p(v), B, D, H, W, w, n, _p(out), _stream())
+    return out
+
+
+def _mask_bytes(mask, shape):
+    if mask is None:
+        return None
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the volume {tuple(shape)}")
+    return (mask != 0).to(torch.uint8).contiguous()
+
+
+def nms_max(data, kernel_size):
+    """utils/image_utils.py:38-50 (fsg_nms_keypoints): window maximum with the reference's asymmetric padding for even
+    kernels; NaN propagates.  data (B, 1, D, H, W) -> same shape"""
+    _need_gpu(data)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(data, "data")
+        out = torch.empty_like(v)
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_nms_keypoints", _p(v), None, B, D, H, W, int(kernel_size), 0.0, _p(out), None, _stream())
+    return out
+
+
+def nms_keypoint_flags(dist, mask, d, thresh):
+    """foerstner.py:90-107 without the nonzero: eroded(mask) & (window max == dist) & (dist >= thresh) -> (B, 1, D, H, W) bool"""
+    _need_gpu(dist, mask)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(dist, "dist")
+        m = _mask_bytes(mask, v.shape)
+        flags = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_nms_keypoints", _p(v), _p(m), B, D, H, W, int(d), float(thresh), None, _p(flags), _stream())
+    return flags.bool()
+
+
+def _mind_tables(shifts, outch):
+    nch = len(shifts)
+    flat = [int(v) for pair in shifts for voxel in pair for v in (voxel if isinstance(voxel, (tuple, list)) else (voxel,))]
+    return nch, _host_ints(flat), _host_ints(outch if outch is not None else range(nch))
+
+
+def mind_mean(img, dilation, sigma, shifts, box):
+    """statistics pass (fsg_mind_stats_f32): the mean over the batch volume of mean_c(ssd_c - min_c ssd_c) -> (1,) fp32 on the
+    device.  `shifts`: per channel the two voxel offsets ((dz, dy, dx), (dz, dy, dx)) in {-1, 0, 1}; with `box`, per channel two
+    27-bit subsets of the 3 x 3 x 3 stencil whose sums are compared."""
+    _need_gpu(img)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(img)
+        nch, sh, _ = _mind_tables(shifts, None)
+        w, n = _host_floats(gaussian_taps(sigma))
+        ws = torch.empty(_lib.lib.fsg_mind_stats_workspace_bytes(B, D, H, W) // 4 + 1, dtype=torch.float32, device=v.device)
+        mean = torch.empty(1, dtype=torch.float32, device=v.device)
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_mind_stats_f32", _p(v), B, D, H, W, int(dilation), nch, int(box), sh, w, n, _p(ws), _p(mean), _stream())
+    return mean
+
+
+def mind_volume(img, dilation, sigma, shifts, outch, box, mean=None):
+    """statistics + evaluation pass for the whole volume -> (B, nch, D, H, W)"""
+    _need_gpu(img)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(img)
+        if mean is None:
+            mean = mind_mean(v, dilation, sigma, shifts, box)
+        nch, sh, oc = _mind_tables(shifts, outch)
+        w, n = _host_floats(gaussian_taps(sigma))
+        out = torch.empty(B, nch, D, H, W, dtype=torch.float32, device=v.device)
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_mind_eval_f32", _p(v), B, D, H, W, int(dilation), nch, int(box), sh, oc, w, n, _p(mean), _p(out),
+                      _stream())
+    return out
+
+
+def mind_keypoints(img, kp, dilation, sigma, shifts, outch, box, mean=None):
+    """statistics pass + evaluation at kp (K, 3) voxel indices (z, y, x) of ONE volume -> (nch, K); the feature volume is
+    never written"""
+    _need_gpu(img, kp)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(img)
+        if B != 1:
+            raise ValueError("mind_keypoints: one volume at a time")
+        if kp.dim() != 2 or kp.shape[1] != 3 or kp.is_floating_point():
+            raise ValueError(f"expected kp (K, 3) integer voxel indices, got {tuple(kp.shape)} {kp.dtype}")
+        nch, sh, oc = _mind_tables(shifts, outch)
+        K = kp.shape[0]
+        out = torch.empty(nch, K, dtype=torch.float32, device=v.device)
+        if K == 0:
+            return out
+        kpc = kp.detach().to(torch.int64).contiguous()
+        lo, hi = kpc.amin(0).tolist(), kpc.amax(0).tolist()
+        if min(lo) < 0 or any(h >= s for h, s in zip(hi, (D, H, W))):
+            raise ValueError(f"keypoints span {lo}..{hi}, outside the volume {(D, H, W)}")
+        if mean is None:
+            mean = mind_mean(v, dilation, sigma, shifts, box)
+        w, n = _host_floats(gaussian_taps(sigma))
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_mind_eval_kp_f32", _p(v), D, H, W, int(dilation), nch, int(box), sh, oc, w, n, _p(mean), _p(kpc), K,
+                      _p(out), _stream())
+    return out

@@ -53,3 +53,53 @@ def farthest_point_sampling(kpts, num_points, start=None):
     new_offset = torch.tensor([num_points], dtype=torch.int32, device=kpts.device)
     ind = (F_hip.fps(pts, offset, new_offset, num_points).long() + start) % N
     return kpts[:, ind, :], ind
+
+
+# ------------------------------------------------------------------ voxel <-> grid coordinates, patches (plain torch, any device)
+ALIGN_CORNERS = False
+
+
+def _extent_xyz(shape, device):
+    depth, height, width = shape
+    return torch.tensor([width, height, depth], device=device)
+
+
+def kpts_to_grid(kpts_world, shape, align_corners=None, return_transform=False):
+    """Same contract as the reference's utils/general_utils.py: kpts_to_grid -- points (N, 3) in (x, y, z) voxel units of a
+    volume with `shape` (D, H, W) -> torch grid coordinates: index 0 maps to -1 and index size - 1 to +1, and without
+    `align_corners` the result is shrunk by (size - 1) / size so that voxel CENTRES sit where `grid_sample` expects them.
+    `return_transform` would need pytorch3d's Transform3d, which this package does not depend on."""
+    if return_transform:
+        raise NotImplementedError("kpts_to_grid(return_transform=True) needs pytorch3d, which this package does not use")
+    size = _extent_xyz(shape, kpts_world.device)
+    grid = (kpts_world * (1 / (size - 1))) * 2 - 1
+    if not align_corners:
+        grid = grid * ((size - 1) / size)
+    return grid
+
+
+def kpts_to_world(kpts_pt, shape, align_corners=None):
+    """the inverse of `kpts_to_grid`: grid coordinates (N, 3) in (x, y, z) -> voxel units of a volume with `shape` (D, H, W)"""
+    size = _extent_xyz(shape, kpts_pt.device)
+    if not align_corners:
+        kpts_pt = kpts_pt / ((size - 1) / size)
+    return ((kpts_pt + 1) / 2) * (size - 1)
+
+
+def sample_patches_at_kpts(img: torch.Tensor, kpts_grid: torch.Tensor, patch_size: int):
+    """Same contract as the reference's sample_patches_at_kpts: img (1, 1, D, H, W), kpts_grid (N, 3) grid coordinates
+    (x, y, z) -> (1, N, p, p, p) with p = patch_size: a p^3 lattice of voxel-spaced samples centred on every keypoint, read by
+    one `grid_sample` call (nearest for odd p, where the lattice falls on voxel centres; trilinear for even p; border
+    padding)."""
+    if bool(kpts_grid.min() < -1) or bool(kpts_grid.max() > 1):
+        raise ValueError('sample_patches_at_kpts: keypoints outside [-1, 1] (expected torch grid coordinates, see kpts_to_grid)')
+    if tuple(img.shape[:2]) != (1, 1):
+        raise NotImplementedError(f'sample_patches_at_kpts: one single-channel volume at a time, got {tuple(img.shape)}')
+    n, p = kpts_grid.shape[0], patch_size
+    nn_f = torch.nn.functional
+    # the identity lattice over [-1, 1]^3 with p samples per axis, scaled to p voxels of this volume
+    lattice = nn_f.affine_grid(torch.eye(3, 4)[None], [1, 1, p, p, p], align_corners=ALIGN_CORNERS).to(img.device)
+    lattice = lattice * (p / torch.tensor(tuple(img.shape[:1:-1]), device=img.device))
+    grid = (lattice + kpts_grid.view(n, 1, 1, 1, 3)).reshape(1, n, p ** 3, 1, 3)
+    out = nn_f.grid_sample(img, grid, mode='nearest' if p % 2 else 'bilinear', padding_mode='border', align_corners=ALIGN_CORNERS)
+    return out.view(1, n, p, p, p)

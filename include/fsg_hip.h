@@ -800,6 +800,46 @@ int fsg_pw_gf_dw_f32(const float *coef, const int32_t *arg, const float *X, int6
                      int64_t ldw, const float *G, const float *P, const float *Q, int B, int C, int K, int Npts, float *dW,
                      int64_t lddw, fsg_stream_t stream);
 
+/*
+ * Image front end on single-channel fp32 volumes (B, D, H, W), contiguous: Foerstner keypoints
+ * (data_processing/foerstner.py:62-108) and MIND descriptors (data_processing/point_features.py:86-150).  Everything here is
+ * an evaluation primitive, not differentiable.  `weights` (HOST, N odd <= 9 floats) are the taps of utils/image_utils.py:
+ * smooth; the host computes them the way the reference does and the kernels apply them along axes 0, 1, 2 with replicate
+ * padding.  All intermediate volumes of the torch composition (gradients, products, squared differences, partially smoothed
+ * channels) live in LDS only.
+ *
+ * Distinctiveness: out (B, D, H, W) = 1 / trace(inverse(smoothed structure tensor of the 5-tap central-difference gradient)),
+ *   in the reference's operation order; NaN where the tensor is singular (constant regions), exactly like the reference.
+ *
+ * Non-maximum suppression: window maximum of utils/image_utils.py: nms over [i - (d - d/2 - 1), i + d/2] per axis (even d is
+ *   asymmetric), replicate padding, NaN propagates through the window.  maxout (B, D, H, W) fp32 or NULL; flags (B, D, H, W)
+ *   bytes or NULL: flags = eroded(mask) & (max == dist) & (dist >= thresh), where a voxel survives the erosion iff its six face
+ *   neighbours inside the volume are all set in `mask` (bytes, NULL = all set) -- the voxel's OWN mask value does not count
+ *   (foerstner.py:93-104).  d <= 13.
+ *
+ * MIND: `shifts` (HOST, nch x 2 x 3 ints in {-1, 0, 1}) are the two voxels of every channel's pair, scaled by `dilation`
+ *   (1..4).  box != 0 selects the general form the reference's ssc = False kernels need (point_features.py:129-132):
+ *   `shifts` is then nch x 2 ints, each a 27-bit subset of the dilated 3 x 3 x 3 stencil (bit (kz * 3 + ky) * 3 + kx), and
+ *   the two operands of a channel are the sums over their subsets.  nch is 6 or 12.  `outch` (HOST, nch ints) is the output position of
+ *   channel c.  The statistics pass writes mean (DEVICE, 1 float) = mean over all voxels of mean_c(ssd_c - min_c ssd_c),
+ *   reduced in a fixed order through `workspace` (fsg_mind_stats_workspace_bytes) -- deterministic, no float atomics, no
+ *   feature volume.  The evaluation passes read it and write exp(-(ssd - min) / clamp(mean_c, 0.001 mean, 1000 mean)) for
+ *   the whole volume (out (B, nch, D, H, W)) or for K voxels kp (K, 3) int64 (z, y, x) of ONE volume (out (nch, K));
+ *   coordinates outside the volume are clamped).  Both run the same code, so the values are bitwise equal.
+ */
+int fsg_foerstner_dist_f32(const float *img, int B, int D, int H, int W, const float *weights, int N, float *out,
+                           fsg_stream_t stream);
+int fsg_nms_keypoints(const float *dist, const uint8_t *mask, int B, int D, int H, int W, int d, float thresh, float *maxout,
+                      uint8_t *flags, fsg_stream_t stream);
+size_t fsg_mind_stats_workspace_bytes(int B, int D, int H, int W);
+int fsg_mind_stats_f32(const float *img, int B, int D, int H, int W, int dilation, int nch, int box, const int *shifts,
+                       const float *weights, int N, void *workspace, float *mean, fsg_stream_t stream);
+int fsg_mind_eval_f32(const float *img, int B, int D, int H, int W, int dilation, int nch, int box, const int *shifts,
+                      const int *outch, const float *weights, int N, const float *mean, float *out, fsg_stream_t stream);
+int fsg_mind_eval_kp_f32(const float *img, int D, int H, int W, int dilation, int nch, int box, const int *shifts,
+                         const int *outch, const float *weights, int N, const float *mean, const int64_t *kp, int K, float *out,
+                         fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

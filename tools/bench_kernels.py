@@ -130,3 +130,41 @@ if "pmdist" in which:   # point-to-mesh distance: the kernel, a torch compositio
         print(f"pmdist {name} B={B} P={P} F={Fn}: kernel median {med:9.1f} us (min {mn:9.1f}; with face+closest {med_all:9.1f})  "
               f"{pairs / med / 1e3:8.1f} G pair/s  {pairs * FLOP_PER_PAIR / (med * 1e-6) / PEAK:6.1%} of fp32 vector peak (nominal)  "
               f"torch composition {med_t:10.1f} us  fp64 CPU oracle, 16 threads ~{cpu_us:12.0f} us (scaled from {nq} queries)")
+if "frontend" in which:
+    # image front end (csrc/volume.hip) beside the torch composition of the same math on the same device (the oracle's fp32
+    # code, tests/frontend_oracle.py): microseconds, GB/s against the compulsory bytes, peak device memory of both
+    import json
+    import frontend_oracle as fo
+    from fissure_segmentation_amd.data_processing import foerstner, point_features
+    shapes = [tuple(int(v) for v in a.split("x")) for a in os.environ.get("FSG_FRONTEND_SHAPES", "128x128x128,256x256x320,320x320x352").split(",")]
+
+    def measure(fn, iters=10, warm=2):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        try:
+            med, mn = timeit(fn, iters, warm)
+        except torch.OutOfMemoryError:
+            return None, None
+        return med, (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+    def line(shape, name, bytes_needed, ours, theirs):
+        rec = dict(kernel=name, shape="x".join(map(str, shape)), voxels=int(torch.tensor(shape).prod()))
+        for tag, (us, mib) in (("hip", ours), ("torch", theirs)):
+            rec[tag + "_us"] = None if us is None else round(us, 1)
+            rec[tag + "_peak_MiB"] = None if mib is None else round(mib, 1)
+            rec[tag + "_GBps"] = None if us is None else round(bytes_needed / us / 1e3, 1)
+        print("FRONTEND " + json.dumps(rec), flush=True)
+
+    for shape in shapes:
+        img = fo.ct_volume(1, (32, 32, 32)).to(dev)
+        img = torch.nn.functional.interpolate(img, size=shape, mode="trilinear") + 5 * torch.randn(1, 1, *shape, device=dev)
+        mask = torch.ones(1, 1, *shape, dtype=torch.bool, device=dev)
+        vox = img.numel()
+        kp = torch.stack([torch.randint(0, s, (20000,), device=dev) for s in shape], 1)
+        line(shape, "distinctiveness sigma=0.5", 8 * vox, measure(lambda: foerstner.distinctiveness(img, 0.5)),
+             measure(lambda: fo.distinctiveness(img, 0.5)))
+        line(shape, "foerstner_kpts sigma=0.5 d=5", 9 * vox, measure(lambda: foerstner.foerstner_kpts(img, mask, 0.5, 5)),
+             measure(lambda: fo.foerstner_kpts(img, mask, 0.5, 5)))
+        line(shape, "mind_at_keypoints K=20000", 4 * vox + 48 * 20000, measure(lambda: point_features.mind_at_keypoints(img, kp)),
+             measure(lambda: fo.mind(img)[0][:, kp[:, 0], kp[:, 1], kp[:, 2]]))
+        line(shape, "mind ssc", 52 * vox, measure(lambda: point_features.mind(img)), measure(lambda: fo.mind(img)))
