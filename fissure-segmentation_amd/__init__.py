@@ -31,6 +31,7 @@ def install_reference_aliases():
         "shape_model": ".shape_model", "shape_model.ssm": ".shape_model.ssm", "metrics": ".metrics",
         "data_processing.foerstner": ".data_processing.foerstner", "data_processing.point_features": ".data_processing.point_features",
         "data_processing.keypoint_extraction": ".data_processing.keypoint_extraction",
+        "data_processing.fissure_enhancement": ".data_processing.fissure_enhancement",
         "utils.image_utils": ".utils.image_utils", "utils.general_utils": ".utils.general_utils",
     }
     for ref_name, ours in pairs.items():

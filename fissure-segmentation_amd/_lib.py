@@ -127,6 +127,8 @@ SIGNATURES = {
     "fsg_mind_stats_f32": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P], _I),
     "fsg_mind_eval_f32": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P], _I),
     "fsg_mind_eval_kp_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P], _I),
+    "fsg_fissure_enhance_f32": ([_P, _P, _I, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P], _I),
+    "fsg_smooth_threshold_f32": ([_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _F, _P, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

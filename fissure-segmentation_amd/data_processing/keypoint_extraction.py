@@ -3,11 +3,13 @@ data_processing/keypoint_extraction.py and point_features.py:163-203), tensors i
 import torch
 
 from ..utils.general_utils import ALIGN_CORNERS, kpts_to_grid
+from .. import functional as F_hip
 from . import foerstner
 from .point_features import image_patch_features, mind_at_keypoints
 
 MAX_KPTS = 20000            # the reference's cap on the size of a cloud
 FEATURE_MODES = (None, 'mind', 'mind_ssc', 'image')
+ENHANCEMENT_FEATURE_MODES = FEATURE_MODES + ('enhancement',)   # of enhancement_point_cloud
 HU_AIR, HU_WATER = -1000.0, 0.0   # 'image' patches are scaled so that air is -1 and water +1 (reference: normalize_img, max_val=0)
 
 
@@ -35,6 +37,53 @@ def foerstner_point_cloud(img, mask, spacing=(1, 1, 1), sigma=0.5, threshold=1e-
     if feature_mode is None:
         return points.contiguous()
     if feature_mode == 'image':
+        feat = image_patch_features(img.float(), points.transpose(0, 1), patch_size=5)
+        feat = (feat - HU_AIR) / (HU_WATER - HU_AIR) * 2 - 1
+    else:
+        feat = mind_at_keypoints(img, kp, dilation=1, sigma=0.8, ssc=feature_mode == 'mind_ssc')
+    return torch.cat([points, feat], dim=0).contiguous()
+
+
+def hessian_enhancement_kpts(enhanced, min_threshold=0.2, max_kpts=MAX_KPTS, spacing=(1, 1, 1), taps=None):
+    """keypoint_extraction.py:134-141: enhanced (1, 1, D, H, W) on the GPU -> (K', 3) int64 voxel indices (z, y, x) of the at
+    most `max_kpts` largest voxels of the smoothed image that exceed `min_threshold`, by value descending, ties by linear
+    voxel index ascending.  The smoothing is ITK's discrete Gaussian of physical variance 1 (`spacing` (z, y, x) turns it
+    into voxel variances) from `functional.discrete_gaussian_taps`, or explicit `taps` = (taps_z, taps_y, taps_x).  One
+    launch smooths and thresholds; `select_candidates` compacts the candidates and sorts only them."""
+    if enhanced.dim() != 5 or enhanced.shape[0] != 1:
+        raise ValueError(f'expected one volume (1, 1, D, H, W), got {tuple(enhanced.shape)}')
+    if taps is None:
+        taps = F_hip.discrete_gaussian_taps(1.0, spacing=spacing)
+    values, flags = F_hip.smooth_threshold(enhanced, taps, min_threshold)
+    return select_candidates(values[0, 0], flags[0, 0], max_kpts)
+
+
+def select_candidates(values, flags, max_kpts=MAX_KPTS):
+    """values (D, H, W), flags (D, H, W) bool, any device -> (K', 3) int64 (z, y, x): the flagged voxels, at most `max_kpts`
+    of them, by value descending, ties by linear voxel index ascending.  The volume is compacted once (`torch.nonzero` of the
+    flat flags, which lists linear indices in ascending order) and only the candidates are sorted, stably."""
+    D, H, W = values.shape
+    lin = torch.nonzero(flags.reshape(-1)).squeeze(1)
+    order = torch.sort(values.reshape(-1)[lin], descending=True, stable=True).indices[:int(max_kpts)]
+    lin = lin[order]
+    return torch.stack([lin // (H * W), (lin // W) % H, lin % W], dim=1)
+
+
+def enhancement_point_cloud(img, mask, fissure_mu, fissure_sigma, spacing=(1, 1, 1), min_threshold=0.2, feature_mode=None):
+    """`foerstner_point_cloud` for the reference's 'enhancement' keypoint mode: img, mask (1, 1, D, H, W) on the GPU ->
+    (C, K) fp32, rows 0..2 the keypoints of `hessian_enhancement_kpts` on the lung-masked enhanced image in grid
+    coordinates (x, y, z), then the features of `feature_mode`: those of FEATURE_MODES, or 'enhancement', the 125 voxels of a
+    5^3 patch of the masked, unsmoothed enhanced image, not normalised (point_features.py:182-199)."""
+    if feature_mode not in ENHANCEMENT_FEATURE_MODES:
+        raise ValueError(f'unknown feature_mode {feature_mode!r}: expected one of {ENHANCEMENT_FEATURE_MODES}')
+    enhanced = F_hip.fissure_enhance(img, fissure_mu, fissure_sigma, 1.0, mask=mask)
+    kp = hessian_enhancement_kpts(enhanced, min_threshold=min_threshold, spacing=spacing)
+    points = keypoints_to_grid(kp, img.shape[2:], spacing)
+    if feature_mode is None:
+        return points.contiguous()
+    if feature_mode == 'enhancement':
+        feat = image_patch_features(enhanced, points.transpose(0, 1), patch_size=5)
+    elif feature_mode == 'image':
         feat = image_patch_features(img.float(), points.transpose(0, 1), patch_size=5)
         feat = (feat - HU_AIR) / (HU_WATER - HU_AIR) * 2 - 1
     else:

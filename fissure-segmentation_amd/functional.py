@@ -2553,3 +2553,112 @@ def mind_keypoints(img, kp, dilation, sigma, shifts, outch, box, mean=None):
             _lib.call("fsg_mind_eval_kp_f32", _p(v), D, H, W, int(dilation), nch, int(box), sh, oc, w, n, _p(mean), _p(kpc), K,
                       _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------ Hessian fissure enhancement (csrc/fissure_enhance.hip)
+MAX_TAP_RADIUS = 4   # of the derivative taps (derivation sigma <= 1) and of the keypoint smoothing taps
+
+
+def gaussian_derivative_taps(sigma, order, truncate=4.0):
+    """utils/image_utils.py:53-58 (scipy's Gaussian kernel of derivative `order`, radius int(truncate sigma + 0.5)), computed
+    the same way in fp64 on the host and cast -> (2 radius + 1,) fp32 CPU tensor"""
+    import numpy as np
+    sigma, order = float(sigma), int(order)
+    if not sigma > 0 or order < 0:
+        raise ValueError(f"gaussian_derivative_taps: sigma {sigma} must be positive and order {order} non-negative")
+    radius = int(truncate * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    if order > 0:   # q <- q' + q p', p' = -x / sigma^2, applied to the coefficients of q `order` times
+        exponents = np.arange(order + 1)
+        q = np.zeros(order + 1)
+        q[0] = 1
+        step = np.diag(exponents[1:], 1) + np.diag(np.ones(order) / -(sigma * sigma), -1)
+        for _ in range(order):
+            q = step.dot(q)
+        phi = (x[:, None] ** exponents).dot(q) * phi
+    return torch.from_numpy(phi).float()
+
+
+def discrete_gaussian_taps(variance, max_error=0.01, max_width=32, spacing=None):
+    """the operator of ITK's DiscreteGaussianImageFilter as ITK documents it (GaussianOperator): coefficients exp(-t) I_k(t),
+    t the variance in voxels, terms added until their sum reaches 1 - max_error (or the width reaches max_width), then
+    normalised.  `variance` is a number or one per axis (z, y, x); with `spacing` (z, y, x) it is physical and becomes
+    variance / spacing^2 per axis (useImageSpacing).  -> three fp32 CPU tensors (z, y, x).  Parity with SimpleITK itself is
+    not pinned by a test; pass explicit taps to `smooth_threshold` to use SimpleITK's."""
+    from scipy.special import ive
+    var = [float(variance)] * 3 if not hasattr(variance, "__len__") else [float(v) for v in variance]
+    sp = [1.0] * 3 if spacing is None else [float(s) for s in spacing]
+    if len(var) != 3 or len(sp) != 3 or min(var) < 0 or min(sp) <= 0:
+        raise ValueError(f"discrete_gaussian_taps: variance {variance} / spacing {spacing} must be three non-negative / positive numbers")
+    taps = []
+    for v, s in zip(var, sp):
+        t = v / (s * s)
+        half = [float(ive(0, t))]
+        total = half[0]
+        while total < 1.0 - max_error and 2 * len(half) + 1 <= max_width:
+            half.append(float(ive(len(half), t)))
+            total += 2 * half[-1]
+        full = half[:0:-1] + half
+        taps.append((torch.tensor(full, dtype=torch.float64) / total).float())
+    return tuple(taps)
+
+
+def _odd_taps(t, what):
+    t = torch.as_tensor(t, dtype=torch.float32).detach().cpu().flatten()
+    if t.numel() % 2 == 0 or t.numel() > 2 * MAX_TAP_RADIUS + 1:
+        raise ValueError(f"{what}: {t.numel()} taps; the kernel takes an odd number, at most {2 * MAX_TAP_RADIUS + 1} "
+                         f"(radius {MAX_TAP_RADIUS})")
+    return t
+
+
+def fissure_enhance_check_sigma(derivation_sigma):
+    """the derivative taps of `derivation_sigma` must fit the kernel's radius (1..4): -> (k1, k2) fp32 CPU tensors"""
+    k1, k2 = gaussian_derivative_taps(derivation_sigma, 1), gaussian_derivative_taps(derivation_sigma, 2)
+    if k1.numel() > 2 * MAX_TAP_RADIUS + 1 or k1.numel() < 3:
+        raise ValueError(f"fissure_enhance: derivation sigma {derivation_sigma} gives a tap radius of {k1.numel() // 2}; the "
+                         f"kernel takes 1..{MAX_TAP_RADIUS} (sigma <= 1)")
+    return k1, k2
+
+
+def fissure_enhance(img, fissure_mu, fissure_sigma, derivation_sigma=1.0, mask=None, return_intermediate=False):
+    """HessianEnhancementFilter.forward + fissure_filter (data_processing/fissure_enhancement.py:47-99, 149-180) in one launch
+    (fsg_fissure_enhance_f32): img (B, 1, D, H, W) -> F of the same shape, times (mask != 0) when a mask of that shape is
+    given; with `return_intermediate` -> (F, planeness, HU weight).  The derivation sigma is at most 1 (tap radius 4)."""
+    k1, k2 = fissure_enhance_check_sigma(derivation_sigma)
+    if not float(fissure_sigma) > 0:
+        raise ValueError(f"fissure_enhance: fissure_sigma {fissure_sigma} must be positive")
+    _need_gpu(img, mask)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(img)
+        if mask is not None and mask.dtype in (torch.bool, torch.uint8) and mask.is_contiguous() and mask.shape == v.shape:
+            m = mask.view(torch.uint8)          # the kernel tests the byte against 0: no dense conversion pass
+        else:
+            m = _mask_bytes(mask, v.shape)
+        out = torch.empty_like(v)
+        P, hw = (torch.empty_like(v), torch.empty_like(v)) if return_intermediate else (None, None)
+        w1, n = _host_floats(k1)
+        w2, _ = _host_floats(k2)
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_fissure_enhance_f32", _p(v), _p(m), B, D, H, W, w1, w2, n, float(fissure_mu), float(fissure_sigma),
+                      _p(out), _p(P), _p(hw), _stream())
+    return (out, P, hw) if return_intermediate else out
+
+
+def smooth_threshold(vol, taps, thresh, return_flags=True):
+    """fsg_smooth_threshold_f32: vol (B, 1, D, H, W) smoothed separably with `taps` = (taps_z, taps_y, taps_x) (odd counts,
+    radius <= 4; axis order 0, 1, 2; replicate padding) -> (values, flags): the smoothed value where it exceeds `thresh` and 0
+    elsewhere, and that comparison as (B, 1, D, H, W) bool (values alone with return_flags=False)"""
+    if len(taps) != 3:
+        raise ValueError("smooth_threshold: expected three tap vectors (z, y, x)")
+    host = [_host_floats(_odd_taps(t, f"smooth_threshold: axis {ax}")) for ax, t in enumerate(taps)]
+    _need_gpu(vol)
+    with torch.no_grad():
+        v, (B, D, H, W) = _volume(vol, "vol")
+        out = torch.empty_like(v)
+        flags = torch.empty(v.shape, dtype=torch.uint8, device=v.device) if return_flags else None
+        with torch.cuda.device(v.device):
+            _lib.call("fsg_smooth_threshold_f32", _p(v), B, D, H, W, host[0][0], host[0][1], host[1][0], host[1][1], host[2][0],
+                      host[2][1], float(thresh), _p(out), _p(flags), _stream())
+    return (out, flags.view(torch.bool)) if return_flags else out   # the kernel writes 0 or 1: a view, not a pass

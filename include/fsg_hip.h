@@ -840,6 +840,29 @@ int fsg_mind_eval_kp_f32(const float *img, int D, int H, int W, int dilation, in
                          const int *outch, const float *weights, int N, const float *mean, const int64_t *kp, int K, float *out,
                          fsg_stream_t stream);
 
+/* Hessian fissure enhancement and its keypoint candidates (csrc/fissure_enhance.hip).  Volumes are (B, 1, D, H, W) fp32,
+ * DEVICE; tap vectors are HOST pointers.
+ *
+ * fsg_fissure_enhance_f32 replaces HessianEnhancementFilter.forward + fissure_filter of the reference
+ *   (data_processing/fissure_enhancement.py:47-99, 149-180) and, with `mask`, the lung-mask product of
+ *   get_enhanced_fissure_image (:213-214).  k1 / k2 (N taps each, N odd, 3..9) are the first- and second-derivative
+ *   Gaussian taps of utils/image_utils.py:53-58 in fp32; k1 must be antisymmetric and k2 symmetric, bit for bit.  Per voxel:
+ *   H[a][a] = k2 along axis a, H[a][b] = k1 along a then k1 along b (a < b), replicate padding; the eigenvalues sorted by
+ *   absolute value, descending; P = (|l1| - |l2|) / (|l1| + |l2|) where l1 < 0, else 0; out = exp(-(img - mu)^2 /
+ *   (2 sigma_hu^2)) * P, times (mask != 0) when mask (bytes) is given.  planeness / hu_weight (NULL or DEVICE, the shape of
+ *   out) receive P and the HU weight (return_intermediate).  Where the (2R + 1)^3 support of a voxel is constant, out and P
+ *   are exactly 0.  No intermediate volume is written.
+ *
+ * fsg_smooth_threshold_f32 is the dense part of get_hessian_fissure_enhancement_kpts (data_processing/
+ *   keypoint_extraction.py:134-141): separable smoothing with per-axis taps wz, wy, wx (odd counts, at most 9; axis order
+ *   0, 1, 2; replicate padding), then out = s > thresh ? s : 0 and flags (bytes) = s > thresh.  Either output may be NULL.
+ */
+int fsg_fissure_enhance_f32(const float *img, const uint8_t *mask, int B, int D, int H, int W, const float *k1, const float *k2,
+                            int N, float mu, float sigma_hu, float *out, float *planeness, float *hu_weight,
+                            fsg_stream_t stream);
+int fsg_smooth_threshold_f32(const float *vol, int B, int D, int H, int W, const float *wz, int Nz, const float *wy, int Ny,
+                             const float *wx, int Nx, float thresh, float *out, uint8_t *flags, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

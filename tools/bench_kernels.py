@@ -168,3 +168,78 @@ if "frontend" in which:
         line(shape, "mind_at_keypoints K=20000", 4 * vox + 48 * 20000, measure(lambda: point_features.mind_at_keypoints(img, kp)),
              measure(lambda: fo.mind(img)[0][:, kp[:, 0], kp[:, 1], kp[:, 2]]))
         line(shape, "mind ssc", 52 * vox, measure(lambda: point_features.mind(img)), measure(lambda: fo.mind(img)))
+if "hessian" in which:
+    # Hessian fissure enhancement (csrc/fissure_enhance.hip) beside the torch composition of the same math on the same device
+    # (the oracle's fp32 code, tests/hessian_oracle.py) over the whole volume -- None where its (D, H, W, 3, 3) tensor and the
+    # eigvalsh workspace do not fit -- and beside the way the reference runs that composition on a GPU: over 64^3 patches with
+    # an overlap of a quarter, blended with a Gaussian weight.
+    import json
+    import frontend_oracle as fo
+    import hessian_oracle as ho
+    from fissure_segmentation_amd.data_processing import keypoint_extraction as ke
+    shapes = [tuple(int(v) for v in a.split("x")) for a in os.environ.get("FSG_FRONTEND_SHAPES", "128x128x128,256x256x320,320x320x352").split(",")]
+
+    def measure(fn, iters=10, warm=2):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        try:
+            med, mn = timeit(fn, iters, warm)
+        except torch.OutOfMemoryError:
+            return None, None
+        return med, (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+    def patch_loop(img, patch=64, overlap=0.25):
+        shape = img.shape[2:]
+        out, weight = torch.zeros(shape, device=dev), torch.zeros(shape, device=dev)
+        r = torch.arange(patch, device=dev) - (patch - 1) / 2
+        g = torch.exp(-r ** 2 / (2 * (patch / 8) ** 2))
+        g3 = g[:, None, None] * g[None, :, None] * g[None, None, :]
+        starts = []
+        for s in shape:
+            n = max(1, -(-(s - patch) // int(patch * (1 - overlap))) + 1)
+            starts.append(sorted({min(int(round(i * max(s - patch, 0) / max(n - 1, 1))), max(s - patch, 0)) for i in range(n)}))
+        for z in starts[0]:
+            for y in starts[1]:
+                for x in starts[2]:
+                    sl = (slice(z, z + patch), slice(y, y + patch), slice(x, x + patch))
+                    p = ho.enhance(img[(slice(None), slice(None)) + sl])[0]
+                    w = g3[: p.shape[0], : p.shape[1], : p.shape[2]]
+                    out[sl] += p * w
+                    weight[sl] += w
+        return out / weight
+
+    for shape in shapes:
+        img = fo.ct_volume(1, (32, 32, 32)).to(dev)
+        img = torch.nn.functional.interpolate(img, size=shape, mode="trilinear") + 5 * torch.randn(1, 1, *shape, device=dev)
+        mask = torch.ones(1, 1, *shape, dtype=torch.bool, device=dev)
+        vox = img.numel()
+        enhanced = F.fissure_enhance(img, ho.MU, ho.SIGMA_HU, mask=mask)
+        taps = F.discrete_gaussian_taps(1.0)
+        rec = dict(kernel="fissure_enhance sigma=1", shape="x".join(map(str, shape)), voxels=vox)
+        us, mib = measure(lambda: F.fissure_enhance(img, ho.MU, ho.SIGMA_HU))
+        rec.update(hip_us=round(us, 1), hip_peak_MiB=round(mib, 1), hip_GBps=round(8 * vox / us / 1e3, 1))
+        us, mib = measure(lambda: F.fissure_enhance(img, ho.MU, ho.SIGMA_HU, mask=mask, return_intermediate=True))
+        rec.update(hip_masked_3out_us=round(us, 1), hip_masked_3out_peak_MiB=round(mib, 1))
+        print("hessian: fused side of %s done, composition running" % rec["shape"], file=sys.stderr, flush=True)
+        for tag, fn in (("torch", lambda: ho.enhance(img)[0]), ("torch_patch_loop", lambda: patch_loop(img))):
+            us, mib = measure(fn, iters=3, warm=1)
+            rec[tag + "_us"] = None if us is None else round(us, 1)
+            rec[tag + "_peak_MiB"] = None if mib is None else round(mib, 1)
+        print("HESSIAN " + json.dumps(rec), flush=True)
+        rec = dict(kernel="smooth_threshold var=1 thresh=0.2", shape=rec["shape"], voxels=vox)
+        us, mib = measure(lambda: F.smooth_threshold(enhanced, taps, 0.2))
+        rec.update(hip_us=round(us, 1), hip_peak_MiB=round(mib, 1), hip_GBps=round(9 * vox / us / 1e3, 1))
+        us, mib = measure(lambda: (ho.smooth(enhanced, taps) > 0.2))
+        rec.update(torch_us=round(us, 1), torch_peak_MiB=round(mib, 1))
+        print("HESSIAN " + json.dumps(rec), flush=True)
+        values, flags = F.smooth_threshold(enhanced, taps, 0.2)
+        ncand = int(flags.sum())
+        rec = dict(kernel="hessian_enhancement_kpts K=20000", shape=rec["shape"], voxels=vox, candidates=ncand)
+        us, mib = measure(lambda: ke.hessian_enhancement_kpts(enhanced))
+        rec.update(hip_us=round(us, 1), hip_peak_MiB=round(mib, 1))
+        cand = values.reshape(-1)[torch.nonzero(flags.reshape(-1)).squeeze(1)]
+        us, _ = measure(lambda: torch.sort(cand, descending=True, stable=True))
+        rec.update(candidate_sort_us=round(us, 1))
+        us, mib = measure(lambda: torch.topk(ho.smooth(enhanced, taps).flatten(), 20000))
+        rec.update(torch_dense_topk_us=round(us, 1), torch_peak_MiB=round(mib, 1))
+        print("HESSIAN " + json.dumps(rec), flush=True)
