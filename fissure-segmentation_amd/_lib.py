@@ -129,6 +129,8 @@ SIGNATURES = {
     "fsg_mind_eval_kp_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P], _I),
     "fsg_fissure_enhance_f32": ([_P, _P, _I, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P], _I),
     "fsg_smooth_threshold_f32": ([_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _F, _P, _P, _P], _I),
+    "fsg_cpd_estep_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
+    "fsg_cpd_estep_f32": ([_P, _L, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

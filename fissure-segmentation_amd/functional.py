@@ -1942,6 +1942,39 @@ def ssm_decode_affine(w, mean, evec, v=None, s=None, tr=None):
     return _SSMDecodeAffine.apply(w, mean, evec, v, s, tr)
 
 
+# ------------------------------------------------------------------ coherent point drift, E-step (shape_model/point_cloud_registration.py)
+def cpd_estep(X, TY, sigma2, w=0.):
+    """The reductions of CPD's responsibility matrix P (M, N) that the M-steps need, without P (fsg_cpd_estep_f32).
+
+    X (B,N,3) fixed points or one (N,3) cloud shared by the batch, TY (B,M,3) transformed moving points, sigma2 (B) on the
+    device (it is never read on the host), w in [0, 1) the outlier weight -> (P1 (B,M), Pt1 (B,N), PX (B,M,3), Np (B)), fp32.
+    Deterministic, and item b's outputs do not depend on the other items.  An evaluation primitive, not differentiable."""
+    _need_gpu(X, TY, sigma2)
+    if TY.dim() != 3 or TY.shape[2] != 3 or X.dim() not in (2, 3) or X.shape[-1] != 3 or (X.dim() == 3 and X.shape[0] != TY.shape[0]):
+        raise ValueError(f"expected X (B,N,3) or (N,3) and TY (B,M,3), got {tuple(X.shape)} and {tuple(TY.shape)}")
+    B, M, _ = TY.shape
+    N = X.shape[-2]
+    if N < 1 or M < 1:
+        raise ValueError(f"cpd_estep: empty cloud (N={N}, M={M})")
+    if sigma2.numel() != B:
+        raise ValueError(f"expected one sigma2 per item ({B}), got {tuple(sigma2.shape)}")
+    if not 0. <= w < 1.:
+        raise ValueError(f"the outlier weight w must lie in [0, 1), got {w}")
+    with torch.no_grad():
+        xc, yc, sc = _f32c(X), _f32c(TY), _f32c(sigma2).reshape(B)
+        dev = yc.device
+        P1 = torch.empty(B, M, dtype=torch.float32, device=dev)
+        Pt1 = torch.empty(B, N, dtype=torch.float32, device=dev)
+        PX = torch.empty(B, M, 3, dtype=torch.float32, device=dev)
+        Np = torch.empty(B, dtype=torch.float32, device=dev)
+        nbytes = _lib.lib.fsg_cpd_estep_workspace_bytes(B, N, M)
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("fsg_cpd_estep_f32", _p(xc), 3 * N if xc.dim() == 3 else 0, _p(yc), _p(sc), float(w), B, N, M, _p(P1),
+                      _p(Pt1), _p(PX), _p(Np), _p(ws), nbytes, _stream())
+    return P1, Pt1, PX, Np
+
+
 # ------------------------------------------------------------------ segmentation loss (losses/nnu_loss.py:6-19)
 class _NNULoss(torch.autograd.Function):
     @staticmethod

@@ -1,0 +1,289 @@
+"""Coherent point drift (Myronenko & Song, "Point Set Registration: Coherent Point Drift", TPAMI 2010) for the
+corresponding-point shapes that `SSM.fit` consumes -- the registration part of the reference's
+shape_model/point_cloud_registration.py, which calls pycpd on the CPU for one case and one object at a time (:101-116 the
+deformable step with alpha = 0.01 and beta = 10, :231-237 the joint rigid pre-registration, :136-177 the inverse transformation
+sampled at the fixed points).
+
+Here a registration object takes a whole batch: X (N,3) or (B,N,3) fixed, Y (M,3) or (B,M,3) moving.  The E-step -- the dense
+(M, N) responsibilities and their three reductions -- is one fused HIP entry point, fp32 in and out (functional.cpd_estep), that never
+stores the matrix; the M-step's 3 x 3 SVDs and M x M solves are torch.linalg in fp64 (the system's condition number grows like
+M / (alpha sigma^2)).  sigma^2, the per-item `active` flag and the iteration counts stay on the device: an item that has met
+its stopping rule is frozen, and the host looks at one "any active" word every `CHECK_EVERY` iterations.
+
+Defaults and stopping rules are pycpd's: sigma^2 starts at sum |x - y|^2 / (3 N M); the rigid run stops when the objective q
+changes by at most `tolerance`, the deformable run when sigma^2 does; a non-positive sigma^2 becomes tolerance / 10.
+
+NOT reproduced: pycpd clamps tiny E-step denominators to machine epsilon, differently from version to version -- one version
+thereby silently drops a fixed point that lies farther than about 8.5 sigma from every moving point.  The kernel evaluates the
+exponent relative to each fixed point's nearest moving point and so keeps the mathematical value.  pycpd is not a dependency
+of this package, and parity with it is unpinned: the yardstick is the fp64 restatement in tests/cpd_oracle.py.
+
+numpy arrays go in the way the reference passes them and come out as numpy (the work still runs on the current GPU); torch
+tensors must be on a GPU and stay there.  A 2-D Y is a batch of one, returned without the batch axis.  Not reproduced either:
+the thin-plate-spline interpolation mode (out of scope, it raises), the open3d / matplotlib driver `register_all`."""
+import numbers
+
+import numpy as np
+import torch
+
+from .. import functional as F_hip
+
+INTERPOLATION_MODES = ['knn', 'tps']
+CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
+
+
+def _as_tensor(a, name):
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if not isinstance(a, torch.Tensor):
+        raise TypeError(f"{name} must be a numpy array or a torch tensor, got {type(a).__name__}")
+    if a.dim() not in (2, 3) or a.shape[-1] != 3 or a.shape[-2] < 1 or not a.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point (points, 3) or (batch, points, 3) array, got {tuple(a.shape)} {a.dtype}")
+    return a
+
+
+def _det3(m):
+    return (m[:, 0, 0] * (m[:, 1, 1] * m[:, 2, 2] - m[:, 1, 2] * m[:, 2, 1])
+            - m[:, 0, 1] * (m[:, 1, 0] * m[:, 2, 2] - m[:, 1, 2] * m[:, 2, 0])
+            + m[:, 0, 2] * (m[:, 1, 0] * m[:, 2, 1] - m[:, 1, 1] * m[:, 2, 0]))
+
+
+class _Registration:
+    """the EM loop and its on-device bookkeeping; subclasses supply `_prepare` and `_maximization`"""
+
+    def __init__(self, X, Y, max_iterations=100, tolerance=1e-3, w=0., sigma2=None):
+        self._numpy = isinstance(Y, np.ndarray)
+        if isinstance(X, np.ndarray) != self._numpy:
+            raise TypeError("X and Y must both be numpy arrays or both be torch tensors")
+        X, Y = _as_tensor(X, "X"), _as_tensor(Y, "Y")
+        if not self._numpy:
+            F_hip._need_gpu(X, Y)
+            if X.device != Y.device:
+                raise ValueError(f"X is on {X.device}, Y on {Y.device}")
+        self._squeeze = Y.dim() == 2
+        B = 1 if self._squeeze else Y.shape[0]
+        if X.dim() == 3 and X.shape[0] != B:
+            raise ValueError(f"X holds {X.shape[0]} clouds, Y {B}")
+        if isinstance(max_iterations, bool) or not isinstance(max_iterations, numbers.Integral) or max_iterations < 0:
+            raise ValueError(f"max_iterations must be a non-negative integer, got {max_iterations!r}")
+        if not isinstance(tolerance, numbers.Real) or not tolerance >= 0:
+            raise ValueError(f"tolerance must be a non-negative number, got {tolerance!r}")
+        if not isinstance(w, numbers.Real) or not 0 <= w < 1:
+            raise ValueError(f"the outlier weight w must lie in [0, 1), got {w!r}")
+        if sigma2 is not None:
+            s2 = torch.as_tensor(sigma2, dtype=torch.float64).reshape(-1)
+            if s2.numel() not in (1, B) or not bool((s2 > 0).all()):
+                raise ValueError(f"sigma2 must be positive, one value or one per item, got {sigma2!r}")
+        self.X, self.Y = X, Y
+        self.max_iterations, self.tolerance, self.w, self._sigma2_init = int(max_iterations), float(tolerance), float(w), sigma2
+        self.B, self.N, self.M = B, X.shape[-2], Y.shape[-2]
+        self._ready = False
+
+    # ---- state
+    def _setup(self):
+        dev = torch.device("cuda", torch.cuda.current_device()) if self._numpy else self.Y.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        X = self.X.to(**f64)
+        self._X = X if X.dim() == 3 else X[None]                      # (B or 1, N, 3)
+        self._Y = self.Y.to(**f64).reshape(self.B, self.M, 3)
+        self._X32 = self.X.to(dtype=torch.float32, device=dev).contiguous()   # keeps (N,3): the kernel shares one cloud
+        if self._X32.dim() == 3 and self.B == 1:
+            self._X32 = self._X32[0]
+        if self._sigma2_init is None:
+            # sum_nm |x_n - y_m|^2 = M sum |x|^2 + N sum |y|^2 - 2 (sum x).(sum y), in fp64
+            sx, sy = self._X.sum(1), self._Y.sum(1)
+            tot = self.M * self._X.square().sum((1, 2)) + self.N * self._Y.square().sum((1, 2)) - 2 * (sx * sy).sum(1)
+            self._sigma2 = (tot / (3 * self.N * self.M)).expand(self.B).clone()
+        else:
+            self._sigma2 = torch.as_tensor(self._sigma2_init, **f64).reshape(-1).expand(self.B).clone()
+        self._TY = self._Y.clone()
+        self._active = torch.full((self.B,), self.max_iterations > 0, dtype=torch.bool, device=dev)
+        self._iters = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._prepare(dev)
+        self._ready = True
+
+    def _keep(self, new, old):
+        """`new` for the active items, `old` for the frozen ones"""
+        return torch.where(self._active.view(-1, *([1] * (new.dim() - 1))), new, old)
+
+    def _finish_iteration(self, sigma2, diff):
+        floor = torch.full_like(sigma2, self.tolerance / 10)
+        self._sigma2 = self._keep(torch.where(sigma2 > 0, sigma2, floor), self._sigma2)
+        self._iters += self._active
+        self._active = self._active & (diff > self.tolerance)
+
+    def _expectation(self):
+        return [t.double() for t in F_hip.cpd_estep(self._X32, self._TY.float(), self._sigma2.float(), self.w)]
+
+    def register(self):
+        with torch.no_grad():
+            self._setup()   # every call registers from the start
+            for it in range(self.max_iterations):
+                if it and it % CHECK_EVERY == 0 and not bool(self._active.any()):   # the only synchronisation of the loop
+                    break
+                self._maximization(*self._expectation())
+            return self._out(self._TY), self.get_registration_parameters()
+
+    # ---- results
+    def _out(self, t):
+        t = t.to(self.Y.dtype)
+        if self._squeeze:
+            t = t[0]
+        return t.cpu().numpy() if self._numpy else t
+
+    @property
+    def iteration(self):
+        """EM iterations each item ran: an int for a 2-D Y, else (B,)"""
+        if not self._ready:
+            return 0 if self._squeeze else self._out_int(torch.zeros(self.B, dtype=torch.int32))
+        return int(self._iters[0]) if self._squeeze else self._out_int(self._iters.clone())
+
+    def _out_int(self, t):
+        return t.cpu().numpy() if self._numpy else t
+
+    @property
+    def sigma2(self):
+        return self._out(self._sigma2) if self._ready else None
+
+    @property
+    def TY(self):
+        return self._out(self._TY) if self._ready else None
+
+
+class RigidRegistration(_Registration):
+    """Rigid CPD with scaling (Myronenko & Song fig. 2): `register()` -> (TY, (scale, rotation, translation)) with
+    TY = scale * Y @ rotation + translation -- the row-vector convention the reference relies on
+    (point_cloud_registration.py:232-237; it stores rotation.T for the column-vector form)."""
+
+    def _prepare(self, dev):
+        B = self.B
+        self._s = torch.ones(B, dtype=torch.float64, device=dev)
+        self._R = torch.eye(3, dtype=torch.float64, device=dev).expand(B, 3, 3).clone()   # paper's R: T(y) = s R y + t
+        self._t = torch.zeros(B, 3, dtype=torch.float64, device=dev)
+        self._q = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+
+    def _maximization(self, P1, Pt1, PX, Np):
+        X, Y = self._X, self._Y
+        muX = PX.sum(1) / Np[:, None]
+        muY = (P1[:, :, None] * Y).sum(1) / Np[:, None]
+        Xh, Yh = X - muX[:, None], Y - muY[:, None]
+        A = (PX - P1[:, :, None] * muX[:, None]).transpose(1, 2) @ Yh          # X^T P^T Y, centred: (B,3,3)
+        U, _, Vh = torch.linalg.svd(A)
+        C = torch.ones_like(muX)
+        C[:, 2] = _det3(U) * _det3(Vh)
+        R = (U * C[:, None, :]) @ Vh
+        trAR = (A * R).sum((1, 2))                                              # tr(A^T R)
+        yPy = (P1 * Yh.square().sum(2)).sum(1)
+        xPx = (Pt1 * Xh.square().sum(2)).sum(1)
+        s = trAR / yPy
+        t = muX - s[:, None] * (R @ muY[:, :, None]).squeeze(2)
+        TY = s[:, None, None] * (Y @ R.transpose(1, 2)) + t[:, None]
+        q = (xPx - 2 * s * trAR + s * s * yPy) / (2 * self._sigma2) + 1.5 * Np * torch.log(self._sigma2)
+        diff = (q - self._q).abs()
+        self._s, self._R, self._t = self._keep(s, self._s), self._keep(R, self._R), self._keep(t, self._t)
+        self._TY, self._q = self._keep(TY, self._TY), self._keep(q, self._q)
+        self._finish_iteration((xPx - s * trAR) / (3 * Np), diff)
+
+    def get_registration_parameters(self):
+        s, rot, t = self._s, self._R.transpose(1, 2).contiguous(), self._t
+        if self._squeeze and self._numpy:
+            return float(s[0]), self._out(rot), self._out(t)
+        return self._out(s), self._out(rot), self._out(t)
+
+
+class DeformableRegistration(_Registration):
+    """Non-rigid CPD (Myronenko & Song fig. 4): `register()` -> (TY, (G, W)) with TY = Y + G @ W,
+    G[i,j] = exp(-|y_i - y_j|^2 / (2 beta^2)).  `alpha` weighs the smoothness of the displacement field against the point
+    fit, `beta` is the width of the kernel that defines smoothness.  G and the solve are fp64."""
+
+    def __init__(self, X, Y, alpha, beta, max_iterations=100, tolerance=1e-3, w=0., sigma2=None):
+        super().__init__(X, Y, max_iterations=max_iterations, tolerance=tolerance, w=w, sigma2=sigma2)
+        for name, v in (("alpha", alpha), ("beta", beta)):
+            if not isinstance(v, numbers.Real) or not v > 0:
+                raise ValueError(f"{name} must be a positive number, got {v!r}")
+        self.alpha, self.beta = float(alpha), float(beta)
+
+    def _prepare(self, dev):
+        Y = self._Y
+        d = torch.zeros(self.B, self.M, self.M, dtype=torch.float64, device=dev)
+        for c in range(3):   # differences, one coordinate at a time: no (B,M,M,3) intermediate
+            d += (Y[:, :, None, c] - Y[:, None, :, c]).square()
+        self._G = torch.exp(d.mul_(-1 / (2 * self.beta ** 2)))
+        self._W = torch.zeros(self.B, self.M, 3, dtype=torch.float64, device=dev)
+        self._eye = torch.eye(self.M, dtype=torch.float64, device=dev)
+        self._Xsq = self._X.square().sum(2)
+
+    def _maximization(self, P1, Pt1, PX, Np):
+        Y, G = self._Y, self._G
+        A = P1[:, :, None] * G + (self.alpha * self._sigma2)[:, None, None] * self._eye
+        W = torch.linalg.solve_ex(A, PX - P1[:, :, None] * Y)[0]   # no status read-back: the loop stays asynchronous
+        TY = Y + G @ W
+        xPx = (Pt1 * self._Xsq).sum(1)
+        yPy = (P1 * TY.square().sum(2)).sum(1)
+        trPXY = (TY * PX).sum((1, 2))
+        sigma2 = (xPx - 2 * trPXY + yPy) / (3 * Np)
+        floor = torch.full_like(sigma2, self.tolerance / 10)
+        diff = (torch.where(sigma2 > 0, sigma2, floor) - self._sigma2).abs()
+        self._W, self._TY = self._keep(W, self._W), self._keep(TY, self._TY)
+        self._finish_iteration(sigma2, diff)
+
+    def get_registration_parameters(self):
+        return self._out(self._G), self._out(self._W)
+
+    def displacements(self):
+        """G @ W = TY - Y, formed in fp64 before it is cast to the type of Y"""
+        return self._out(self._G @ self._W)
+
+
+def register_cpd_deformable(fixed_pc_np, moving_pc_np_prereg):
+    """point_cloud_registration.py:101-116 (assumes a rigid / affine pre-registration): deformable CPD with alpha = 0.01,
+    beta = 10 -> (deformed cloud, its displacements G @ W).  Batched inputs register every pair at once."""
+    deformable = DeformableRegistration(X=fixed_pc_np, Y=moving_pc_np_prereg, alpha=0.01, beta=10)
+    deformed, _ = deformable.register()
+    return deformed, deformable.displacements()
+
+
+def interpolate_displacements_weighted_knn(existing_points, values_at_existing_points, interpolation_points, k=5):
+    """point_cloud_registration.py:136-148: at every interpolation point, the mean of the values at its k nearest existing
+    points, weighted by 1 / (distance + 1e-8).  existing_points (Ne,3) or (B,Ne,3), values (.., Ne, C), interpolation_points
+    (.., Nq, 3) -> (.., Nq, C) fp32.  The neighbours come from the segment kNN kernel and the weighted mean from the
+    interpolation kernel of the PointTransformer (functional.knn_segment / functional.interpolate); no (Nq, Ne) distance
+    matrix, no dense topk.  GPU tensors in, GPU tensor out (the reference returns a squeezed numpy array)."""
+    e, v, q = existing_points, values_at_existing_points, interpolation_points
+    F_hip._need_gpu(e, v, q)
+    if e.dim() not in (2, 3) or e.dim() != v.dim() or e.dim() != q.dim() or e.shape[-1] != 3 or q.shape[-1] != 3 \
+            or e.shape[:-1] != v.shape[:-1] or e.shape[:-2] != q.shape[:-2]:
+        raise ValueError(f"expected existing (..,Ne,3), values (..,Ne,C) and query (..,Nq,3), got {tuple(e.shape)}, "
+                         f"{tuple(v.shape)} and {tuple(q.shape)}")
+    Ne, Nq, C = e.shape[-2], q.shape[-2], v.shape[-1]
+    if not 1 <= k <= min(8, Ne):
+        raise ValueError(f"k={k}: the interpolation kernel serves 1 <= k <= 8, and k <= {Ne} existing points")
+    B = e.shape[0] if e.dim() == 3 else 1
+    with torch.no_grad():
+        offset = torch.arange(1, B + 1, dtype=torch.int32, device=e.device)
+        idx, d2 = F_hip.knn_segment(k, e.reshape(B * Ne, 3), q.reshape(B * Nq, 3), offset * Ne, offset * Nq)
+        out = F_hip.interpolate(v.reshape(B * Ne, C), idx, d2)
+    return out.view(*q.shape[:-1], C)
+
+
+def inverse_transformation_at_sampled_points(deformed_pc_np, moving_displacements, sample_point_cloud, img_shape=None,
+                                             interpolation_mode='knn'):
+    """point_cloud_registration.py:151-177: the displacements of the moved cloud, interpolated at the sample locations and
+    subtracted from them -> the sample points in the moving cloud's space.  numpy in, numpy out (as the reference); GPU
+    tensors in, GPU tensor out.  Only the 'knn' interpolation is part of this package."""
+    if interpolation_mode == 'tps':
+        raise NotImplementedError("inverse_transformation_at_sampled_points(interpolation_mode='tps'): the thin-plate-spline "
+                                  "interpolation of the reference is out of scope of this package; use 'knn'")
+    if interpolation_mode != 'knn':
+        raise ValueError(f"interpolation_mode must be one of {INTERPOLATION_MODES}, got {interpolation_mode!r}")
+    as_numpy = isinstance(sample_point_cloud, np.ndarray)
+    if as_numpy:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        deformed, disp, sample = (torch.from_numpy(np.asarray(a)).to(device=dev, dtype=torch.float32)
+                                  for a in (deformed_pc_np, moving_displacements, sample_point_cloud))
+    else:
+        deformed, disp, sample = deformed_pc_np, moving_displacements, sample_point_cloud
+    interpolated = interpolate_displacements_weighted_knn(deformed, disp, sample)
+    if as_numpy:
+        return sample_point_cloud - interpolated.cpu().numpy().astype(sample_point_cloud.dtype)
+    return sample - interpolated.to(sample.dtype)

@@ -1,4 +1,5 @@
 """Drop-in for the kNN part of the reference's utils/general_utils.py (:43-53, :315-327)."""
+import numpy as np
 import torch
 
 from .. import functional as F_hip
@@ -53,6 +54,16 @@ def farthest_point_sampling(kpts, num_points, start=None):
     new_offset = torch.tensor([num_points], dtype=torch.int32, device=kpts.device)
     ind = (F_hip.fps(pts, offset, new_offset, num_points).long() + start) % N
     return kpts[:, ind, :], ind
+
+
+def inverse_affine_transform(point_cloud, scaling, rotation_mat, affine_translation):
+    """Same contract as utils/general_utils.py:299-312: undo p = scaling * rotation_mat @ x + affine_translation for every row
+    of point_cloud (N, 3), numpy or torch (any device) -> (N, 3).  With the parameters the reference stores for a rigid
+    pre-registration -- scale, rotation.T and translation of RigidRegistration (point_cloud_registration.py:236-237) -- this
+    takes registered points back to the moving cloud's space."""
+    centred = (point_cloud - affine_translation) / scaling          # rows: rotation_mat @ x
+    linalg = torch.linalg if isinstance(centred, torch.Tensor) else np.linalg
+    return linalg.solve(rotation_mat, centred.T).T                  # one 3 x 3 solve for all rows, no explicit inverse
 
 
 # ------------------------------------------------------------------ voxel <-> grid coordinates, patches (plain torch, any device)

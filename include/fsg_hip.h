@@ -863,6 +863,23 @@ int fsg_fissure_enhance_f32(const float *img, const uint8_t *mask, int B, int D,
 int fsg_smooth_threshold_f32(const float *vol, int B, int D, int H, int W, const float *wz, int Nz, const float *wy, int Ny,
                              const float *wx, int Nx, float thresh, float *out, uint8_t *flags, fsg_stream_t stream);
 
+/* Coherent point drift, E-step without the (M, N) responsibility matrix (csrc/cpd.hip).  Serves the pycpd registrations of the
+ * reference, shape_model/point_cloud_registration.py:101-116,231-232 (register_cpd_deformable and the joint rigid
+ * pre-registration), whose expectation step is dense numpy on the CPU, one case at a time.
+ *   X (N, 3) fixed points of item b at X + b * x_batch_stride floats (0: one cloud shared by the batch); TY (B, M, 3) the
+ *   transformed moving points; sigma2 (B) DEVICE, > 0; w in [0, 1) the outlier weight.  All fp32, contiguous rows.
+ *   P[m,n] = exp(-|x_n - ty_m|^2 / 2 sigma2) / (sum_m' exp(-|x_n - ty_m'|^2 / 2 sigma2) + c),
+ *   c = (2 pi sigma2)^(3/2) * w / (1 - w) * M / N, evaluated relative to every column's smallest distance (no underflow of a
+ *   column sum; where the rescaled c overflows, the column is 0).  Distances are sums of squared differences.
+ *   P1 (B, M) = sum_n P, Pt1 (B, N) = sum_m P, PX (B, M, 3) = sum_n P x_n, Np (B) = sum_mn P (added up over Pt1).
+ * Two launches, no atomics: the same inputs give the same bits, and an item's outputs do not depend on the rest of the batch.
+ * The exponentials are fp32; distances, exponents and sums are carried in fp64.  Any N, M >= 1.  workspace:
+ * fsg_cpd_estep_workspace_bytes(B, N, M) bytes (16 N per item), 8-byte aligned. */
+size_t fsg_cpd_estep_workspace_bytes(int B, int N, int M);
+int fsg_cpd_estep_f32(const float *X, int64_t x_batch_stride, const float *TY, const float *sigma2, float w, int B, int N, int M,
+                      float *P1, float *Pt1, float *PX, float *Np, void *workspace, size_t workspace_bytes,
+                      fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

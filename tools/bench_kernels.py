@@ -243,3 +243,58 @@ if "hessian" in which:
         us, mib = measure(lambda: torch.topk(ho.smooth(enhanced, taps).flatten(), 20000))
         rec.update(torch_dense_topk_us=round(us, 1), torch_peak_MiB=round(mib, 1))
         print("HESSIAN " + json.dumps(rec), flush=True)
+if "cpd" in which:
+    # CPD's E-step (csrc/cpd.hip) beside the torch composition of the same math on the same device (the oracle's fp32 formula,
+    # batched: it materialises (B, M, N) tensors), with the peak extra device memory of both; then a whole 100-iteration
+    # deformable registration at B = 32 and the share of it spent in the M x M solves (timed on their own, same matrices).
+    import json
+    import cpd_oracle as co
+    from fissure_segmentation_amd.shape_model.point_cloud_registration import DeformableRegistration
+
+    def measure(fn, iters=20, warm=3):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        med, _ = timeit(fn, iters, warm)
+        return round(med, 1), round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    def torch_estep(X, TY, s2):
+        K = torch.exp(-(X[:, None, :, :] - TY[:, :, None, :]).square().sum(3) / (2 * s2[:, None, None]))
+        P = K / K.sum(1, keepdim=True)
+        P1 = P.sum(2)
+        return P1, P.sum(1), P @ X, P1.sum(1)
+
+    def clouds(B, N, M):
+        ps = [co.sheet_pair(N=N, M=M, seed=s) for s in range(B)]
+        return torch.stack([p[0] for p in ps]).float().to(dev), torch.stack([p[1] for p in ps]).float().to(dev)
+
+    for (B, N, M) in [(1, 1024, 1024), (32, 1024, 1024), (1, 3072, 3072)]:
+        X, TY = clouds(B, N, M)
+        s2 = torch.full((B,), 25., device=dev)
+        rec = dict(kernel="cpd_estep sigma2=25 w=0", B=B, N=N, M=M, pairs=B * N * M)
+        rec["hip_us"], rec["hip_peak_MiB"] = measure(lambda: F.cpd_estep(X, TY, s2))
+        rec["torch_us"], rec["torch_peak_MiB"] = measure(lambda: torch_estep(X, TY, s2), iters=10, warm=2)
+        # pair visits: the column launch sweeps every pair twice (minimum, then sum), the row launch once
+        rec["hip_Gvisit_per_s"] = round(3 * B * N * M / rec["hip_us"] / 1e3, 1)
+        print("CPD " + json.dumps(rec), flush=True)
+    B, N, M, ITERATIONS, ALPHA = 32, 1024, 1024, 100, 0.01
+    X, Y = clouds(B, N, M)
+    reg = DeformableRegistration(X, Y, alpha=ALPHA, beta=10., max_iterations=ITERATIONS, tolerance=0)
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    reg.register()
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    TY, (G, _) = reg.register()
+    torch.cuda.synchronize()
+    whole = time.perf_counter() - t1
+    # one solve on its own, on the system of the last iteration: diag(P1) G + alpha sigma2 I, fp64
+    sigma2 = reg.sigma2
+    P1 = F.cpd_estep(X, TY, sigma2)[0].double()
+    A = P1[:, :, None] * G.double() + (ALPHA * sigma2.double())[:, None, None] * torch.eye(M, dtype=torch.float64, device=dev)
+    rhs = torch.randn(B, M, 3, dtype=torch.float64, device=dev)
+    solve_us, _ = timeit(lambda: torch.linalg.solve_ex(A, rhs), iters=10, warm=2)
+    print("CPD " + json.dumps(dict(kernel=f"deformable registration, {ITERATIONS} iterations", B=B, N=N, M=M,
+                                   first_run_s=round(t1 - t0, 3), run_s=round(whole, 3), iterations=reg.iteration.tolist()[:4],
+                                   solve_us_each=round(solve_us, 1),
+                                   solves_fraction_of_run=round(ITERATIONS * solve_us * 1e-6 / whole, 3))), flush=True)
