@@ -4,18 +4,11 @@
 // backward = 4 reads + 1 write; lanes run along channels (C % 64 == 0) so every access is a 256-byte row segment.
 // Statistics: per-workgroup shifted sums -> (n, mean, M2) records merged with Chan's formula in fp64
 // (bn_merge_finalize_kernel of edgeconv.hip), i.e. no E[x^2]-E[x]^2 cancellation (MIOpen's BN loses ~1e-2 there).
-#include "fsg_common.h"
-
-int fsg_ec_finalize_launch(const float *partials, int R, int Co, float eps, float momentum, float *mean, float *invstd,
-                           float *running_mean, float *running_var, hipStream_t st);                 // edgeconv.hip
-size_t fsg_ec_finalize_stage_floats(int Co);
-int fsg_ec_sum_launch(const float *partials, int R, int L, int nvec, float *out0, float *out1, hipStream_t st);
+#include "edgeconv_internal.h"
 
 namespace {
 
 constexpr int ROWS = 128;  // rows per workgroup in the reduction kernels
-
-__device__ __forceinline__ float lrelu(float u, float slope) { return u > 0.f ? u : u * slope; }
 
 __global__ __launch_bounds__(256) void bnact_stats_kernel(const float *__restrict__ y, long M, int C,
                                                            float *__restrict__ partials) {

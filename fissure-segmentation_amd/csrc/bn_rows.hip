@@ -12,12 +12,6 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 constexpr int GMAX = 256;
 
 __global__ void bnr_stats_kernel(const float *__restrict__ x, long M, int C, double *__restrict__ rec) {
@@ -51,8 +45,8 @@ __global__ __launch_bounds__(256) void bnr_finalize_kernel(const double *__restr
         S += rec[(long)r * 2 * C + l];
         SS += rec[(long)r * 2 * C + C + l];
     }
-    S = wave_sum_d(S);
-    SS = wave_sum_d(SS);
+    S = wave_sum_lane0(S);
+    SS = wave_sum_lane0(SS);
     if (lane != 0) return;
     const double m = S / M;
     double var = SS / M - m * m;
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(256) void bnr_fold_kernel(const double *__restrict_
     if (l >= 2 * C) return;
     double S = 0;
     for (int r = lane; r < R; r += 64) S += rec[(long)r * 2 * C + l];
-    S = wave_sum_d(S);
+    S = wave_sum_lane0(S);
     if (lane == 0) (l < C ? dgamma[l] : dbeta[l - C]) = (float)S;
 }
 

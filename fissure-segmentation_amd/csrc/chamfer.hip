@@ -6,14 +6,9 @@
 // eight waves of a workgroup split between them.  d = fma(dz,dz, fma(dy,dy, dx*dx)) -- bit-exact with
 // oracle/fsg_oracle.c.  (First version: one lane per query, 128-thread workgroups = 2 waves per CU at 8 x 4096 points:
 // 122 us; the backward used atomicAdd = CAS loops: 123 us.)
-#include "fsg_common.h"
+#include "edgeconv_internal.h"
 
 namespace {
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
 
 constexpr int WAVES = 8;             // 512 threads
 constexpr int QW = 128;              // queries per workgroup: two per lane
@@ -164,9 +159,6 @@ __global__ __launch_bounds__(256) void chamfer_bwd_y_kernel(const float *__restr
 }
 
 }  // namespace
-
-int fsg_csr_bipartite_launch(const int32_t *idx, int B, int NS, int N, int k, int32_t *rowptr, int32_t *col, int32_t *cnt,
-                             int32_t *tmp, hipStream_t st);   // edgeconv.hip
 
 extern "C" size_t fsg_chamfer_nn_bwd_workspace_bytes(int B, int N, int M) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;

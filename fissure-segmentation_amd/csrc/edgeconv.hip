@@ -24,19 +24,14 @@
 // cloud's P rows.
 #include <type_traits>
 
+#include "edgeconv_internal.h"
 #include "knn_internal.h"
-
-size_t fsg_ec_finalize_stage_floats(int Co);
-int fsg_ec_finalize_launch(const float *partials, int R, int Co, float eps, float momentum, float *mean, float *invstd,
-                           float *running_mean, float *running_var, hipStream_t st);
 
 namespace {
 
 constexpr int TP = 16;  // points per tile in the gather kernels (4 waves x 4 points)
 constexpr int FSG_CSR_SPLIT = 16;  // workgroups per cloud of the multi-workgroup reverse-graph build
 constexpr int TPW = 2;  // tiles per workgroup of the statistics kernel: 8 waves, one BN partial record per workgroup
-
-__device__ __forceinline__ float lrelu(float u, float slope) { return u > 0.f ? u : u * slope; }
 
 // ------------------------------------------------------------------ reverse graph
 __global__ __launch_bounds__(1024) void csr_build_kernel(const int32_t *__restrict__ idx, int N, int k,
@@ -283,9 +278,9 @@ __global__ __launch_bounds__(512) void ec1_stats_select_kernel(const float *__re
                                                                 int training, float *__restrict__ ysel,
                                                                 uint8_t *__restrict__ arg, float *__restrict__ ssum,
                                                                 float *__restrict__ partials) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    typedef f32x2 f2;
+    typedef f32x4 f4;
+    typedef u32x4 u4;
     constexpr int NW = 4 * TPW;                        // waves
     __shared__ float red[2][4 * NW][64];               // (mean, M2) of every 16-lane group (= point) of the workgroup
     const int b = blockIdx.x, tile = blockIdx.y, cg = blockIdx.z;
@@ -293,8 +288,7 @@ __global__ __launch_bounds__(512) void ec1_stats_select_kernel(const float *__re
     const int g = lane >> 4, c16 = lane & 15;
     const int c0 = cg * 64 + 4 * c16;                 // first of this lane's four channels
     const int ld = 2 * Co;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(pq + (long)b * N * ld), 0, __builtin_amdgcn_readfirstlane((int)((long)N * ld * 4)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(pq + (long)b * N * ld, __builtin_amdgcn_readfirstlane((int)((long)N * ld * 4)));
     f2 sgn[2] = {{1.f, 1.f}, {1.f, 1.f}};
     if (SELECT) {
         const f4 gm = *reinterpret_cast<const f4 *>(gamma + c0);
@@ -535,15 +529,13 @@ __global__ __launch_bounds__(256) void ec1_apply_kernel(const float *__restrict_
 // the 64 points whose activations it holds in LDS -- the product that used to be a vendor-library GEMM launch (7.3 us + a launch
 // boundary per layer) rides here as 64 x 128 x 64 on v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fma chain per output,
 // reproducible): wave w owns output columns 32 w .. 32 w + 31 for both 32-point halves, the weight is staged transposed in LDS.
-typedef unsigned ec_u32x4 __attribute__((ext_vector_type(4)));
-typedef float ec_f32x16 __attribute__((ext_vector_type(16)));
 template <bool PQ>
 __global__ __launch_bounds__(256) void ec1_apply_prep_kernel(const float *__restrict__ ysel, const float *__restrict__ gamma,
                                                               const float *__restrict__ beta, const float *__restrict__ mean,
                                                               const float *__restrict__ invstd, int N, float slope,
                                                               float *__restrict__ out, float *__restrict__ out_pm,
                                                               float *__restrict__ xx, float *__restrict__ xs,
-                                                              ec_u32x4 *__restrict__ cand, float *__restrict__ cscale,
+                                                              u32x4 *__restrict__ cand, float *__restrict__ cscale,
                                                               const float *__restrict__ w_next, float *__restrict__ pq_next) {
     constexpr int Co = 64, KS = 4, CN = 128;
     __shared__ float tile[64][65];
@@ -553,7 +545,7 @@ __global__ __launch_bounds__(256) void ec1_apply_prep_kernel(const float *__rest
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane;
     if (PQ) {     // (requested first: the weight is not on this kernel's dependency chain)
-        typedef float f4 __attribute__((ext_vector_type(4)));
+        typedef f32x4 f4;
 #pragma unroll
         for (int e = threadIdx.x; e < CN * 16; e += 256) {
             const int n = e >> 4, k4 = 4 * (e & 15);
@@ -598,7 +590,7 @@ __global__ __launch_bounds__(256) void ec1_apply_prep_kernel(const float *__rest
         // pq_next tile: rows = the 64 points, columns 32 wave .. 32 wave + 31; A = tile (lane m = point, k half = lane / 32),
         // B = wt (lane n = column); D: lane (n, h) holds rows 8 (e / 4) + 4 h + e % 4
         const int mn = lane & 31, kk = lane >> 5;
-        ec_f32x16 acc0, acc1;
+        f32x16 acc0, acc1;
 #pragma unroll
         for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
 #pragma unroll 8
@@ -654,7 +646,7 @@ __global__ __launch_bounds__(256) void ec1_apply_prep_kernel(const float *__rest
             cw[i] = (unsigned)__builtin_bit_cast(unsigned short, hv);
         }
         cand[(((long)b * T + (i0 / 32 + half_tile)) * KS + s2) * 64 + ln] =
-            ec_u32x4{cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16), cw[4] | (cw[5] << 16), cw[6] | (cw[7] << 16)};
+            u32x4{cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16), cw[4] | (cw[5] << 16), cw[6] | (cw[7] << 16)};
     }
 }
 
@@ -774,8 +766,8 @@ __global__ __launch_bounds__(256) void ec1_bwd_gather_kernel(
     const float *__restrict__ gamma, const float *__restrict__ mean, const float *__restrict__ invstd,
     const float *__restrict__ dbeta, const float *__restrict__ dgamma, int N, int k, int Co, int training, float invM,
     float *__restrict__ grad_pq) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef f32x2 f2;
+    typedef f32x4 f4;
     __shared__ float comb[4][2][4][64];        // [wave][ah | aq][group][channel]
     const int b = blockIdx.x, cg = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -849,7 +841,7 @@ __global__ __launch_bounds__(256) void ec1_bwd_gather_kernel(
 
 }  // namespace
 
-// launch helpers shared with edgeconv2.hip
+// launch helpers shared with edgeconv2.hip, bn_act.hip and chamfer.hip: edgeconv_internal.h
 int fsg_ec_stats1_records(int B, int N) { return B * fsg_cdiv(N, TP * TPW); }
 
 int fsg_ec_stats1_launch(const float *pq, const int32_t *idx, const float *gamma, int B, int N, int k, int Co,
@@ -887,10 +879,10 @@ int fsg_ec_apply_prep_launch(const float *ysel, const float *gamma, const float 
     }
     if (w_next)
         hipLaunchKernelGGL(ec1_apply_prep_kernel<true>, dim3(B, N / 64), dim3(256), 0, st, ysel, gamma, beta, mean, invstd, N,
-                           slope, out, out_pm, xx, xs, reinterpret_cast<ec_u32x4 *>(cand), cscale, w_next, pq_next);
+                           slope, out, out_pm, xx, xs, reinterpret_cast<u32x4 *>(cand), cscale, w_next, pq_next);
     else
         hipLaunchKernelGGL(ec1_apply_prep_kernel<false>, dim3(B, N / 64), dim3(256), 0, st, ysel, gamma, beta, mean, invstd, N,
-                           slope, out, out_pm, xx, xs, reinterpret_cast<ec_u32x4 *>(cand), cscale, nullptr, nullptr);
+                           slope, out, out_pm, xx, xs, reinterpret_cast<u32x4 *>(cand), cscale, nullptr, nullptr);
     FSG_CHECK_LAUNCH("fsg_edgeconv_apply_f32/prep");
     return FSG_OK;
 }
@@ -963,11 +955,7 @@ extern "C" int fsg_graph_reverse_csr(const int32_t *idx, int B, int N, int k, in
         if (rc != FSG_ERR_UNSUPPORTED) return rc;
     }
     const size_t lds = sizeof(int) * ((size_t)N + 1024);
-    static FsgLdsGrant grant;
-    if (!grant.raise((const void *)csr_build_kernel, lds)) {
-        fsg_set_error("fsg_graph_reverse_csr: cannot raise dynamic LDS to %zu", lds);
-        return FSG_ERR_HIP;
-    }
+    FSG_GRANT_LDS("fsg_graph_reverse_csr", csr_build_kernel, lds);
     hipLaunchKernelGGL(csr_build_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, idx, N, k, rowptr, col);
     FSG_CHECK_LAUNCH("fsg_graph_reverse_csr");
     hipLaunchKernelGGL(csr_sort_rows_kernel, dim3(fsg_cdiv(N, 4), B), dim3(256), 0, (hipStream_t)stream, rowptr, col, N, N * k,

@@ -18,12 +18,9 @@
 // reverse-graph gather over du1 (no float atomics anywhere).
 #include <stdlib.h>
 
-#include "fsg_common.h"
+#include "edgeconv_internal.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // bf16 operand mode (fsg_edgeconv2_{fwd,bwd}_bf16): the per-edge products run on v_mfma_f32_32x32x16_bf16 -- operands
 // rounded to bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32) on their way out of LDS, fp32 accumulation, everything else
@@ -39,8 +36,6 @@ __device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
 constexpr int C1 = 64;          // width of the first layer (all reference configurations)
 constexpr int LD1 = C1 + 1;     // padded LDS row: column reads by 32 lanes hit 32 banks
 constexpr int MAXPAIR = 3;      // output tiles per wave
-
-__device__ __forceinline__ float lrelu(float u, float slope) { return u > 0.f ? u : u * slope; }
 
 struct Tile {
     int TP, R, Rpad;
@@ -490,8 +485,8 @@ __global__ __launch_bounds__(256) void ec2_bwd_gather_kernel(
     const float *__restrict__ du1, const float *__restrict__ ssum1, const float *__restrict__ gamma1,
     const float *__restrict__ mean1, const float *__restrict__ invstd1, const float *__restrict__ dbeta1,
     const float *__restrict__ dgamma1, int N, int k, int training, float invM, float *__restrict__ grad_pq) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef f32x2 f2;
+    typedef f32x4 f4;
     __shared__ float comb[4][3][4][C1];          // [wave][ad | aq | own][group][channel]
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: keep it scalar
@@ -588,43 +583,6 @@ __global__ __launch_bounds__(256) void ec2_bwd_gather_kernel(
 //     bank conflicts;
 //   * the weights are loop invariants of a wave (it keeps its column tile): their fragments stay in registers;
 //   * the gathers of tile t + 1 (and the neighbour indices of tile t + 2) are in flight while tile t is computed.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {   // (a, b) -> packed bf16 pair, a in the low half, RNE
-    bf16x2 v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-
-// two fp32 values -> their three bf16 pieces, packed pairwise
-__device__ __forceinline__ void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    h = pk_bf16(a, b);
-    const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-    m = pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(m << 16), sb = rb - __uint_as_float(m & 0xffff0000u);
-    l = pk_bf16(sa, sb);
-}
-
-template <int NP>
-__device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&p)[NP]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if constexpr (NP == 3) {
-            unsigned h, m, l;
-            split2(x[2 * q], x[2 * q + 1], h, m, l);
-            p[0][q] = h;
-            p[1][q] = m;
-            p[2][q] = l;
-        } else {
-            p[0][q] = pk_bf16(x[2 * q], x[2 * q + 1]);
-        }
-    }
-}
-
 // byte offset of the 16-byte chunk c (eight channels) of row `row` in a [rows][64 x bf16] dual-use image.  Bank row = 256
 // bytes = two image rows.  Row reads: the 16-lane groups of ds_read_b128 ({0-3,12-15,20-27}, ...) take one chunk index of 16
 // rows -- 8 even, 8 odd; the XOR value 4 ((row >> 1) & 1) + ((row >> 2) & 3) is distinct over the 8 rows of either parity.
@@ -632,21 +590,6 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&p)[NP]) {
 // bank row, rows r + 2, r + 3 the other chunk quad (XOR bit 2).
 __device__ __forceinline__ int img_off(int row, int c) {
     return 128 * row + 16 * (c ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3)));
-}
-
-template <int NP>
-__device__ __forceinline__ f32x16 mfma_split(const u32x4 (&a)[NP], const u32x4 (&b)[NP], f32x16 c) {
-    const bf16x8 ah = __builtin_bit_cast(bf16x8, a[0]), bh = __builtin_bit_cast(bf16x8, b[0]);
-    if constexpr (NP == 3) {
-        const bf16x8 am = __builtin_bit_cast(bf16x8, a[1]), al = __builtin_bit_cast(bf16x8, a[2]);
-        const bf16x8 bm = __builtin_bit_cast(bf16x8, b[1]), bl = __builtin_bit_cast(bf16x8, b[2]);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, c, 0, 0, 0);
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
 }
 
 // operand fragment for a contraction over CHANNELS: lane (ql, half) takes channels 16 ks + 8 half .. + 7 of row rt * 32 + ql
@@ -676,22 +619,6 @@ __device__ __forceinline__ void tr_frag(const unsigned char *img, int piece_byte
         f[pc] = u32x4{a[0], a[1], b[0], b[1]};
     }
 }
-
-// 16-byte gathers with a per-lane byte offset into the [P | Q] rows of a cloud; !ok -> an offset outside the resource (0)
-struct ChunkGather {
-    __amdgpu_buffer_rsrc_t rs;
-    unsigned oob;
-    __device__ __forceinline__ ChunkGather(const float *base, long bytes) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(base);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        const int n = __builtin_amdgcn_readfirstlane((int)bytes);
-        rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0, n, 0x00020000);
-        oob = (unsigned)n;
-    }
-    __device__ __forceinline__ float4 load(bool ok, unsigned byte_off) const {
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? byte_off : oob, 0, 0));
-    }
-};
 
 // the gather state of one tile: RT items per thread, item `it` = (row irow + 32 it, chunk) of the tile
 template <int RT>
@@ -1119,8 +1046,8 @@ __global__ __launch_bounds__(256, (NP == 3 && RT == 4) ? 1 : 2) void ec2s_bwd_ke
                 for (int j = 0; j < 4; ++j) dy[j] = valid ? dy[j] : 0.f;
                 unsigned hh[2], mm[2] = {0u, 0u}, ll[2] = {0u, 0u};
                 if constexpr (NP == 3) {
-                    split2(dy[0], dy[1], hh[0], mm[0], ll[0]);
-                    split2(dy[2], dy[3], hh[1], mm[1], ll[1]);
+                    bf16_split3(dy[0], dy[1], hh[0], mm[0], ll[0]);
+                    bf16_split3(dy[2], dy[3], hh[1], mm[1], ll[1]);
                 } else {
                     hh[0] = pk_bf16(dy[0], dy[1]);
                     hh[1] = pk_bf16(dy[2], dy[3]);
@@ -1212,16 +1139,6 @@ __global__ __launch_bounds__(256, (NP == 3 && RT == 4) ? 1 : 2) void ec2s_bwd_ke
 }
 
 }  // namespace
-
-// shared with edgeconv.hip
-int fsg_ec_stats1_launch(const float *pq, const int32_t *idx, const float *gamma, int B, int N, int k, int Co,
-                         float *ysel, uint8_t *arg, float *ssum, float *partials, hipStream_t st);
-int fsg_ec_finalize_launch(const float *partials, int R, int Co, float eps, float momentum, float *mean, float *invstd,
-                           float *running_mean, float *running_var, hipStream_t st);
-int fsg_ec_apply_launch(const float *ysel, const float *gamma, const float *beta, const float *mean, const float *invstd,
-                        int B, int N, int Co, float slope, float *out, float *out_pm, hipStream_t st);
-int fsg_ec_stats1_records(int B, int N);
-size_t fsg_ec_finalize_stage_floats(int Co);
 
 static int ec2_env_int(const char *name) {
     const char *e = getenv(name);
@@ -1340,21 +1257,13 @@ static int ec2_fwd_impl(bool bf16, const float *pq, const int32_t *idx, const fl
     const size_t lds = sizeof(float) * ((size_t)C2 * LD1 + (size_t)Rpad * (C2 + 1) + 3 * 4 * C2);
 #define FSG_EC2_FWD(CC, BFX)                                                                                             \
     do {                                                                                                                 \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)ec2_fwd_kernel<CC, BFX>, 160 * 1024 - 512)) {                                  \
-            fsg_set_error("fsg_edgeconv2_fwd: cannot raise dynamic LDS");                                             \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
+        FSG_GRANT_LDS("fsg_edgeconv2_fwd", (ec2_fwd_kernel<CC, BFX>), FSG_LDS_WHOLE_CU);                             \
         hipLaunchKernelGGL((ec2_fwd_kernel<CC, BFX>), dim3(B, G), dim3(256), lds, st, pq, idx, w2, gamma1, beta1, mean1,    \
                            invstd1, gamma2, N, k, TP, Rpad, training, slope, ysel2, arg2, ssum2, part2);                 \
     } while (0)
 #define FSG_EC2S_FWD(NPX, RTX)                                                                                            \
     do {                                                                                                                 \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)ec2s_fwd_kernel<NPX, RTX>, 160 * 1024 - 512)) {                                \
-            fsg_set_error("fsg_edgeconv2_fwd: cannot raise dynamic LDS");                                             \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
+        FSG_GRANT_LDS("fsg_edgeconv2_fwd", (ec2s_fwd_kernel<NPX, RTX>), FSG_LDS_WHOLE_CU);                           \
         hipLaunchKernelGGL((ec2s_fwd_kernel<NPX, RTX>), dim3(B, G), dim3(256), ec2s_fwd_lds(NPX, RTX, TPs), st, pq, idx, w2,    \
                            gamma1, beta1, mean1, invstd1, gamma2, N, k, TPs, training, slope, ysel2, arg2, ssum2, part2); \
     } while (0)
@@ -1397,12 +1306,6 @@ extern "C" int fsg_edgeconv2_fwd_bf16(const float *pq, const int32_t *idx, const
                                      void *workspace, fsg_stream_t stream) {
     return ec2_fwd_impl(true, pq, idx, w2, gamma1, beta1, running_mean1, running_var1, gamma2, beta2, running_mean2, running_var2, B, N, k, C2, training, momentum1, momentum2, eps1, eps2, slope, out, out_pm, ssum1, mean1, invstd1, ysel2, arg2, ssum2, mean2, invstd2, workspace, stream);
 }
-
-int fsg_ec_bwd_point_launch(const float *gout, const float *gout_pm, long ld_pm, const float *gout_pm2, long ld_pm2,
-                            const float *ysel, const float *gamma,
-                            const float *beta, const float *mean, const float *invstd, int B, int N, int Co, float slope,
-                            float *h, float *partials, float *dbeta, float *dgamma, hipStream_t st);
-int fsg_ec_sum_launch(const float *partials, int R, int L, int nvec, float *out0, float *out1, hipStream_t st);
 
 static void ec2_bwd_tiling(int k, int C2, int &TP, int &Rpad, int &G, int B, int N) {
     // 64 edge rows per tile: two row tiles x two column tiles = one MFMA pair per wave in every phase (balanced), and
@@ -1477,29 +1380,21 @@ static int ec2_bwd_impl(bool bf16, const float *grad_out, const float *grad_out_
                                         2 * C1 + 2 * C1) + (size_t)TP * C2 + 2 * (size_t)Rpad + 16;
 #define FSG_EC2_BWD(CC, BFX)                                                                                                \
     do {                                                                                                                 \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)ec2_bwd_kernel<CC, BFX>, 160 * 1024 - 512)) {                                  \
-            fsg_set_error("fsg_edgeconv2_bwd_f32: cannot raise dynamic LDS");                                         \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
+        FSG_GRANT_LDS("fsg_edgeconv2_bwd_f32", (ec2_bwd_kernel<CC, BFX>), FSG_LDS_WHOLE_CU);                         \
         hipLaunchKernelGGL((ec2_bwd_kernel<CC, BFX>), dim3(B, G), dim3(256), lds, st, pq, idx, w2, gamma1, beta1, mean1, invstd1, \
                            gamma2, mean2, invstd2, grad_beta2, grad_gamma2, h2, arg2, N, k, TP, Rpad, training, invM,    \
                            slope, du1, dw_part, p1_part);                                                                \
     } while (0)
 #define FSG_EC2S_BWD(NPX, RTX)                                                                                            \
     do {                                                                                                                 \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)ec2s_bwd_kernel<NPX, RTX>, 160 * 1024 - 512)) {                                \
-            fsg_set_error("fsg_edgeconv2_bwd_f32: cannot raise dynamic LDS");                                         \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
+        FSG_GRANT_LDS("fsg_edgeconv2_bwd_f32", (ec2s_bwd_kernel<NPX, RTX>), FSG_LDS_WHOLE_CU);                       \
         hipLaunchKernelGGL((ec2s_bwd_kernel<NPX, RTX>), dim3(B, G), dim3(256), ec2s_bwd_lds(NPX, RTX, TPs), st, pq, idx,   \
                            w2, gamma1, beta1, mean1, invstd1, gamma2, mean2, invstd2, grad_beta2, grad_gamma2, h2, arg2, \
                            N, k, TPs, training, invM, slope, du1, dw_part, p1_part);                                     \
     } while (0)
     if (ec2_split(C2)) {
         G = Gs;
-        FSG_REQUIRE(ec2s_bwd_lds(bf16 ? 1 : 3, RTs, TPs) <= 160 * 1024 - 512, "fsg_edgeconv2_bwd: k=%d needs too much LDS", k);
+        FSG_REQUIRE(ec2s_bwd_lds(bf16 ? 1 : 3, RTs, TPs) <= FSG_LDS_WHOLE_CU, "fsg_edgeconv2_bwd: k=%d needs too much LDS", k);
         if (bf16) { if (RTs == 4) FSG_EC2S_BWD(1, 4); else FSG_EC2S_BWD(1, 2); }
         else { if (RTs == 4) FSG_EC2S_BWD(3, 4); else FSG_EC2S_BWD(3, 2); }
     } else if (C2 == 64) { if (bf16) FSG_EC2_BWD(64, true); else FSG_EC2_BWD(64, false); }

@@ -53,7 +53,6 @@ struct SmoothArgs {
     float thresh;
 };
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __device__ __forceinline__ void fill_tile(float *src, const float *vol, int z0, int y0, int x0, int Rz, int Ry, int Rx, int D,
                                           int H, int W) {
@@ -246,8 +245,7 @@ extern "C" int fsg_fissure_enhance_f32(const float *img, const uint8_t *mask, in
     a.denom = 2.f * sigma_hu * sigma_hu;
     FSG_REQUIRE(img && out, "%s: NULL pointer", name);
     const size_t bytes = tile_bytes(R, R, R);
-    static FsgLdsGrant grant;
-    FSG_REQUIRE(bytes <= LDS_MAX && grant.raise(reinterpret_cast<const void *>(enhance_kernel), bytes),
+    FSG_REQUIRE(bytes <= LDS_MAX && FSG_LDS_GRANTED(enhance_kernel, bytes),
                 "%s: %zu bytes of LDS refused", name, bytes);
     enhance_kernel<<<grid, dim3(NT), bytes, (hipStream_t)stream>>>(a, img, mask, out, planeness, hu_weight);
     FSG_CHECK_LAUNCH(name);
@@ -273,8 +271,7 @@ extern "C" int fsg_smooth_threshold_f32(const float *vol, int B, int D, int H, i
     }
     FSG_REQUIRE(vol && (out || flags), "%s: NULL pointer", name);
     const size_t bytes = tile_bytes(a.R[0], a.R[1], a.R[2]);
-    static FsgLdsGrant grant;
-    FSG_REQUIRE(bytes <= LDS_MAX && grant.raise(reinterpret_cast<const void *>(smooth_threshold_kernel), bytes),
+    FSG_REQUIRE(bytes <= LDS_MAX && FSG_LDS_GRANTED(smooth_threshold_kernel, bytes),
                 "%s: %zu bytes of LDS refused", name, bytes);
     smooth_threshold_kernel<<<grid, dim3(NT), bytes, (hipStream_t)stream>>>(a, vol, out, flags);
     FSG_CHECK_LAUNCH(name);

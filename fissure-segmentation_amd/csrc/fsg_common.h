@@ -1,4 +1,4 @@
-// Shared host-side helpers for libfsg_hip.so (gfx950 only).
+// Shared host-side helpers for libfsg_hip.so (gfx950 only); the device-side ones are in fsg_device.h, included at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +29,24 @@ void fsg_set_error(const char *fmt, ...);
         }                                                                             \
     } while (0)
 
+// Raise the dynamic-LDS limit of `kernel` to `bytes` on the current device or fail the entry point `entry` with FSG_ERR_HIP.
+// Each expansion owns one FsgLdsGrant (below): one per call site / template instantiation, as that struct requires.
+// FSG_LDS_GRANTED is the bare test for a caller that reports the refusal itself.
+#define FSG_LDS_GRANTED(kernel, bytes)                               \
+    ([&]() -> bool {                                                 \
+        static FsgLdsGrant grant_;                                   \
+        return grant_.raise((const void *)(kernel), (size_t)(bytes)); \
+    }())
+#define FSG_GRANT_LDS(entry, kernel, bytes)                                                        \
+    do {                                                                                           \
+        if (!FSG_LDS_GRANTED(kernel, bytes)) {                                                     \
+            fsg_set_error("%s: cannot raise dynamic LDS to %zu", entry, (size_t)(bytes));          \
+            return FSG_ERR_HIP;                                                                    \
+        }                                                                                          \
+    } while (0)
+// what the kernels that take "all" of a CU's 160 KiB of LDS ask for
+constexpr size_t FSG_LDS_WHOLE_CU = 160 * 1024 - 512;
+
 static inline int fsg_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Dynamic LDS above the 64 KiB every kernel may use is granted per kernel AND per device (hipFuncSetAttribute acts on the
@@ -57,25 +75,5 @@ struct FsgLdsGrant {
 };
 
 #ifdef __HIPCC__
-// Row gathers with lanes = channels: the row index is wave-uniform (v_readlane of the neighbour list), so the row offset
-// belongs in the SCALAR offset of a buffer load and the lane's channel in its vector offset -- no per-load 64-bit address
-// arithmetic on the VALU (the plain-pointer form cost ~5 VALU issues per load, 160 of the ~330 of the gather phase), and a
-// row outside the tile is simply an offset outside the resource (reads 0).
-struct RowGather {
-    __amdgpu_buffer_rsrc_t rs;
-    unsigned oob;   // a byte offset outside the resource
-    __device__ __forceinline__ RowGather(const float *base, long bytes) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(base);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        const int n = __builtin_amdgcn_readfirstlane((int)bytes);
-        rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0, n, 0x00020000);
-        oob = (unsigned)n;
-    }
-    // element `col` (per lane) of row `row` (uniform) of a matrix with `ld` floats per row; !ok -> 0
-    __device__ __forceinline__ float load(bool ok, int row, int ld, int col) const {
-        const unsigned so = ok ? (unsigned)row * (unsigned)(ld * 4) : oob;
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)col * 4u,
-                                                                             __builtin_amdgcn_readfirstlane(so), 0));
-    }
-};
+#include "fsg_device.h"   // the device-side helpers every kernel file shares
 #endif

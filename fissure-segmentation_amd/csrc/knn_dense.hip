@@ -226,11 +226,7 @@ extern "C" int fsg_knn_dense_f32(const float *x, int B, int N, int64_t stride_b,
             fsg_set_error("fsg_knn_dense_f32: LDS need %zu B > 160 KiB (N=%d c_knn=%d)", lds, N, c_knn);
             return FSG_ERR_UNSUPPORTED;
         }
-        static FsgLdsGrant grant;  // per QB (the lambda's call operator is instantiated per type of qb)
-        if (!grant.raise((const void *)kern, lds)) {
-            fsg_set_error("fsg_knn_dense_f32: cannot raise dynamic LDS to %zu", lds);
-            return FSG_ERR_HIP;
-        }
+        FSG_GRANT_LDS("fsg_knn_dense_f32", kern, lds);  // per QB (the lambda's call operator is instantiated per type of qb)
         dim3 grid(fsg_cdiv(N, QB), B);
         hipLaunchKernelGGL(kern, grid, dim3(BLOCK), lds, st, x, N, Npad, (long)stride_b, (long)stride_c, c_knn, k,
                            flags, idx_out, dist_out);

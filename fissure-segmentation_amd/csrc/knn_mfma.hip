@@ -20,18 +20,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
 constexpr int CAP = 64;  // LDS column depth per lane; k + drop + 16 <= CAP
-
-__device__ __forceinline__ unsigned f2o(float d) {
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float o2f(unsigned k) {
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
 
 __global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float *__restrict__ x, int N, long sb, long sc, int c_knn,
                                                           float *__restrict__ xx) {
@@ -214,11 +203,7 @@ int fsg_knn_mfma_launch(const float *x, int B, int N, int64_t stride_b, int64_t 
     dim3 grid(fsg_cdiv(N, 32), B);
 #define FSG_KNN_MFMA(KS)                                                                                              \
     do {                                                                                                              \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)knn_mfma_kernel<KS>, (int)lds)) {                                              \
-            fsg_set_error("fsg_knn_dense_f32: cannot raise dynamic LDS to %zu", lds);                                 \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
+        FSG_GRANT_LDS("fsg_knn_dense_f32", knn_mfma_kernel<KS>, lds);                                                 \
         hipLaunchKernelGGL(knn_mfma_kernel<KS>, grid, dim3(256), lds, st, x, xx_scratch, N, (long)stride_b,           \
                            (long)stride_c, c_knn, k, flags, idx_out, dist_out);                                       \
     } while (0)

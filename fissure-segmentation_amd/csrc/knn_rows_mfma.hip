@@ -22,34 +22,10 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
-
 constexpr int QB = 32;            // queries per workgroup (two 16-row MFMA blocks)
 // CH = candidates per chunk (template): 1024 -> 131 KB of distance rows, one workgroup per CU; 512 -> 66 KB, TWO workgroups
 // per CU, so one workgroup's selection phase overlaps the other's MFMA phase.  LDS row stride CH + 4 floats:
 // 4*STRIDE = 16 (mod 32) -> conflict-free accumulator stores.  CK = capacity of the carried best list (>= k + drop).
-
-__device__ __forceinline__ unsigned f2o(float d) {
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float o2f(unsigned k) {
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-// inclusive prefix sum over the 64 lanes on the DPP network (Kogge-Stone inside each row of 16, then the row totals are
-// broadcast down): 6 VALU steps; the shuffle version (ds_bpermute) paid ~100 cycles of LDS-crossbar latency per step
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-    (void)lane;
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2 and 3
-    return v;
-}
 
 // bitonic sort, ascending, of 128 values spread as element (slot*64 + lane); T = unsigned or u64
 template <typename T>
@@ -258,16 +234,13 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
     // (channel l4, candidate col) + a scalar offset of four channel rows per MFMA step, instead of 16 per-lane
     // 64-bit pointers (32 VGPRs -- the compiler's choice for plain pointers); channels >= c_knn fall outside the
     // resource and read as 0, which is exactly the zero padding of the last K group.
-    const uintptr_t xba = reinterpret_cast<uintptr_t>(xb);   // uniform by construction: tell the compiler so
-    const unsigned xlo = __builtin_amdgcn_readfirstlane((unsigned)xba);
-    const unsigned xhi = __builtin_amdgcn_readfirstlane((unsigned)(xba >> 32));
+    const void *xbu = uniform_ptr(xb);   // uniform by construction: tell the compiler so
     // the resource ends with column N-1 of the LAST channel row: a read past it returns 0, every read before it
     // stays inside this cloud's own extent (with a channel stride > N, or the last cloud of a tensor, "the whole
     // row of every channel" would reach beyond the allocation); columns >= N of the earlier rows read whatever
     // lies between the rows -- those columns are overwritten with +inf below
     const int nrec = __builtin_amdgcn_readfirstlane((int)((((long)c_knn - 1) * sc + N) * 4));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void *>(((uintptr_t)xhi << 32) | xlo), 0, nrec, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(xbu, nrec);
 
     const unsigned sc32f = (unsigned)sc;
     constexpr int TPC = CH / 16;          // tiles per chunk
@@ -351,8 +324,7 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
     // 4 l15 + u in lane l15) reuse the loaded registers -- a quarter of the load instructions.  No software pipelining: the
     // other three waves of the SIMD keep the matrix pipe busy while one waits for its loads.
     const bool wide = !SEG && (N & 3) == 0;
-    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(xxb), 0, SEG ? 0 : N * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx = buffer_rsrc(xxb, SEG ? 0 : N * 4);
     auto ld4 = [&](f32x4 (&bt)[KS], f32x4 &xt, unsigned col) {
         const unsigned vo = ((unsigned)l4 * sc32f + col) * 4u;
 #pragma unroll
@@ -640,7 +612,9 @@ __global__ __launch_bounds__(WAVES * 64, (STREAM && WAVES == 8) ? 4 : 1) void kn
                     int mine = 0;
         #pragma unroll
                     for (int e = 0; e < VPL; ++e) mine += v[e] <= tau_f ? 1 : 0;
-                    const int incl = wave_incl_scan(mine, lane);
+                    // the prefix sum runs on the DPP network: 6 VALU steps; the shuffle version (ds_bpermute) paid ~100 cycles
+                    // of LDS-crossbar latency per step
+                    const int incl = wave_incl_scan(mine);
                     const int total = cc + __builtin_amdgcn_readlane(incl, 63);
                     if (total <= SURV) {
                         int pos = cc + incl - mine;
@@ -746,11 +720,7 @@ int fsg_knn_rows_mfma_launch(const float *x, int B, int N, int64_t stride_b, int
     do {                                                                                                               \
         const size_t lds = sizeof(float) * QB * ((CHK) + 4) + sizeof(u64) * (QB * (CKK)) + sizeof(int) * QB +           \
                            ((QL) ? sizeof(float) * 4 * (KS) * QB : 0) + ((STRM) ? 2 * sizeof(int) * QB : 0);           \
-        static FsgLdsGrant grant;                                                                                     \
-        if (!grant.raise((const void *)knn_rows_mfma_kernel<KS, WV, SV, CHK, CKK, false, QL, STRM>, (int)lds)) {      \
-            fsg_set_error("fsg_knn_dense_f32: cannot raise dynamic LDS to %zu", lds);                                 \
-            return FSG_ERR_HIP;                                                                                       \
-        }                                                                                                             \
+        FSG_GRANT_LDS("fsg_knn_dense_f32", (knn_rows_mfma_kernel<KS, WV, SV, CHK, CKK, false, QL, STRM>), lds);       \
         hipLaunchKernelGGL((knn_rows_mfma_kernel<KS, WV, SV, CHK, CKK, false, QL, STRM>), grid, dim3((WV) * 64), lds, st, x, \
                            xx_scratch, N,                                                                              \
                            (long)stride_b, (long)stride_c, c_knn, k, flags, idx_out, dist_out, SegArgs{});             \
@@ -794,11 +764,7 @@ int fsg_knn_segment_rows_launch(const float *xyz, const float *new_xyz, const in
     if (nsample > 32 || b > 4096) return FSG_ERR_UNSUPPORTED;
     constexpr int WV = 16, SV = 96, CHK = 1024, CKK = 64;
     const size_t lds = sizeof(float) * QB * (CHK + 4) + sizeof(u64) * (QB * CKK) + sizeof(int) * QB;
-    static FsgLdsGrant grant;
-    if (!grant.raise((const void *)knn_rows_mfma_kernel<1, WV, SV, CHK, CKK, true>, (int)lds)) {
-        fsg_set_error("fsg_knn_segment_f32: cannot raise dynamic LDS to %zu", lds);
-        return FSG_ERR_HIP;
-    }
+    FSG_GRANT_LDS("fsg_knn_segment_f32", (knn_rows_mfma_kernel<1, WV, SV, CHK, CKK, true>), lds);
     const SegArgs sa{new_xyz, offset, new_offset, b};
     hipLaunchKernelGGL((knn_rows_mfma_kernel<1, WV, SV, CHK, CKK, true>), dim3(fsg_cdiv(m, QB) + b), dim3(WV * 64), lds, st,
                        xyz, (const float *)nullptr, n, 0L, 0L, 3, nsample, 0, idx, dist2, sa);

@@ -68,64 +68,10 @@ extern "C" int fsg_debug_knn_split_stamps(unsigned long long *out) {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
-
 constexpr int QB = 64;        // queries per workgroup
 constexpr int WAVES = 8;
 constexpr int MSL = 4;         // group-minimum slots per lane and query block in sweep 1
 constexpr int NMIN = 2 * WAVES * MSL;   // group minima per query (64): tau = the K-th smallest of them
-
-__device__ __forceinline__ unsigned f2o(float d) {
-    const unsigned u = __float_as_uint(d);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float o2f(unsigned k) {
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-// round-to-nearest-even bf16 of a finite float, in integer arithmetic
-__device__ __forceinline__ unsigned bf16_rne(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ float bf16_f(unsigned h) { return __uint_as_float(h << 16); }
-
-struct Split { unsigned hi, lo; };
-__device__ __forceinline__ Split split2(float v) {
-    Split s;
-    s.hi = bf16_rne(v);
-    s.lo = bf16_rne(v - bf16_f(s.hi));   // v - hi is exact in fp32
-    return s;
-}
-
-// wave-wide sum / maximum of a float on the DPP network (row_shr 1,2,4,8, then the row totals broadcast down): lane 63 holds
-// the result, returned to every lane through a scalar read
-__device__ __forceinline__ float wave_sum_f(float v) {
-#define FSG_DPP_F(x, ctrl, rm, bc) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rm, 0xf, bc))
-    v += FSG_DPP_F(v, 0x111, 0xf, true);
-    v += FSG_DPP_F(v, 0x112, 0xf, true);
-    v += FSG_DPP_F(v, 0x114, 0xf, true);
-    v += FSG_DPP_F(v, 0x118, 0xf, true);
-    v += FSG_DPP_F(v, 0x142, 0xa, false);
-    v += FSG_DPP_F(v, 0x143, 0xc, false);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-// maximum of NON-NEGATIVE floats (a masked-out DPP source reads as +0, the identity here)
-__device__ __forceinline__ float wave_max_nonneg_f(float v) {
-    v = fmaxf(v, FSG_DPP_F(v, 0x111, 0xf, true));
-    v = fmaxf(v, FSG_DPP_F(v, 0x112, 0xf, true));
-    v = fmaxf(v, FSG_DPP_F(v, 0x114, 0xf, true));
-    v = fmaxf(v, FSG_DPP_F(v, 0x118, 0xf, true));
-    v = fmaxf(v, FSG_DPP_F(v, 0x142, 0xa, false));
-    v = fmaxf(v, FSG_DPP_F(v, 0x143, 0xc, false));
-#undef FSG_DPP_F
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 // ---------------------------------------------------------------------------------------------------------------- prep
 // grid (Np / 32, B), 256 threads: 32 points = one operand tile.
@@ -164,11 +110,11 @@ __global__ __launch_bounds__(256) void knn_split_prep_kernel(const float *__rest
         float dv = 0.f;
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-            const float m = wave_sum_f(sv[r]) * (1.0f / 64.0f);
+            const float m = wave_sum_bcast_f(sv[r]) * (1.0f / 64.0f);
             if (sp == 0) mu[w + 4 * r] = m;
             dv = fmaxf(dv, fabsf(sv[r] - m));
         }
-        dv = wave_max_nonneg_f(dv);
+        dv = wave_max_nonneg_bcast_f(dv);
         if (sp == 0) wred[w] = dv;
         __syncthreads();
         const float maxdev = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
@@ -245,7 +191,7 @@ __global__ __launch_bounds__(256) void knn_split_prep_kernel(const float *__rest
             unsigned hi[4], lo[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const Split s = split2(slab[i][m]);
+                const Bf16Split2 s = bf16_split2_finite(slab[i][m]);
                 hi[i] = s.hi; lo[i] = s.lo;
             }
             // candidate image [hi | hi] / [lo | 0]; the query image of the same point is [hi | lo] / [hi | 0] (times -2):
@@ -262,7 +208,7 @@ __global__ __launch_bounds__(256) void knn_split_prep_kernel(const float *__rest
             unsigned cw[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const Split sp = split2(slab[16 * s + 8 * h + i][m]);
+                const Bf16Split2 sp = bf16_split2_finite(slab[16 * s + 8 * h + i][m]);
                 cw[i] = part ? sp.lo : sp.hi;
             }
             const long o = ((((long)b * T + tile) * KS + s) * 2 + part) * 64 + lane;
@@ -291,17 +237,6 @@ __device__ __forceinline__ float above(float thr) {
     if (thr == -INFINITY || thr != thr) return thr;
     if (thr == 0.f) return __uint_as_float(1u);
     return __uint_as_float(thr > 0.f ? u + 1u : u - 1u);
-}
-
-// inclusive prefix sum over the 64 lanes on the DPP network (as knn_rows_mfma.hip)
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return v;
 }
 
 template <int KS, bool PACK, bool HALF>
@@ -587,9 +522,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_split_kernel(const float *_
 #pragma unroll
             for (int e = 0; e < KPL; ++e) m = __builtin_amdgcn_alignbit(m, key[e] - t1, 31);
             int c = __popc(m);
-            c += __builtin_amdgcn_update_dpp(0, c, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
-            c += __builtin_amdgcn_update_dpp(0, c, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
-            c += __builtin_amdgcn_update_dpp(0, c, 0x141, 0xf, 0xf, true);   // row_half_mirror: the other quad of the eight
+            c += dpp_mov0<0xB1, 0xf, true>(c);    // quad_perm [1,0,3,2]
+            c += dpp_mov0<0x4E, 0xf, true>(c);    // quad_perm [2,3,0,1]
+            c += dpp_mov0<0x141, 0xf, true>(c);   // row_half_mirror: the other quad of the eight
             if (c < KK) prefix |= 1u << bit;
         }
         prefix = (prefix << 1) | 1u;     // back to 32-bit keys, rounded up
@@ -1078,7 +1013,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_nominate_kernel(const float
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             if (c < raw.c_knn) {
-                const Split sp = split2(xrb[c * raw.sc + 32 * t + n]);
+                const Bf16Split2 sp = bf16_split2_finite(xrb[c * raw.sc + 32 * t + n]);
                 hh[c] = sp.hi;
                 ll[c] = sp.lo;
             }
@@ -1320,7 +1255,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void knn_nominate_kernel(const float
             for (int e = 0; e < 4; ++e) kv[4 * e4 + e] = va[e] + xq;
         }
 #define FSG_CE(a, b) { const float lo_ = fminf(kv[a], kv[b]), hi_ = fmaxf(kv[a], kv[b]); kv[a] = lo_; kv[b] = hi_; }
-#define FSG_DPPF(x, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
+#define FSG_DPPF(x, ctrl) dpp_mov0<ctrl, 0xf, true>(x)
         auto in4 = [&]() { FSG_CE(0, 4) FSG_CE(1, 5) FSG_CE(2, 6) FSG_CE(3, 7) };
         auto in2 = [&]() { FSG_CE(0, 2) FSG_CE(1, 3) FSG_CE(4, 6) FSG_CE(5, 7) };
         auto in1 = [&]() { FSG_CE(0, 1) FSG_CE(2, 3) FSG_CE(4, 5) FSG_CE(6, 7) };
@@ -1610,9 +1545,9 @@ __global__ __launch_bounds__(128) void knn_refine_kernel(const float *__restrict
         return __popc(a[0]) + __popc(a[1]) + __popc(a[2]) + __popc(a[3]) + __popc(c[0]) + __popc(c[1]) + __popc(c[2]) + __popc(c[3]);
     };
     auto sum8 = [](int c) {                         // sum over the eight lanes of a query, in every lane
-        c += __builtin_amdgcn_update_dpp(0, c, 0xB1, 0xf, 0xf, true);
-        c += __builtin_amdgcn_update_dpp(0, c, 0x4E, 0xf, 0xf, true);
-        c += __builtin_amdgcn_update_dpp(0, c, 0x141, 0xf, 0xf, true);
+        c += dpp_mov0<0xB1, 0xf, true>(c);
+        c += dpp_mov0<0x4E, 0xf, true>(c);
+        c += dpp_mov0<0x141, 0xf, true>(c);
         return c;
     };
     load_chunk(0, wa, wb);
@@ -1676,9 +1611,9 @@ __global__ __launch_bounds__(128) void knn_refine_kernel(const float *__restrict
             const int cn = popc8(a, c);
             // exclusive prefix over the eight lanes of the query (row_shr inside the 16-lane row, masked at the group start)
             int ps = cn;
-            { const int t = __builtin_amdgcn_update_dpp(0, ps, 0x111, 0xf, 0xf, true); ps += l8 >= 1 ? t : 0; }
-            { const int t = __builtin_amdgcn_update_dpp(0, ps, 0x112, 0xf, 0xf, true); ps += l8 >= 2 ? t : 0; }
-            { const int t = __builtin_amdgcn_update_dpp(0, ps, 0x114, 0xf, 0xf, true); ps += l8 >= 4 ? t : 0; }
+            { const int t = dpp_mov0<0x111, 0xf, true>(ps); ps += l8 >= 1 ? t : 0; }
+            { const int t = dpp_mov0<0x112, 0xf, true>(ps); ps += l8 >= 2 ? t : 0; }
+            { const int t = dpp_mov0<0x114, 0xf, true>(ps); ps += l8 >= 4 ? t : 0; }
             int pos = sstart + runoff + ps - cn;
             runoff += sum8(cn);
             const unsigned tagw = (unsigned)qi << 16;
@@ -1716,8 +1651,7 @@ __global__ __launch_bounds__(128) void knn_refine_kernel(const float *__restrict
         // step: the chain of a step is ~500 cycles, an L2 round trip under load several times that).  Buffer loads: the row
         // offset is one v_lshl_add from the entry, the slab's offset is scalar.
         const int rs = lane / LS, lc = lane % LS;
-        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float *>(xtb), 0, __builtin_amdgcn_readfirstlane((int)min((long)Np * CP * 4, 0x7FFFFFFFL)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(xtb, __builtin_amdgcn_readfirstlane((int)min((long)Np * CP * 4, 0x7FFFFFFFL)));
         const int NT = ((E + 63) >> 6) * NSLAB;
         u32x4 g[2][NI];
         float xnr[2] = {0.f, 0.f};
@@ -1940,11 +1874,7 @@ int launch_monolithic(const SplitArgs &a) {
     while (PC >= 256 && fixed + 8 * (size_t)WAVES * PC > 160 * 1024) PC /= 2;
     if (PC < 256) return FSG_ERR_UNSUPPORTED;
     const size_t lds = fixed + 8 * (size_t)WAVES * PC;
-    static FsgLdsGrant grant;   // per instantiation
-    if (!grant.raise((const void *)knn_split_kernel<KS, PK, HF>, 160 * 1024)) {
-        fsg_set_error("fsg_knn_dense_ws_f32: cannot raise dynamic LDS");
-        return FSG_ERR_HIP;
-    }
+    FSG_GRANT_LDS("fsg_knn_dense_ws_f32", (knn_split_kernel<KS, PK, HF>), 160 * 1024);   // per instantiation
     launch_prep<KS, PK, HF>(a);
     hipLaunchKernelGGL((knn_split_kernel<KS, PK, HF>), dim3(p.Np / 64, a.B), dim3(WAVES * 64), lds, a.st, a.xx, a.xt, a.cand, a.xs,
                        a.cscale, a.N, p.Np, a.k, a.flags, PC, a.idx_out, a.dist_out);
@@ -1954,11 +1884,7 @@ int launch_monolithic(const SplitArgs &a) {
 
 template <int KS, bool PK, bool HF, bool RES, bool RAW>
 int launch_nominate(const SplitArgs &a, size_t lds, int PCAP, int TS, const RawPoints &raw) {
-    static FsgLdsGrant grant;   // per instantiation: the one that is launched
-    if (!grant.raise((const void *)knn_nominate_kernel<KS, PK, HF, RES, RAW>, lds)) {
-        fsg_set_error("fsg_knn_dense_ws_f32: cannot raise dynamic LDS to %zu", lds);
-        return FSG_ERR_HIP;
-    }
+    FSG_GRANT_LDS("fsg_knn_dense_ws_f32", (knn_nominate_kernel<KS, PK, HF, RES, RAW>), lds);   // per instantiation: the one that is launched
     hipLaunchKernelGGL((knn_nominate_kernel<KS, PK, HF, RES, RAW>), dim3(a.p.Np / 64, a.B), dim3(WAVES * 64), lds, a.st, a.xx, a.xt,
                        a.cand, a.xs, a.cscale, a.N, a.p.Np, a.k, a.flags, PCAP, a.bmg, TS, a.idx_out, a.dist_out, raw);
     return FSG_OK;

@@ -12,11 +12,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
-
 template <int NS>
 __global__ __launch_bounds__(BLOCK) void knn_segment_kernel(const float *__restrict__ xyz,
                                                              const float *__restrict__ new_xyz,

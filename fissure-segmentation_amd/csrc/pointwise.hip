@@ -27,35 +27,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 enum { PW_STORE = 1, PW_STATS = 2, PW_SEL = 4, PW_BWDSTATS = 8, PW_BIAS = 16 };
 enum { PRO_NONE = 0, PRO_BNACT = 1, PRO_BNBWD = 2 };
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {   // (a, b) -> packed bf16 pair, a in the low half, RNE
-    bf16x2 v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-
-// eight fp32 values -> three bf16 pieces each (h, m, l as packed operand fragments)
-__device__ __forceinline__ void split8(const float (&x)[8], u32x4 &h, u32x4 &m, u32x4 &l) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = x[2 * q], b = x[2 * q + 1];
-        const unsigned ph = pk_bf16(a, b);
-        const float ra = a - __uint_as_float(ph << 16), rb = b - __uint_as_float(ph & 0xffff0000u);
-        const unsigned pm = pk_bf16(ra, rb);
-        const float sa = ra - __uint_as_float(pm << 16), sb = rb - __uint_as_float(pm & 0xffff0000u);
-        h[q] = ph;
-        m[q] = pm;
-        l[q] = pk_bf16(sa, sb);
-    }
-}
 
 // B operand image of a (N, K) matrix W(n, k) = W[n * sn + k * sk] * scale:  blocks [nb][ks][piece][lane] of 16 bytes, lane
 // (n = 32 nb + (lane & 31), k = 16 ks + 8 (lane >> 5) + 0..7); rows >= N and columns >= K read as zero.  `ks0`/`KS`: the
@@ -578,11 +551,7 @@ int launch_rowgemm(const RowGemmArgs &a, hipStream_t st, const char *name) {
     size_t lds = (PIPE ? 2 : 1) * ((size_t)(BM / 32) * 2 * NP + (size_t)(BN / 32) * 2 * NP) * 1024 + sizeof(float) * 4 * (size_t)a.K1;
     const size_t scratch = sizeof(float) * 2 * 2 * WN * 32;
     if (lds < scratch) lds = scratch;
-    static FsgLdsGrant grant;      // (per template instantiation; the grant itself is per device)
-    if (!grant.raise((const void *)pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP>, lds)) {
-        fsg_set_error("%s: cannot raise dynamic LDS to %zu", name, lds);
-        return FSG_ERR_HIP;
-    }
+    FSG_GRANT_LDS(name, (pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP>), lds);   // (per template instantiation; the grant itself is per device)
     hipLaunchKernelGGL((pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP>), dim3(grid), dim3(256), lds, st, a);
     FSG_CHECK_LAUNCH(name);
     return FSG_OK;

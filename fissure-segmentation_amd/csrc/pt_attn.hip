@@ -26,7 +26,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef fsg_pt_layer_params Prm;
 
 constexpr int MAXNS = 16;
@@ -57,17 +56,6 @@ struct Stats {
 __host__ __device__ inline Stats split_stats(const float *s, int c) {
     const int cs = c / 8;
     return Stats{s, s + 3, s + 6, s + 6 + c, s + 6 + 2 * c, s + 6 + 2 * c + cs};
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
 }
 
 // positional front end of one tile: neighbour ids and t = relu(BNp(W1 d + b1)); optionally a-hat and d
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(256) void pt_stats_p_kernel(const float *__restrict
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
-        const double a = wave_sum_d(s[m]), b = wave_sum_d(ss[m]);
+        const double a = wave_sum_lane0(s[m]), b = wave_sum_lane0(ss[m]);
         if (lane == 0) { red[wave][m] = a; red[wave][3 + m] = b; }
     }
     __syncthreads();
@@ -142,8 +130,8 @@ __global__ __launch_bounds__(256) void pt_bn_finalize_kernel(const double *__res
         S += rec[(long)r * 2 * L + l];
         SS += rec[(long)r * 2 * L + L + l];
     }
-    S = wave_sum_d(S);
-    SS = wave_sum_d(SS);
+    S = wave_sum_lane0(S);
+    SS = wave_sum_lane0(SS);
     if (lane != 0) return;
     const double m = S / M;
     double var = SS / M - m * m;
@@ -713,7 +701,7 @@ __global__ __launch_bounds__(Geo<C>::NT) void pt_b3_kernel(const float *__restri
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
-        const float a = wave_sum_f(dgp[m]), b = wave_sum_f(dbp[m]);
+        const float a = wave_sum_lane0(dgp[m]), b = wave_sum_lane0(dbp[m]);
         if (lane == 0) { REDP[wave][m] = a; REDP[wave][3 + m] = b; }
     }
     __syncthreads();
@@ -764,7 +752,7 @@ __global__ __launch_bounds__(256) void pt_b4_kernel(const float *__restrict__ p,
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
-        const float a = wave_sum_f(acc[i]);
+        const float a = wave_sum_lane0(acc[i]);
         if (lane == 0) red[wave][i] = a;
     }
     __syncthreads();

@@ -53,12 +53,6 @@ __device__ __forceinline__ void load_softmax(const float *__restrict__ logits, l
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // record layout per block: [tp_c | sp_c | cnt_c] (3*C) then ce_num, ce_den, n_bad
 template <int MAXC>
 __global__ __launch_bounds__(BLOCK) void nnu_partial_kernel(const float *__restrict__ logits, long sb, long sc, long sn,
@@ -87,11 +81,11 @@ __global__ __launch_bounds__(BLOCK) void nnu_partial_kernel(const float *__restr
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
-        const double a = wave_sum((double)tp[c]), s2 = wave_sum((double)sp[c]), n2 = wave_sum((double)cnt[c]);
+        const double a = wave_sum_lane0((double)tp[c]), s2 = wave_sum_lane0((double)sp[c]), n2 = wave_sum_lane0((double)cnt[c]);
         if (lane == 0 && c < C) { part[wave][c] = a; part[wave][C + c] = s2; part[wave][2 * C + c] = n2; }
     }
     {
-        const double a = wave_sum((double)ce_num), d = wave_sum((double)ce_den), e = wave_sum((double)bad);
+        const double a = wave_sum_lane0((double)ce_num), d = wave_sum_lane0((double)ce_den), e = wave_sum_lane0((double)bad);
         if (lane == 0) { part[wave][3 * C] = a; part[wave][3 * C + 1] = d; part[wave][3 * C + 2] = e; }
     }
     __syncthreads();

@@ -17,8 +17,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int TI = 64, TJ = 64, TK = 32, LDT = 65;  // k-major LDS tiles [TK][64 + 1]
 constexpr int LPT = TI * TK / 256;                  // tile elements per thread and operand
 
@@ -104,7 +102,6 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(const float *__restrict
 // (round to nearest even, as torch's .bfloat16()) on their way into LDS and the products run on v_mfma_f32_32x32x16_bf16 with
 // fp32 accumulation -- two matrix instructions per 32-deep tile and wave instead of sixteen.  LDS tiles are row-major [64][32 + 8]
 // bf16 (a fragment = eight consecutive k of one row = one 16-byte read).  The row-sum by-product sums the ROUNDED values.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 constexpr int LDH = TK + 8;   // bf16 row stride (80 bytes: 16-byte aligned fragments, rows spread over the banks)
 __device__ __forceinline__ u16 to_bf16(float x) {

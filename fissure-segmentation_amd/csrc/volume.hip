@@ -39,7 +39,6 @@ struct VolArgs {
     int outch[MAXCH];                 // MIND: output position of channel c
 };
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 template <int MODE, int NCH, int TZ, int TY, int TX, int NT>
 __global__ __launch_bounds__(NT) void vol_kernel(VolArgs a, const float *__restrict__ img, float *__restrict__ out,
@@ -323,9 +322,8 @@ int launch_vol(const char *name, const VolArgs &a, dim3 grid, const float *img, 
                           (size_t)NCH * (TY + 2 * a.R) * (TX + 2 * a.R) + (size_t)NCH * TY * (TX + 2 * a.R);
     const size_t bytes = floats * sizeof(float);   // (the planes hold more than NT floats: the statistics tree fits)
     FSG_REQUIRE(bytes <= LDS_MAX, "%s: sigma / dilation need %zu bytes of LDS per tile, the CU has %zu", name, bytes, LDS_MAX);
-    static FsgLdsGrant grant;
     auto kernel = vol_kernel<MODE, NCH, TZ, TY, TX, NT>;
-    FSG_REQUIRE(grant.raise(reinterpret_cast<const void *>(kernel), bytes), "%s: %zu bytes of LDS refused", name, bytes);
+    FSG_REQUIRE(FSG_LDS_GRANTED(kernel, bytes), "%s: %zu bytes of LDS refused", name, bytes);
     kernel<<<grid, dim3(NT), bytes, stream>>>(a, img, out, kp, K, mean, partial);
     FSG_CHECK_LAUNCH(name);
     return FSG_OK;
@@ -364,9 +362,8 @@ extern "C" int fsg_nms_keypoints(const float *dist, const uint8_t *mask, int B, 
     const long gz = (long)B * fsg_cdiv(D, VZ);
     FSG_REQUIRE(gz <= 65535 && fsg_cdiv(H, VY) <= 65535, "%s: volume too large for one launch", name);
     const size_t bytes = ((size_t)(VZ + d - 1) * (VY + d - 1) * (VX + d - 1) + (size_t)(VZ + d - 1) * (VY + d - 1) * VX) * sizeof(float);
-    static FsgLdsGrant grant;
     auto kernel = nms_kernel<VZ, VY, VX, VT>;
-    FSG_REQUIRE(bytes <= LDS_MAX && grant.raise(reinterpret_cast<const void *>(kernel), bytes), "%s: %zu bytes of LDS refused",
+    FSG_REQUIRE(bytes <= LDS_MAX && FSG_LDS_GRANTED(kernel, bytes), "%s: %zu bytes of LDS refused",
                 name, bytes);
     kernel<<<dim3(fsg_cdiv(W, VX), fsg_cdiv(H, VY), (unsigned)gz), dim3(VT), bytes, (hipStream_t)stream>>>(
         dist, mask, B, D, H, W, lo, hi, thresh, maxout, flags);
