@@ -33,6 +33,7 @@ def install_reference_aliases():
         "data_processing.foerstner": ".data_processing.foerstner", "data_processing.point_features": ".data_processing.point_features",
         "data_processing.keypoint_extraction": ".data_processing.keypoint_extraction",
         "data_processing.fissure_enhancement": ".data_processing.fissure_enhancement",
+        "data_processing.random_walk": ".data_processing.random_walk", "data_processing.find_lobes": ".data_processing.find_lobes",
         "utils.image_utils": ".utils.image_utils", "utils.general_utils": ".utils.general_utils",
     }
     for ref_name, ours in pairs.items():

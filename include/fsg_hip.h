@@ -880,6 +880,48 @@ int fsg_cpd_estep_f32(const float *X, int64_t x_batch_stride, const float *TY, c
                       float *P1, float *Pt1, float *PX, float *Np, void *workspace, size_t workspace_bytes,
                       fsg_stream_t stream);
 
+/* Random-walker lobe filling and lobes-to-fissures (csrc/random_walk.hip).  Volumes are (B, D, H, W), DEVICE, contiguous.
+ *
+ * The graph of compute_laplace_matrix (data_processing/random_walk.py:15-77) is never a matrix: nodes are the voxels, edges
+ *   the axis neighbours inside the volume (no wrap), w_ij = (im_i == im_j ? 1 : 0.01) for FSG_RW_BINARY (im: bytes) or
+ *   exp(-(im_i - im_j)^2 / (2 * 8^2)) for FSG_RW_INTENSITY (im: fp32), L = diag(1e-5 + sum_j w_ij) - W.  The degree counts
+ *   every in-volume neighbour, masked or seeded alike (:70-75).
+ * The solve is random_walk (:80-116): seeded = label != 0 inside the mask (mask NULL: every voxel is inside), unknown = the
+ *   rest of the mask, system k has the right-hand side b_i = sum of w_ij over seeded in-mask neighbours j of label k + 1.  A
+ *   label outside 0..K seeds no system (it absorbs with value 0).  Instead of the reference's pyamg hierarchy (:309-321) the
+ *   B K systems run Jacobi-preconditioned conjugate gradients together from x = 0: `prep` writes the state byte, the inverse
+ *   diagonal, r = b and the first reductions (two launches); `iterate` enqueues `iterations` iterations numbered from
+ *   `first_iteration` (the caller counts; three launches each: stencil, update, one workgroup per system for the scalars).
+ *   A system stops once |r| <= tol |b| on the recurrence's r: stop_iter[b K + k] (DEVICE, int32) then holds the number of
+ *   iterations it took (-1 while it runs, 0 for an all-zero right-hand side) and its x is final -- later iterations skip it,
+ *   so its result does not depend on the rest of the batch.  relres (DEVICE, fp32, per system) = |r| / |b| after the last
+ *   iteration the system took part in.  The host decides when to look (the wrapper does every 25 iterations).
+ *   `finish` writes prob (B, D, H, W, K) fp32 (one-hot rows at seeds, x at unknowns, 0 outside the mask; may be NULL) and
+ *   filled (bytes; may be NULL) = first-index argmax + 1 inside the mask, 0 outside: fill_lobes (data_processing/
+ *   find_lobes.py:17-30), where a voxel whose probabilities are all 0 becomes label 1.
+ * K is 1..8.  Reductions are fp64 partials summed in a fixed order, no atomics: the same input gives the same bits.
+ * workspace: the query below, 8-byte aligned, owned by the caller from prep to finish; it holds five (B, K, D, H, W) fp32
+ *   vectors, 5 bytes per voxel of state and the partial sums.  Too small a workspace is FSG_ERR_ARG.
+ *
+ * fsg_lobes_to_fissures_u8 is the tensor part of lobes_to_fissures (find_lobes.py:47-88) on labels, without the one-hot
+ *   volume: a label counts as present at a voxel if the voxel or one of its six in-volume neighbours carries it; fissure 1
+ *   where 3 and 4 are present, overwritten by 2 where 1 and 2 (n_lobes == 5: or 1 and 5) are, overwritten by 3 where 2 and 5
+ *   are (n_lobes == 5 only).  n_lobes is the largest label of the volume, at least 4 (the reference fails on an index below).
+ */
+#define FSG_RW_BINARY 0
+#define FSG_RW_INTENSITY 1
+size_t fsg_random_walk_workspace_bytes(int B, int K, int D, int H, int W);
+int fsg_random_walk_prep(const void *im, int mode, const void *labels, int labels_are_i32, const uint8_t *mask, int B, int K, int D,
+                         int H, int W, void *workspace, size_t workspace_bytes, int32_t *stop_iter, float *relres,
+                         fsg_stream_t stream);
+int fsg_random_walk_iterate(const void *im, int mode, int B, int K, int D, int H, int W, int first_iteration, int iterations,
+                            float tol, void *workspace, size_t workspace_bytes, int32_t *stop_iter, float *relres,
+                            fsg_stream_t stream);
+int fsg_random_walk_finish(int B, int K, int D, int H, int W, const void *workspace, size_t workspace_bytes, float *prob,
+                           uint8_t *filled, fsg_stream_t stream);
+int fsg_lobes_to_fissures_u8(const uint8_t *lobes, int B, int D, int H, int W, int n_lobes, uint8_t *fissures,
+                             fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,3 +298,93 @@ if "cpd" in which:
                                    first_run_s=round(t1 - t0, 3), run_s=round(whole, 3), iterations=reg.iteration.tolist()[:4],
                                    solve_us_each=round(solve_us, 1),
                                    solves_fraction_of_run=round(ITERATIONS * solve_us * 1e-6 / whole, 3))), flush=True)
+if "rw" in which:
+    # random-walker lobe filling (csrc/random_walk.hip) beside the same Jacobi-preconditioned conjugate gradients written as a
+    # torch composition on the same device (shifted-slice stencil over the whole volume, torch reductions, no host reads), run
+    # for the iteration count the fused path needed.  Ellipsoid mask, K = 5 lobes, 2048 seeds, the binary graph of fill_lobes.
+    import json, time, warnings
+    import random_walk_oracle as ro
+    shapes = [tuple(int(v) for v in a.split("x")) for a in os.environ.get("FSG_RW_SHAPES", "128x128x128,256x256x320").split(",")]
+    K = 5
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); out = fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        return statistics.median(ts), out
+
+    def peak(fn):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn(); torch.cuda.synchronize()
+        del out
+        return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    def torch_pcg(labels, mask, iters):
+        im = labels != 0
+        unknown, seeded = mask & ~im, mask & im
+        w = [torch.where(im.narrow(a, 1, im.shape[a] - 1) == im.narrow(a, 0, im.shape[a] - 1), 1.0, 0.01) for a in range(3)]
+
+        def nbr_sum(p):   # sum_j w_ij p_j over the axis neighbours, p (K, D, H, W)
+            out = torch.zeros_like(p)
+            for a in range(3):
+                n = p.shape[a + 1] - 1
+                out.narrow(a + 1, 1, n).add_(w[a] * p.narrow(a + 1, 0, n))
+                out.narrow(a + 1, 0, n).add_(w[a] * p.narrow(a + 1, 1, n))
+            return out
+        diag = 1e-5 + nbr_sum(torch.ones(1, *im.shape, device=dev))[0]
+        dinv = unknown / diag
+        onehot = torch.stack([(seeded & (labels == k + 1)).float() for k in range(K)])
+        r = nbr_sum(onehot) * unknown
+        x, p = torch.zeros_like(r), dinv * r
+        rz = (r * p).sum((1, 2, 3))
+        for _ in range(iters):
+            q = (diag * p - nbr_sum(p)) * unknown
+            pq = (p * q).sum((1, 2, 3))
+            alpha = torch.where(pq > 0, rz / pq, torch.zeros_like(pq))[:, None, None, None]
+            x += alpha * p
+            r -= alpha * q
+            z = dinv * r
+            rz2 = (r * z).sum((1, 2, 3))
+            p = z + torch.where(rz > 0, rz2 / rz, torch.zeros_like(rz))[:, None, None, None] * p
+            rz = rz2
+        return x
+
+    lines = []
+    for shape in shapes:
+        vol = ro.make_volume(shape, 2048, n_lobes=K, seed=0)
+        labels, mask = torch.from_numpy(vol["labels"]).to(dev), torch.from_numpy(vol["mask"]).to(dev)
+        V, U = labels.numel(), int((mask & (labels == 0)).sum())
+        solve = lambda **kw: F.random_walk_fill(labels, mask, num_labels=K, return_info=True, **kw)
+        solve(); solve()   # warm-up
+        us, (filled, info) = wall(solve)
+        iters = info["iterations"].tolist()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")   # tol = 0 never stops: every system stays live, the count is fixed
+            n_it = 100
+            us0, _ = wall(lambda: solve(tol=0.0, max_iter=0))
+            us1, _ = wall(lambda: solve(tol=0.0, max_iter=n_it, check_every=n_it))
+        us_iter = (us1 - us0) / n_it
+        bytes_iter = U * (40 * K + 9) + 2 * V   # vectors of the unknown voxels, their image byte and inverse diagonal, every state byte twice
+        rec = dict(kernel="random_walk_fill binary K=5 seeds=2048 tol=1e-3", shape="x".join(map(str, shape)), voxels=V, unknowns=U,
+                   iterations=iters, relative_residual=[round(v, 6) for v in info["relative_residual"].tolist()],
+                   hip_solve_us=round(us, 1), hip_setup_and_finish_us=round(us0, 1), hip_us_per_iteration_all_live=round(us_iter, 1),
+                   bytes_per_iteration=bytes_iter, hip_GBps=round(bytes_iter / us_iter / 1e3, 1),
+                   hip_share_of_6p29TBps=round(bytes_iter / us_iter / 6.29e6, 3),
+                   hip_workspace_MiB=round(fsg._lib.lib.fsg_random_walk_workspace_bytes(1, K, *shape) / 2 ** 20, 1))
+        rec["hip_peak_MiB"] = peak(solve)
+        print("rw: fused side of %s done, composition running" % rec["shape"], file=sys.stderr, flush=True)
+        n = max(iters)
+        torch_pcg(labels, mask, 2)   # warm-up
+        tus, _ = wall(lambda: torch_pcg(labels, mask, n), reps=3)
+        tus0, _ = wall(lambda: torch_pcg(labels, mask, 0), reps=3)
+        rec.update(torch_iterations=n, torch_solve_us=round(tus, 1), torch_us_per_iteration=round((tus - tus0) / n, 1),
+                   torch_peak_MiB=peak(lambda: torch_pcg(labels, mask, 2)))
+        rec["speedup_same_iterations"] = round(tus / us, 2)
+        print("RW " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    out_path = os.environ.get("FSG_RW_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
