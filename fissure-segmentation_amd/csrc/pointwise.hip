@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
     // ---------------------------------------------------------------- epilogue: lane holds column (lane & 31) of each of its
     // tiles and rows (e & 3) + 8 (e >> 2) + 4 (lane >> 5), e = 0..15
     const int half = lane >> 5, lc = lane & 31;
-    if ((EPI & PW_STORE) && col0 >= p.store_n0) {
+    if ((EPI & PW_STORE) && col0 + BN > p.store_n0) {     // (store_n0 may fall inside a column tile: the general path masks per column)
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
                 const int col = col0 + (wn * WN + j) * 32 + lc;
                 float bv = 0.f;                       // the bias is applied on the way out (PW_BIAS comes with PW_STORE only)
                 if constexpr ((EPI & PW_BIAS) != 0) bv = col < p.N ? p.bias[col] : 0.f;
-                if (row0 + BM <= p.M && col0 + BN <= p.N) {       // tile inside the matrix (workgroup-uniform): sixteen plain stores
+                if (row0 + BM <= p.M && col0 + BN <= p.N && col0 >= p.store_n0) {   // tile inside the stored part (workgroup-uniform): sixteen plain stores
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int row = row0 + (wm * WM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int row = row0 + (wm * WM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                        if (row < p.M && col < p.N) p.C[(long)row * p.ldc + (col - p.store_n0)] = acc[i][j][e] + bv;
+                        if (row < p.M && col < p.N && col >= p.store_n0) p.C[(long)row * p.ldc + (col - p.store_n0)] = acc[i][j][e] + bv;
                     }
                 }
             }
@@ -1497,7 +1497,7 @@ __global__ __launch_bounds__(256) void pw_tn_reduce_many_kernel(const TnReduceJo
 
 template <int T1, int T2, int NP = 3>
 int launch_tn(const TnArgs &a, int S, hipStream_t st) {
-    const int N1 = a.N1a + a.N1b;
+    const int N1 = a.N1a + a.N1b + a.ones;            // (the ones row may open a tile of its own: N1a + N1b a multiple of the tile)
     const dim3 grid(((N1 + 64 * T1 - 1) / (64 * T1)) * ((a.N2 + 64 * T2 - 1) / (64 * T2)), S);
     hipLaunchKernelGGL((pw_tn_kernel<T1, T2, NP>), grid, dim3(256), 0, st, a);
     FSG_CHECK_LAUNCH("fsg_pw_tn_f32");
@@ -1664,6 +1664,8 @@ extern "C" int fsg_pw_rowgemm_f32(const fsg_pw_rowgemm_args *a, int pro, int epi
     const int key = pro * 1000 + epi * 10 + tile;
 #define PW_CASE(PRO, EPI, TILE, WMv, WNv) \
     case (PRO) * 1000 + (EPI) * 10 + (TILE): return launch_rowgemm<WMv, WNv, PRO, EPI>(k, st, "fsg_pw_rowgemm_f32")
+    // (tests/pw_oracle.py: instantiated_combinations() reads this table -- one `PW_CASE(PRO, EPI, tile, WM, WN);` per line, the
+    //  hand-written one as `case PRO * 1000 + (EPI) * 10 + tile:` -- and tests/test_pw_oracle_cpu.py pins their number)
     switch (key) {
         PW_CASE(PRO_NONE, PW_STORE, 1, 2, 2);
         PW_CASE(PRO_NONE, PW_STORE, 2, 1, 2);

@@ -2719,7 +2719,8 @@ def test_seg_head_fused_vs_fp64_and_unfused(fsg, device, B, Npts, train):
     """The fused DGCNN-seg head (functional.seg_head: csrc/pointwise.hip) against the same head in float64 torch ops and
     against the round-2 path (vendor GEMMs + fsg_bn_act stages): logits 1e-4 of their scale, gradients of the input rows and
     of all 14 parameters 2e-3 in norm (and no worse than 3x the unfused path's own error), running statistics 1e-4.
-    Reference: models/dgcnn.py:123-162,282-323."""
+    Reference: models/dgcnn.py:123-162,282-323.  The members of the family are tested one by one against fp64 (per output, relative to
+    the sum of absolute summands) in tests/test_pw_family_gpu.py."""
     from fissure_segmentation_amd.models.dgcnn import DGCNNSeg
     F_hip = fsg.functional
     torch.manual_seed(1000 + B + Npts)
