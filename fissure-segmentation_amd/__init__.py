@@ -35,6 +35,7 @@ def install_reference_aliases():
         "data_processing.fissure_enhancement": ".data_processing.fissure_enhancement",
         "data_processing.random_walk": ".data_processing.random_walk", "data_processing.find_lobes": ".data_processing.find_lobes",
         "utils.image_utils": ".utils.image_utils", "utils.general_utils": ".utils.general_utils",
+        "utils.image_ops": ".utils.image_ops",
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)

@@ -136,11 +136,20 @@ SIGNATURES = {
     "fsg_random_walk_iterate": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, ctypes.c_size_t, _P, _P, _P], _I),
     "fsg_random_walk_finish": ([_I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P], _I),
     "fsg_lobes_to_fissures_u8": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_bits_pack_u8": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_bits_unpack_u8": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_bits_window": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_ball_dilate_bits": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_cc_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
+    "fsg_cc_label_bits": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_component_stats_i32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_relabel_lut_i32": ([_P, _I, _L, _P, _I, _P, _I, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync
     _fn.argtypes, _fn.restype = _args, _res
 
+MORPH_MAX_RADIUS = 8   # csrc/morphology.hip: MAXR
 RW_BINARY, RW_INTENSITY, RW_MAX_LABELS = 0, 1, 8   # include/fsg_hip.h: FSG_RW_*; csrc/random_walk.hip builds K = 1..8
 KNN_FIX_DIAG, KNN_DROP_FIRST, KNN_FORCE_ROWS, KNN_FORCE_MFMA, KNN_MAX_K = 1, 2, 4, 8, 64
 # debug / cross-check bits of the kNN `flags` (csrc/knn_internal.h has the meanings; any other bit is rejected by the library)

@@ -1,8 +1,10 @@
 """Lobe filling and lobes-to-fissures with the reference's names (data_processing/find_lobes.py:17-92), tensors in, tensors
 out: no SimpleITK.  Convert an image with `torch.from_numpy(sitk.GetArrayFromImage(img).astype(int))` on the way in and
-`GetImageFromArray(t.cpu().numpy())` + `CopyInformation` on the way out, as the reference does around the same calls.  The
-connected-component and marching-cubes parts of the reference's module (find_lobes, compute_surface_mesh_marching_cubes) are
-not here."""
+`GetImageFromArray(t.cpu().numpy())` + `CopyInformation` on the way out, as the reference does around the same calls.
+`find_lobes` (:95-177) goes from fissures back to lobes with the ball morphology and connected components of
+csrc/morphology.hip; the marching-cubes part of the reference's module (compute_surface_mesh_marching_cubes) is not here, so
+the mesh list that find_lobes returns is empty."""
+import numpy as np
 import torch
 
 from .. import functional as F_hip
@@ -21,3 +23,67 @@ def lobes_to_fissures(lobes: torch.Tensor, mask: torch.Tensor, device=None, **so
         lobes, mask = lobes.to(device), mask.to(device)
     lobes_filled = F_hip.random_walk_fill(lobes, mask, **solver)
     return F_hip.lobes_to_fissures_labels(lobes_filled), lobes_filled.long()
+
+
+_BALL4 = 389   # voxels of the radius-4 ball
+
+
+def find_lobes(fissure_seg: torch.Tensor, lung_mask: torch.Tensor, exclude_rhf: bool = False):
+    """find_lobes.py:95-177 for tensors: fissure labels and a lung mask (D, H, W) -> (lobes, [], success).  The steps are
+    the reference's, each SimpleITK filter replaced by its bit-plane launch (the volume stays in bit planes from the two
+    packs to the component labels):
+      not_lobes = not erode(lung, 2, boundary = foreground) or (fissures != 0)      :114-119 (label 3 dropped first if exclude_rhf)
+      not_lobes = dilate(closing(not_lobes, 2), 2)                                  :122-123
+      lobes_mask = opening(not not_lobes, 4)                                        :127-128
+      components with connectivity 6                                                :130-132
+    Fewer than 4 (exclude_rhf) or 5 components: (the component image int32, [], False), as the reference returns it.
+    Otherwise the largest 4 or 5 (ties: the smaller component label first) are renumbered from their centroids (:156-177):
+    smaller x is right; right lobes by z: lowest 1, highest 2, (5 lobes) middle 5; left lobes: lower 3, higher 4.  Centroids
+    are compared in fp64 from the exact integer sums.  -> (lobes int64, [], True); the list would hold the marching-cubes
+    meshes, which are not built here.  One host read: the count and the statistics of the `target` largest components, which
+    are picked on the device.  The statistics table needs no count from the host: every voxel of an opening by the radius-4 ball
+    lies in a whole ball of set voxels, the ball is 6-connected, and the balls of two components are disjoint, so there are at
+    most D H W / 389 components."""
+    if fissure_seg.dim() != 3 or fissure_seg.shape != lung_mask.shape:
+        raise ValueError(f"find_lobes: fissure_seg {tuple(fissure_seg.shape)} and lung_mask {tuple(lung_mask.shape)} must be one "
+                         f"(D, H, W) shape")
+    if fissure_seg.is_floating_point() or lung_mask.is_floating_point():
+        raise ValueError(f"find_lobes: expected bool or integer volumes, got {fissure_seg.dtype} and {lung_mask.dtype}")
+    F_hip._need_gpu(fissure_seg, lung_mask)
+    target = 4 if exclude_rhf else 5
+    with torch.no_grad():
+        W = fissure_seg.shape[-1]
+        fis = fissure_seg[None]
+        if exclude_rhf:
+            fis = torch.where(fis == 3, torch.zeros_like(fis), fis)
+        r2, r4 = (2, 2, 2), (4, 4, 4)
+        # not erode(lung, border 1) = dilate(not lung, border 0): one launch, the NOTs inside it
+        not_lobes = F_hip._bits_dilate(F_hip._pack_bits(lung_mask[None]), W, r2, border=0, inv_in=True) | F_hip._pack_bits(fis)
+        not_lobes = F_hip._bits_closing(not_lobes, W, r2)
+        lobes_mask = F_hip._bits_dilate(not_lobes, W, r2, border=0, inv_out=True)
+        lobes_mask = F_hip._bits_opening(lobes_mask, W, r4)
+        labels, n_dev = F_hip._cc_bits(lobes_mask, W, 6)
+        cap = max(fissure_seg.numel() // _BALL4, 1)
+        stats = F_hip._stats_device(labels, cap)[0]                            # (cap, 4); the labels past n hold zeros
+        k = min(target, cap)
+        top = torch.sort(stats[:, 0], descending=True, stable=True).indices[:k]   # by size descending, ties by the smaller label
+        host = torch.cat([n_dev.long(), top, stats[top].reshape(-1)]).cpu().numpy()   # the one host read
+        n = int(host[0])
+        if n < target:
+            return labels[0], [], False
+        order, st = host[1:1 + target], host[1 + target:].reshape(target, 4)   # old labels - 1 of the sorted labels 1..target
+        centroids = st[:, 1:].astype(np.float64) / st[:, :1].astype(np.float64)   # (z, y, x)
+        sort_by_x = np.argsort(centroids[:, 2], kind="stable")
+        num_right = 2 if exclude_rhf else 3
+        right, left = sort_by_x[:num_right], sort_by_x[num_right:]
+        new = np.zeros(target, np.int64)
+        left_z = np.argsort(centroids[left, 0], kind="stable")
+        new[left[left_z[0]]], new[left[left_z[1]]] = 3, 4
+        right_z = np.argsort(centroids[right, 0], kind="stable")
+        new[right[right_z[0]]], new[right[right_z[-1]]] = 1, 2
+        if not exclude_rhf:
+            new[right[right_z[1]]] = 5
+        lut = np.zeros(n + 1, np.int32)
+        lut[order + 1] = new
+        lobes = F_hip._apply_lut(labels, torch.from_numpy(lut).to(labels.device)[None], torch.int64)
+    return lobes[0], [], True

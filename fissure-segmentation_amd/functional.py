@@ -2814,3 +2814,238 @@ def lobes_to_fissures_labels(lobes_filled):
         with torch.cuda.device(lc.device):
             _lib.call("fsg_lobes_to_fissures_u8", _p(lc), B, D, H, W, hi, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------ ball morphology, connected components (csrc/morphology.hip)
+def _radius3(radius):
+    """an int or three ints (rz, ry, rx), each 0..8"""
+    if isinstance(radius, int) and not isinstance(radius, bool):
+        r = (radius,) * 3
+    else:
+        r = tuple(radius) if isinstance(radius, (tuple, list)) else ()
+    if len(r) != 3 or any(not isinstance(x, int) or isinstance(x, bool) for x in r):
+        raise ValueError(f"radius must be an int or three ints (rz, ry, rx), got {radius!r}")
+    if any(x < 0 or x > _lib.MORPH_MAX_RADIUS for x in r):
+        raise ValueError(f"radius {r} outside 0..{_lib.MORPH_MAX_RADIUS}")
+    return r
+
+
+def ball_offsets(radius):
+    """the offsets (n, 3) int64 (dz, dy, dx), in raster order, of the ball structuring element of per-axis radius
+    (rz, ry, rx): sum_i (o_i / (r_i + 0.5))^2 <= 1 (an axis of radius 0 contributes only 0) -- the definition used here in
+    place of sitk.sitkBall (parity with SimpleITK is unpinned).  Decided in integers: with m = 2 r + 1 the
+    test is 4 sum_i o_i^2 prod_{j != i} m_j^2 <= prod_j m_j^2, whose sides have different parity."""
+    rz, ry, rx = _radius3(radius)
+    mz, my, mx = (2 * rz + 1) ** 2, (2 * ry + 1) ** 2, (2 * rx + 1) ** 2
+    offs = [(dz, dy, dx) for dz in range(-rz, rz + 1) for dy in range(-ry, ry + 1) for dx in range(-rx, rx + 1)
+            if 4 * (dz * dz * my * mx + dy * dy * mz * mx + dx * dx * mz * my) <= mz * my * mx]
+    return torch.tensor(offs, dtype=torch.int64)
+
+
+def _binary_volume(vol, what):
+    """(D, H, W) or (B, D, H, W), bool or integer -> the tensor as (B, D, H, W) and whether it came without a batch axis"""
+    if vol.dim() not in (3, 4) or vol.is_floating_point() or vol.is_complex():
+        raise ValueError(f"{what}: expected a bool or integer volume (D, H, W) or (B, D, H, W), got {tuple(vol.shape)} {vol.dtype}")
+    if vol.numel() == 0:
+        raise ValueError(f"{what}: empty volume {tuple(vol.shape)}")
+    _need_gpu(vol)
+    return (vol[None] if vol.dim() == 3 else vol), vol.dim() == 3
+
+
+def _pack_bits(v4, value=None):
+    """(B, D, H, W) bool / integer on the device -> bit plane (B, D, H, ceil(W / 64)) int64: voxel != 0, or == value (0..255
+    on a uint8 volume)"""
+    if v4.dtype == torch.bool:
+        src = v4.contiguous().view(torch.uint8)
+    elif v4.dtype == torch.uint8:
+        src = v4.contiguous()
+    elif value is None:
+        src = (v4 != 0).contiguous().view(torch.uint8)       # (a comparison keeps the strides of a permuted input)
+    else:
+        src, value = (v4 == value).contiguous().view(torch.uint8), None
+    B, D, H, W = src.shape
+    bits = torch.empty(B, D, H, (W + 63) // 64, dtype=torch.int64, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.call("fsg_bits_pack_u8", _p(src), B, D, H, W, -1 if value is None else int(value), _p(bits), _stream())
+    return bits
+
+
+def _unpack_bits(bits, W):
+    B, D, H, _ = bits.shape
+    out = torch.empty(B, D, H, W, dtype=torch.uint8, device=bits.device)
+    with torch.cuda.device(bits.device):
+        _lib.call("fsg_bits_unpack_u8", _p(bits), B, D, H, W, _p(out), _stream())
+    return out.view(torch.bool)   # the kernel writes 0 or 1: a view, not a pass
+
+
+def _bits_dilate(bits, W, r, border=0, inv_in=False, inv_out=False):
+    """one launch on a bit plane: [not] dilate([not] bits) with the ball of radius r = (rz, ry, rx) and the border value"""
+    B, D, H, _ = bits.shape
+    out = torch.empty_like(bits)
+    with torch.cuda.device(bits.device):
+        _lib.call("fsg_ball_dilate_bits", _p(bits), B, D, H, W, r[0], r[1], r[2], int(border), int(inv_in), int(inv_out), _p(out),
+                  _stream())
+    return out
+
+
+def _bits_erode(bits, W, r, border=1):
+    """erosion = the complement of the dilation of the complement with the complementary border (the ball is symmetric)"""
+    return _bits_dilate(bits, W, r, border=1 - int(border), inv_in=True, inv_out=True)
+
+
+def _bits_window(bits, W, offset, out_dhw):
+    """the box of size out_dhw whose corner sits at `offset` of the volume (negative: padding with 0), in bit-plane space"""
+    B, D, H, _ = bits.shape
+    Do, Ho, Wo = out_dhw
+    out = torch.empty(B, Do, Ho, (Wo + 63) // 64, dtype=torch.int64, device=bits.device)
+    with torch.cuda.device(bits.device):
+        _lib.call("fsg_bits_window", _p(bits), B, D, H, W, offset[0], offset[1], offset[2], Do, Ho, Wo, _p(out), _stream())
+    return out
+
+
+def _bits_closing(bits, W, r):
+    """closing on the zero-extended infinite grid, cropped: the dilation is also formed r voxels outside the volume (the
+    plane is padded in bit space, never as bytes), so the erosion sees what it would on the infinite grid"""
+    B, D, H, _ = bits.shape
+    Wp = W + 2 * r[2]
+    padded = _bits_window(bits, W, (-r[0], -r[1], -r[2]), (D + 2 * r[0], H + 2 * r[1], Wp))
+    closed = _bits_erode(_bits_dilate(padded, Wp, r, border=0), Wp, r, border=0)
+    return _bits_window(closed, Wp, r, (D, H, W))
+
+
+def _bits_opening(bits, W, r):
+    """dilate(erode(x, border 0), border 0): what the zero-extended infinite grid gives, cropped"""
+    return _bits_dilate(_bits_erode(bits, W, r, border=0), W, r, border=0)
+
+
+def _morph_public(vol, radius, what, op):
+    r = _radius3(radius)
+    v4, squeeze = _binary_volume(vol, what)
+    with torch.no_grad():
+        out = _unpack_bits(op(_pack_bits(v4), v4.shape[-1], r), v4.shape[-1])
+    return out[0] if squeeze else out
+
+
+def _border01(border):
+    if border not in (0, 1, False, True):
+        raise ValueError(f"border must be 0 or 1, got {border!r}")
+    return int(border)
+
+
+def binary_dilate(vol, radius, border=0):
+    """sitk.BinaryDilate with a ball (find_lobes.py:123): vol (D, H, W) or (B, D, H, W), bool or integer (nonzero = set) ->
+    bool.  radius an int or (rz, ry, rx), each 0..8, the ball of `ball_offsets`; `border` is the value outside the volume."""
+    b = _border01(border)
+    return _morph_public(vol, radius, "binary_dilate", lambda bits, W, r: _bits_dilate(bits, W, r, border=b))
+
+
+def binary_erode(vol, radius, border=1):
+    """sitk.BinaryErode with a ball (find_lobes.py:118; its boundary counts as foreground, hence border = 1)"""
+    b = _border01(border)
+    return _morph_public(vol, radius, "binary_erode", lambda bits, W, r: _bits_erode(bits, W, r, border=b))
+
+
+def binary_closing(vol, radius):
+    """sitk.BinaryMorphologicalClosing with a ball (find_lobes.py:122) on the zero-extended infinite grid, cropped"""
+    return _morph_public(vol, radius, "binary_closing", _bits_closing)
+
+
+def binary_opening(vol, radius):
+    """sitk.BinaryMorphologicalOpening with a ball (find_lobes.py:128) on the zero-extended infinite grid, cropped"""
+    return _morph_public(vol, radius, "binary_opening", _bits_opening)
+
+
+def _cc_bits(bits, W, connectivity):
+    """bit plane -> (labels (B, D, H, W) int32, n (B) int32 on the device): no host read"""
+    B, D, H, _ = bits.shape
+    dev = bits.device
+    nbytes = _lib.lib.fsg_cc_workspace_bytes(B, D, H, W)
+    ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+    labels = torch.empty(B, D, H, W, dtype=torch.int32, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("fsg_cc_label_bits", _p(bits), B, D, H, W, int(connectivity), _p(labels), _p(n), _p(ws), nbytes, _stream())
+    return labels, n
+
+
+def _stats_device(labels4, cap):
+    """(B, D, H, W) int32 labels -> (B, cap, 4) int64 on the device: count, sum z, sum y, sum x of the labels 1..cap"""
+    B, D, H, W = labels4.shape
+    stats = torch.empty(B, cap, 4, dtype=torch.int64, device=labels4.device)
+    with torch.cuda.device(labels4.device):
+        _lib.call("fsg_component_stats_i32", _p(labels4), B, D, H, W, int(cap), _p(stats), _stream())
+    return stats
+
+
+def _labels_volume(labels, what):
+    if labels.dim() not in (3, 4) or labels.dtype != torch.int32:
+        raise ValueError(f"{what}: expected int32 labels (D, H, W) or (B, D, H, W), got {tuple(labels.shape)} {labels.dtype}")
+    _need_gpu(labels)
+    return (labels[None] if labels.dim() == 3 else labels).contiguous(), labels.dim() == 3
+
+
+def _count(n, B, what):
+    """n as given to component_stats / relabel_by_size: an int, or one int per item -> the capacity max(n, 1)"""
+    ns = [n] if isinstance(n, int) else list(n)
+    if any(not isinstance(x, int) or x < 0 for x in ns) or len(ns) not in (1, B):
+        raise ValueError(f"{what}: n must be a non-negative int (or one per item), got {n!r}")
+    return max(max(ns), 1)
+
+
+def connected_components(mask, connectivity=6):
+    """sitk.ConnectedComponentImageFilter (find_lobes.py:130-132; 6 is its default, fullyConnected is 26): mask (D, H, W) or
+    (B, D, H, W), bool or integer (nonzero = object) -> (labels int32, n).  Components are numbered 1..n in raster order of
+    their first voxel, as scipy.ndimage.label numbers them; n is an int, or a list of B ints for a batch (one host read)."""
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    v4, squeeze = _binary_volume(mask, "connected_components")
+    with torch.no_grad():
+        labels, n = _cc_bits(_pack_bits(v4), v4.shape[-1], connectivity)
+        n = n.tolist()
+    return (labels[0], n[0]) if squeeze else (labels, n)
+
+
+def component_stats(labels, n):
+    """sizes and index sums of the labels 1..n (RelabelComponentImageFilter's sizes, LabelShapeStatisticsImageFilter's
+    centroids before the division; find_lobes.py:141-158): labels int32 (D, H, W) -> (sizes (n) int64, index_sums (n, 3)
+    int64 in (z, y, x) order), on the device, exact; a batch (B, D, H, W) with n = max over the items -> (B, n), (B, n, 3).
+    No host read."""
+    l4, squeeze = _labels_volume(labels, "component_stats")
+    cap = _count(n, l4.shape[0], "component_stats")
+    n_max = max([n] if isinstance(n, int) else list(n))
+    with torch.no_grad():
+        stats = _stats_device(l4, cap)[:, :n_max]
+    sizes, sums = stats[..., 0], stats[..., 1:]
+    return (sizes[0], sums[0]) if squeeze else (sizes, sums)
+
+
+def _size_order_lut(sizes):
+    """(B, n) int64 sizes -> lut (B, n + 1) int32: old label -> rank by size, largest first, ties by the smaller label (a
+    stable sort)"""
+    B, n = sizes.shape
+    order = torch.sort(sizes, dim=1, descending=True, stable=True).indices           # order[b, new - 1] = old - 1
+    lut = torch.zeros(B, n + 1, dtype=torch.int32, device=sizes.device)
+    lut.scatter_(1, order + 1, torch.arange(1, n + 1, dtype=torch.int32, device=sizes.device).expand(B, n).contiguous())
+    return lut
+
+
+def _apply_lut(l4, lut, out_dtype=torch.int32):
+    B = l4.shape[0]
+    out = torch.empty(l4.shape, dtype=out_dtype, device=l4.device)
+    lut = lut.contiguous()
+    with torch.cuda.device(l4.device):
+        _lib.call("fsg_relabel_lut_i32", _p(l4), B, l4[0].numel(), _p(lut), lut.shape[1], _p(out), int(out_dtype == torch.int64),
+                  _stream())
+    return out
+
+
+def relabel_by_size(labels, n):
+    """sitk.RelabelComponentImageFilter with SortByObjectSize (find_lobes.py:141-143): label 1 becomes the largest component;
+    equal sizes keep the order of their labels (this rule is ours, ITK's is unpinned).  labels int32 with values 0..n -> int32.
+    Items of a batch whose count is below n have empty trailing labels, which sort last.  No host read."""
+    l4, squeeze = _labels_volume(labels, "relabel_by_size")
+    cap = _count(n, l4.shape[0], "relabel_by_size")
+    with torch.no_grad():
+        lut = _size_order_lut(_stats_device(l4, cap)[..., 0])
+        out = _apply_lut(l4, lut)
+    return out[0] if squeeze else out

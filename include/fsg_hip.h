@@ -922,6 +922,42 @@ int fsg_random_walk_finish(int B, int K, int D, int H, int W, const void *worksp
 int fsg_lobes_to_fissures_u8(const uint8_t *lobes, int B, int D, int H, int W, int n_lobes, uint8_t *fissures,
                              fsg_stream_t stream);
 
+/* Binary morphology with ball structuring elements, connected components and component statistics on bit planes
+ * (csrc/morphology.hip).  Replaces the SimpleITK filters of find_lobes (data_processing/find_lobes.py:114-158: BinaryErode,
+ * BinaryDilate, BinaryMorphologicalClosing, BinaryMorphologicalOpening, ConnectedComponentImageFilter,
+ * RelabelComponentImageFilter, LabelShapeStatisticsImageFilter) and of multiple_objects_morphology (utils/image_ops.py:31-47:
+ * DilateObjectMorphology, ErodeObjectMorphology).  Volumes are (B, D, H, W), DEVICE, contiguous.
+ *
+ * A bit plane of a binary volume is (B, D, H, WW) 64-bit words, WW = ceil(W / 64): bit i of word j of a row is voxel
+ *   x = 64 j + i; the bits past W are always 0.  `pack` sets a bit where the byte is nonzero (value = -1) or equals `value`
+ *   (0..255), `unpack` writes bytes 0 / 1.  `window` copies a box: out(z, y, x) = in(z + oz, y + oy, x + ox) where that lies
+ *   inside `in` and 0 elsewhere -- negative offsets pad, positive ones crop; in and out must differ.
+ * Ball dilation: the structuring element is the set of offsets o with sum_i (o_i / (r_i + 0.5))^2 <= 1, r = (rz, ry, rx), each
+ *   0..8 (19, 81, 179, 389 voxels for isotropic r = 1..4); `border` (0 / 1) is the value outside the volume.  inv_in complements
+ *   the input inside the volume before, inv_out the result after, so erosion with border b is inv_in = inv_out = 1 with
+ *   border 1 - b.  One launch; in and out must differ.  Closing / opening are compositions of these.
+ * Connected components of a bit plane, connectivity 6, 18 or 26 -> labels (B, D, H, W) int32, 0 = background, components
+ *   numbered 1..n in raster order of their first voxel (scipy.ndimage.label's numbering), n (B) int32 DEVICE.  Union-find by
+ *   smallest voxel index with atomicMin: the same input gives the same labels, an item's labels do not depend on the batch.
+ *   workspace: the query below (4 bytes per voxel + 4 per 1024 voxels), 8-byte aligned.
+ * Component statistics: stats (B, cap, 4) int64 = voxel count and the sums of the z, y, x indices of the labels 1..cap (a
+ *   larger label is left out), zeroed by the call, integer atomics (exact).
+ * Relabel: out[i] = lut[b][labels[i]] (0 for a label outside 0..lut_len-1); lut (B, lut_len) int32; out int32 or int64.
+ * Bad arguments (a radius outside 0..8, a connectivity other than 6 / 18 / 26, a NULL pointer, a short workspace, 2^31 or more
+ *   voxels) are FSG_ERR_ARG. */
+int fsg_bits_pack_u8(const uint8_t *vol, int B, int D, int H, int W, int value, uint64_t *bits, fsg_stream_t stream);
+int fsg_bits_unpack_u8(const uint64_t *bits, int B, int D, int H, int W, uint8_t *vol, fsg_stream_t stream);
+int fsg_bits_window(const uint64_t *in, int B, int Di, int Hi, int Wi, int oz, int oy, int ox, int Do, int Ho, int Wo,
+                    uint64_t *out, fsg_stream_t stream);
+int fsg_ball_dilate_bits(const uint64_t *in, int B, int D, int H, int W, int rz, int ry, int rx, int border, int inv_in,
+                         int inv_out, uint64_t *out, fsg_stream_t stream);
+size_t fsg_cc_workspace_bytes(int B, int D, int H, int W);
+int fsg_cc_label_bits(const uint64_t *bits, int B, int D, int H, int W, int connectivity, int32_t *labels, int32_t *n,
+                      void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+int fsg_component_stats_i32(const int32_t *labels, int B, int D, int H, int W, int cap, int64_t *stats, fsg_stream_t stream);
+int fsg_relabel_lut_i32(const int32_t *labels, int B, int64_t n_per_item, const int32_t *lut, int lut_len, void *out,
+                        int out_is_i64, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

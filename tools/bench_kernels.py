@@ -388,3 +388,108 @@ if "rw" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "morph" in which:
+    # ball morphology and connected components on bit planes (csrc/morphology.hip) beside (a) the torch composition on the same
+    # device -- conv3d of the fp16 volume with the ball as kernel, thresholded, as the reference's own dilation in
+    # lobes_to_fissures does; there is no torch composition of connected components, so that stage has the host baseline only --
+    # and (b) scipy.ndimage on the host.  Input: the synthetic two-lung volume of the tests scaled to the shape.
+    import json, time
+    import numpy as np
+    import morphology_oracle as mo
+    from fissure_segmentation_amd.data_processing import find_lobes as fl
+    shapes = [tuple(int(v) for v in a.split("x")) for a in os.environ.get("FSG_MORPH_SHAPES", "128x128x128,256x256x320").split(",")]
+    with_host = os.environ.get("FSG_MORPH_HOST", "1") != "0"
+
+    def wall(fn, reps=5):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); out = fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        return statistics.median(ts), out
+
+    def peak(fn):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn(); torch.cuda.synchronize()
+        del out
+        return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    def host(fn):
+        t0 = time.perf_counter(); out = fn()
+        return (time.perf_counter() - t0) * 1e6, out
+
+    def t_dilate(x, r, border=0):   # x (1, 1, D, H, W) fp16 0 / 1
+        k = torch.from_numpy(mo.ball(r)).to(dev, torch.float16)[None, None]
+        xp = torch.nn.functional.pad(x, (r,) * 6, value=float(border))
+        return (torch.nn.functional.conv3d(xp, k) > 0).to(torch.float16)
+
+    def t_erode(x, r, border=1):
+        return 1 - t_dilate(1 - x, r, 1 - border)
+
+    def t_closing(x, r):
+        p = torch.nn.functional.pad(x, (r,) * 6)
+        return t_erode(t_dilate(p, r), r, 0)[..., r:-r, r:-r, r:-r]
+
+    def t_opening(x, r):
+        return t_dilate(t_erode(x, r, 0), r)
+
+    lines = []
+    for shape in shapes:
+        lung, fis = mo.lung_volume(shape)
+        tl, tf = torch.from_numpy(lung).to(dev), torch.from_numpy(fis).to(dev)
+        W = shape[-1]
+        not_lobes_np = ~mo.erode(lung, 2, 1) | (fis != 0) if with_host else None
+        bits = F._pack_bits(tl[None])
+        nl_bits = F._bits_dilate(bits, W, (2, 2, 2), border=0, inv_in=True) | F._pack_bits(tf[None])
+        nl16 = F._unpack_bits(nl_bits, W)[None].to(torch.float16)
+        lm_bits = F._bits_dilate(F._bits_closing(nl_bits, W, (2, 2, 2)), W, (2, 2, 2), border=0, inv_out=True)
+        lm16 = F._unpack_bits(lm_bits, W)[None].to(torch.float16)
+        open_bits = F._bits_opening(lm_bits, W, (4, 4, 4))
+        rec = dict(kernel="ball morphology + connected components on bit planes", shape="x".join(map(str, shape)),
+                   voxels=int(np.prod(shape)))
+        stages = {
+            "closing_r2": (lambda: F._bits_closing(nl_bits, W, (2, 2, 2)), lambda: t_closing(nl16, 2)),
+            "opening_r4": (lambda: F._bits_opening(lm_bits, W, (4, 4, 4)), lambda: t_opening(lm16, 4)),
+            "components": (lambda: F._cc_bits(open_bits, W, 6), None),
+            "find_lobes": (lambda: fl.find_lobes(tf, tl), None),
+        }
+        for name, (fused, comp) in stages.items():
+            fused(); fused()
+            us, out = wall(fused)
+            rec[f"{name}_hip_us"] = round(us, 1)
+            rec[f"{name}_hip_peak_MiB"] = peak(fused)
+            if comp is not None:
+                comp(); ref = comp()
+                same = torch.equal(F._unpack_bits(out, W)[None], ref > 0)
+                tus, _ = wall(comp, reps=3)
+                rec[f"{name}_torch_us"] = round(tus, 1)
+                rec[f"{name}_torch_peak_MiB"] = peak(comp)
+                rec[f"{name}_speedup_vs_torch"] = round(tus / us, 2)
+                rec[f"{name}_equals_torch"] = bool(same)
+            print("morph: %s %s done" % (rec["shape"], name), file=sys.stderr, flush=True)
+        rec["find_lobes_components"] = int(F._cc_bits(open_bits, W, 6)[1][0])
+        # find_lobes as a torch composition: its four morphology steps (the component stage has none)
+        def t_chain():
+            nl = t_dilate(t_closing(torch.maximum(1 - t_erode(tl[None, None].to(torch.float16), 2, 1),
+                                                   (tf != 0)[None, None].to(torch.float16)), 2), 2)
+            return t_opening(1 - nl, 4)
+        t_chain()
+        tus, ref = wall(t_chain, reps=3)
+        rec["find_lobes_morphology_torch_us"] = round(tus, 1)
+        rec["find_lobes_morphology_torch_peak_MiB"] = peak(t_chain)
+        rec["find_lobes_morphology_equals_torch"] = bool(torch.equal(F._unpack_bits(open_bits, W)[None], ref > 0))
+        if with_host:
+            hus, c_np = host(lambda: mo.closing(not_lobes_np, 2)); rec["closing_r2_scipy_us"] = round(hus, 1)
+            lm_np = ~mo.dilate(c_np, 2, 0)
+            hus, o_np = host(lambda: mo.opening(lm_np, 4)); rec["opening_r4_scipy_us"] = round(hus, 1)
+            hus, (lab_np, n_np) = host(lambda: mo.label(o_np, 6)); rec["components_scipy_us"] = round(hus, 1)
+            hus, (lobes_np, ok) = host(lambda: mo.find_lobes(fis, lung)); rec["find_lobes_scipy_us"] = round(hus, 1)
+            got, _, ok_hip = fl.find_lobes(tf, tl)
+            rec["find_lobes_equals_scipy"] = bool(ok == ok_hip and np.array_equal(got.cpu().numpy(), lobes_np))
+            rec["components_equal_scipy"] = bool(np.array_equal(F._cc_bits(open_bits, W, 6)[0][0].cpu().numpy(), lab_np))
+        print("MORPH " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    out_path = os.environ.get("FSG_MORPH_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
