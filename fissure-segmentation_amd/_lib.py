@@ -144,6 +144,11 @@ SIGNATURES = {
     "fsg_cc_label_bits": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_component_stats_i32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
     "fsg_relabel_lut_i32": ([_P, _I, _L, _P, _I, _P, _I, _P], _I),
+    "fsg_mesh_reg_workspace_bytes": ([_I, _I], ctypes.c_size_t),
+    "fsg_mesh_reg_f32": ([_P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_mesh_sample_workspace_bytes": ([_I, _I], ctypes.c_size_t),
+    "fsg_mesh_sample_f32": ([_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_mesh_sample_bwd_f32": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

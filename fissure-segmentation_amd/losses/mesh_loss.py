@@ -12,7 +12,10 @@ decoders is out of scope), so the surface SAMPLING stays with the caller:
   regularisers (edge length, normal consistency, uniform Laplacian) come from pytorch3d exactly as in the reference.
 
 The regularisers need mesh connectivity; without pytorch3d a positive weight on any of them raises NotImplementedError at
-CONSTRUCTION (never a silent zero, never a failure after the run has been set up).  Returns `(loss, components)` like the reference (model_trainer.py:180-185 unpacks it)."""
+CONSTRUCTION (never a silent zero, never a failure after the run has been set up).  Returns `(loss, components)` like the reference (model_trainer.py:180-185 unpacks it).
+
+`RegularizedMeshLossHIP` (below) is the complete loss without pytorch3d, on `fissure_segmentation_amd.mesh.Meshes`: sampling and
+the three regularisers run on csrc/mesh.hip.  It is a separate, opt-in class; `RegularizedMeshLoss` is unchanged."""
 from torch import nn
 
 from .chamfer_loss import chamfer_distance
@@ -91,4 +94,59 @@ class RegularizedMeshLoss(nn.Module):
                 term = getattr(p3[0], fn)(mesh_prediction, **kw)
                 components[name] = term
                 loss = loss + w * term
+        return loss, components
+
+
+class RegularizedMeshLossHIP(nn.Module):
+    """The reference's RegularizedMeshLoss (losses/mesh_loss.py:7-64) complete, on `fissure_segmentation_amd.mesh.Meshes`:
+    Chamfer on `n_samples` surface samples per mesh (csrc/mesh.hip sampler + csrc/chamfer.hip) plus the edge-length,
+    normal-consistency and uniform-Laplacian terms of the prediction from one launch (fsg_mesh_reg_f32).  Same constructor,
+    same `(loss, components)` and component names; `generator` (a torch.Generator on the meshes' device) makes the samples
+    reproducible.  The target may also be (B, n, 3) / (B, 3, n) samples or any object with `sample_points(n)`: it only feeds
+    the Chamfer term.  `RegularizedMeshLoss` above and the registry name 'mesh' are unchanged; INTEGRATION.md shows the
+    binding."""
+
+    def __init__(self, w_chamfer=1., w_edge_length=1., w_normal_consistency=0.1, w_laplacian=0.1, n_samples=2048,
+                 generator=None):
+        super().__init__()
+        self.w_chamfer = w_chamfer
+        self.w_edge_length = w_edge_length
+        self.w_normal_consistency = w_normal_consistency
+        self.w_laplacian = w_laplacian
+        self.n_samples = n_samples
+        self.generator = generator
+
+    def _samples(self, mesh):
+        import torch
+        from ..mesh import Meshes
+        if isinstance(mesh, Meshes):
+            return mesh.sample_points(self.n_samples, generator=self.generator)
+        if torch.is_tensor(mesh):
+            pts = mesh.transpose(1, 2) if (mesh.dim() == 3 and mesh.shape[1] == 3 and mesh.shape[2] != 3) else mesh
+            if pts.dim() != 3 or pts.shape[2] != 3:
+                raise ValueError(f"surface samples must be (B, n, 3) or (B, 3, n), got {tuple(mesh.shape)}")
+            return pts
+        if hasattr(mesh, "sample_points"):
+            return mesh.sample_points(self.n_samples)
+        raise TypeError(f"RegularizedMeshLossHIP: cannot draw surface samples from {type(mesh).__name__}: pass Meshes, "
+                        "(B, n, 3) samples or an object with sample_points(n)")
+
+    def forward(self, mesh_prediction, mesh_target):
+        from ..mesh import Meshes, mesh_regularizers
+        if not isinstance(mesh_prediction, Meshes):
+            raise TypeError("RegularizedMeshLossHIP: the prediction must be fissure_segmentation_amd.mesh.Meshes (set "
+                            f"DGCNNFoldingNet.return_meshes = True), got {type(mesh_prediction).__name__}")
+        components = {}
+        loss = 0
+        if self.w_chamfer > 0:      # mesh_loss.py:28-33
+            loss_chamfer, _ = chamfer_distance(self._samples(mesh_prediction), self._samples(mesh_target))
+            components['Chamfer'] = loss_chamfer
+            loss = loss + self.w_chamfer * loss_chamfer
+        weights = (('Edge Length', self.w_edge_length), ('Normal Consistency', self.w_normal_consistency),
+                   ('Laplacian', self.w_laplacian))
+        if any(w > 0 for _, w in weights):      # mesh_loss.py:37-57
+            for (name, w), term in zip(weights, mesh_regularizers(mesh_prediction)):
+                if w > 0:
+                    components[name] = term
+                    loss = loss + w * term
         return loss, components

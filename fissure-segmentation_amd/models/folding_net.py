@@ -1,7 +1,7 @@
 """Point-cloud auto-encoder (DGCNN encoder + folding / deforming decoder) on the HIP path.
 Same classes, arguments and state_dict keys as the reference's models/folding_net.py; the encoder's
-four graph builds + gathers run in libfsg_hip.so.  Mesh output (pytorch3d `Meshes`) is out of scope:
-`decode_mesh=True` uses the mesh-vertex grid of get_plane_mesh but returns the (B,3,m) vertices."""
+four graph builds + gathers run in libfsg_hip.so.  `decode_mesh=True` uses the mesh-vertex grid of get_plane_mesh and
+returns the (B,3,m) vertices; with `DGCNNFoldingNet.return_meshes = True` they come wrapped in `mesh.Meshes`."""
 import torch
 from torch import nn
 
@@ -170,7 +170,11 @@ class DeformingDecoder(Decoder):
 
 
 class DGCNNFoldingNet(LoadableModel):
-    """folding_net.py:42-79."""
+    """folding_net.py:42-79.  `return_meshes` (a class attribute, not a constructor argument: `config` and checkpoints do not
+    know it): when True and the decoder has `decode_mesh`, `forward` wraps the vertices it returns in `mesh.Meshes` with the
+    decoder's faces, as folding_net.py:76-77, 225-226, 285-286 do with pytorch3d's."""
+
+    return_meshes = False
 
     @store_config_args
     def __init__(self, k, n_embedding, shape_type, n_input_points=1024, decode_mesh=True, deform=False,
@@ -188,6 +192,9 @@ class DGCNNFoldingNet(LoadableModel):
     def forward(self, x, return_hidden=False):
         h = self.encoder(x)
         out = self.decoder(h)
+        if self.return_meshes and self.decoder.decode_mesh:
+            from ..mesh import Meshes
+            out = Meshes(out.transpose(1, 2), self.decoder.faces)
         return (out, h) if return_hidden else out
 
     def predict_full_pointcloud(self, pc, sample_points=1024, n_runs=50):

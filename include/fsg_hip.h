@@ -958,6 +958,43 @@ int fsg_component_stats_i32(const int32_t *labels, int B, int D, int H, int W, i
 int fsg_relabel_lut_i32(const int32_t *labels, int B, int64_t n_per_item, const int32_t *lut, int lut_len, void *out,
                         int out_is_i64, fsg_stream_t stream);
 
+/* Mesh regularisers and surface sampling for the PC-AE mesh loss (csrc/mesh.hip).  Replace pytorch3d's mesh_edge_loss,
+ * mesh_normal_consistency, mesh_laplacian_smoothing(method="uniform") and sample_points_from_meshes as
+ * losses/mesh_loss.py:28-57 and data_processing/surface_fitting_optimization.py call them.  All pointers DEVICE.
+ *
+ * A batch is N meshes over one packed vertex array verts (total_verts, 3) fp32.  Topology is built once per face list by the
+ *   caller (fissure_segmentation_amd/mesh.py) and holds LOCAL vertex indices, so the meshes of a shared-face batch point at
+ *   one copy.  desc (N, 8) int32 per mesh: first vertex, vertex count V, first entry of its V + 1 offsets in nbr_off and
+ *   inc_off, first pair, edge count E, pair count P, two unused.  nbr_off[o + i] .. nbr_off[o + i + 1] delimit vertex i's
+ *   neighbours in nbr (ascending, over the unique undirected edges); pairs (., 4) int32 = (v0, v1, a, b): an edge and the
+ *   opposite vertices of two faces sharing it; inc_off likewise delimits vertex i's entries in inc, each 4 * (pair - first
+ *   pair) + role (0..3 = v0, v1, a, b), ascending.
+ * Per mesh, each a mean:  edge = mean over edges |va - vb|^2;  normal = mean over pairs 1 - cos(n0, n1), n0 = (v1 - v0) x
+ *   (a - v0), n1 = -(v1 - v0) x (b - v0), cos = n0 / max(|n0|, 1e-8) . n1 / max(|n1|, 1e-8) (0 without pairs);  laplacian =
+ *   mean over vertices |sum_j v_j / d_i - v_i| (degree 0: |v_i|; gradient 0 where the norm is 0).
+ * -> terms (N, 3) fp32 (edge, normal, laplacian), mean (3) over the meshes, grads (3, total_verts, 3) = d terms[m, t] / d verts
+ *   of mesh m (NULL: not written).  One launch plus a one-workgroup finalize.  Gradients are formed per vertex from the
+ *   incidence lists in list order, sums are fp64 in a fixed order, no atomics: the same input gives the same bits and a mesh's
+ *   numbers do not depend on the rest of the batch.  Any V; meshes of up to 4096 vertices are staged in LDS.
+ * workspace: the query below, 8-byte aligned.  The topology arrays are NOT checked against V (the caller builds them).
+ *
+ * Sampling: sdesc (N, 4) int32 per mesh: first vertex, V, first face in faces (., 3) int32 (LOCAL indices), face count F > 0.
+ *   u (N, n, 3) uniforms in [0, 1).  face = min{ j : C[j] > u0 C[F-1] }, C the inclusive fp64 prefix sum of the fp64 face
+ *   areas in face order (a mesh without area: every face alike, C[j] = j + 1); weights (1 - sqrt u1, sqrt u1 (1 - u2),
+ *   sqrt u1 u2) fp32 -> pts (N, n, 3) = sum_c w_c v[face_c], face (N, n) int32, w (N, n, 3).  Two launches.
+ *   bwd: grad_verts (total_verts, 3) = sum over the mesh's samples, in sample order, of w_c g on the face corners that are the
+ *   vertex (every vertex of every mesh is written); g (N, n, 3).  O(V n) compares per mesh, no sort, no atomics, one launch.
+ * N <= 65535.  Bad shapes, NULL pointers, a short or misaligned workspace are FSG_ERR_ARG before any launch. */
+size_t fsg_mesh_reg_workspace_bytes(int N, int max_V);
+int fsg_mesh_reg_f32(const float *verts, int64_t total_verts, const int32_t *desc, int N, int max_V, const int32_t *nbr_off,
+                     const int32_t *nbr, const int32_t *pairs, const int32_t *inc_off, const int32_t *inc, float *terms,
+                     float *mean, float *grads, void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+size_t fsg_mesh_sample_workspace_bytes(int N, int max_F);
+int fsg_mesh_sample_f32(const float *verts, const int32_t *faces, const int32_t *sdesc, int N, int max_F, const float *u, int n,
+                        float *pts, int32_t *face, float *w, void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+int fsg_mesh_sample_bwd_f32(const float *g, const int32_t *face, const float *w, const int32_t *faces, const int32_t *sdesc,
+                            int N, int max_V, int n, float *grad_verts, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

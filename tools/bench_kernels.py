@@ -493,3 +493,101 @@ if "morph" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "mesh" in which:
+    # mesh regularisers, surface sampler and the whole default mesh loss (csrc/mesh.hip) beside the torch composition of the
+    # same math on the same device (the oracle's fp32 code, tests/mesh_oracle.py, batched over the shared face list), value +
+    # gradient, with the peak extra device memory of both.  B = 32 is the training step of train_pc_ae.py --loss mesh.
+    import json
+    import mesh_oracle as mo
+    from fissure_segmentation_amd.losses.mesh_loss import RegularizedMeshLossHIP
+    from fissure_segmentation_amd.mesh import Meshes, mesh_regularizers, sample_points_from_uniforms
+    from fissure_segmentation_amd.shapes.shape_constructor import get_plane_mesh
+
+    def measure(fn, iters=50, warm=5):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        med, _ = timeit(fn, iters, warm)
+        return round(med, 1), round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 2)
+
+    lines = []
+    n_samples = 2048
+    for B in (32, 1):
+        p, faces = get_plane_mesh(2048, xrange=(-0.3, 0.3), yrange=(-0.3, 0.3))
+        faces = faces.to(dev)
+        verts = torch.cat([p, torch.zeros(len(p), 1)], 1).to(dev)[None].repeat(B, 1, 1)
+        verts = (verts + 0.01 * torch.randn(B, len(p), 3, device=dev)).requires_grad_(True)
+        target = (verts.detach() * 0.9 + 0.02).contiguous()
+        topo = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in mo.brute_topology(faces, len(p)).items()}
+        u = torch.rand(B, n_samples, 3, device=dev)
+        g = torch.randn(B, n_samples, 3, device=dev)
+        fl = faces.long()
+
+        def t_terms(v):        # mesh_oracle.mesh_terms, batched: (B, V, 3) -> three batch means
+            e, pr = topo["edges"], topo["pairs"]
+            edge = (v[:, e[:, 0]] - v[:, e[:, 1]]).square().sum(2).mean(1).mean()
+            v0, ed = v[:, pr[:, 0]], v[:, pr[:, 1]] - v[:, pr[:, 0]]
+            n0, n1 = torch.linalg.cross(ed, v[:, pr[:, 2]] - v0), -torch.linalg.cross(ed, v[:, pr[:, 3]] - v0)
+            normal = (1 - torch.nn.functional.cosine_similarity(n0, n1, dim=2)).mean(1).mean()
+            s = torch.zeros_like(v).index_add(1, topo["src"], v[:, topo["dst"]])
+            lap = (s / topo["deg"].clamp(min=1)[None, :, None] - v).norm(dim=2).mean(1).mean()
+            return edge, normal, lap
+
+        def t_sample(v, u):    # mesh_oracle.sample, batched
+            tri = v[:, fl]
+            area = 0.5 * torch.linalg.cross(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0]).double().norm(dim=2)
+            C = torch.cumsum(area.detach(), 1)
+            face = torch.searchsorted(C, u[:, :, 0].double() * C[:, -1:], right=True).clamp(max=fl.shape[0] - 1)
+            r = u[:, :, 1].sqrt()
+            w = torch.stack([1 - r, r * (1 - u[:, :, 2]), r * u[:, :, 2]], 2)
+            corners = torch.gather(v[:, fl].flatten(2), 1, face[:, :, None].expand(-1, -1, 9)).unflatten(2, (3, 3))
+            return (corners * w[:, :, :, None]).sum(2)
+
+        def t_chamfer(x, y):
+            d = torch.cdist(x, y).square()
+            return d.min(2).values.mean(1).mean() + d.min(1).values.mean(1).mean()
+
+        def hip_reg():
+            e, n, l = mesh_regularizers(Meshes(verts, faces))
+            return torch.autograd.grad(e + 0.1 * n + 0.1 * l, verts)
+
+        def torch_reg():
+            e, n, l = t_terms(verts)
+            return torch.autograd.grad(e + 0.1 * n + 0.1 * l, verts)
+
+        def hip_sample():
+            return torch.autograd.grad(sample_points_from_uniforms(Meshes(verts, faces), u), verts, g)
+
+        def torch_sample():
+            return torch.autograd.grad(t_sample(verts, u), verts, g)
+
+        loss_fn = RegularizedMeshLossHIP()
+
+        def hip_loss():
+            return torch.autograd.grad(loss_fn(Meshes(verts, faces), Meshes(target, faces))[0], verts)
+
+        def torch_loss():
+            e, n, l = t_terms(verts)
+            u1, u2 = torch.rand(B, n_samples, 3, device=dev), torch.rand(B, n_samples, 3, device=dev)
+            c = t_chamfer(t_sample(verts, u1), t_sample(target, u2))
+            return torch.autograd.grad(c + e + 0.1 * n + 0.1 * l, verts)
+
+        for stage, ours, theirs in (("regularisers value+grad", hip_reg, torch_reg), ("sampler fwd+bwd", hip_sample, torch_sample),
+                                    ("default loss fwd+bwd", hip_loss, torch_loss)):
+            rec = dict(kernel="mesh " + stage, B=B, V=len(p), F=int(faces.shape[0]), n_samples=n_samples)
+            rec["hip_us"], rec["hip_peak_MiB"] = measure(ours)
+            rec["torch_us"], rec["torch_peak_MiB"] = measure(theirs)
+            rec["speedup"] = round(rec["torch_us"] / rec["hip_us"], 2)
+            print("MESH " + json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+        fsg._lib.start_timing()
+        for _ in range(20):
+            hip_loss()
+        for name, v in fsg._lib.stop_timing().items():
+            rec = dict(kernel="mesh default loss: " + name, B=B, calls_per_step=len(v) // 20,
+                       median_us=round(1e3 * sorted(v)[len(v) // 2], 1))
+            print("MESH " + json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+    out_path = os.environ.get("FSG_MESH_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
