@@ -149,11 +149,17 @@ SIGNATURES = {
     "fsg_mesh_sample_workspace_bytes": ([_I, _I], ctypes.c_size_t),
     "fsg_mesh_sample_f32": ([_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_mesh_sample_bwd_f32": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P], _I),
+    "fsg_grid_corners_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "fsg_grid_splat_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
+    "fsg_grid_splat_sorted_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_grid_sample_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "fsg_psr_spectral_f32": ([_P, _I, _I, _I, _I, ctypes.c_double, _I, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync
     _fn.argtypes, _fn.restype = _args, _res
 
+GRID_TORCH, GRID_SAP = 0, 1   # include/fsg_hip.h: FSG_GRID_*
 MORPH_MAX_RADIUS = 8   # csrc/morphology.hip: MAXR
 RW_BINARY, RW_INTENSITY, RW_MAX_LABELS = 0, 1, 8   # include/fsg_hip.h: FSG_RW_*; csrc/random_walk.hip builds K = 1..8
 KNN_FIX_DIAG, KNN_DROP_FIRST, KNN_FORCE_ROWS, KNN_FORCE_MFMA, KNN_MAX_K = 1, 2, 4, 8, 64

@@ -3049,3 +3049,188 @@ def relabel_by_size(labels, n):
         lut = _size_order_lut(_stats_device(l4, cap)[..., 0])
         out = _apply_lut(l4, lut)
     return out[0] if squeeze else out
+
+
+# ------------------------------------------------------------------ point cloud <-> dense grid, spectral PSR (csrc/grid_points.hip)
+GRID_MODES = {"torch": _lib.GRID_TORCH, "sap": _lib.GRID_SAP}
+
+
+def _grid_mode(mode):
+    if isinstance(mode, str) and mode.lower() in GRID_MODES:
+        return GRID_MODES[mode.lower()]
+    raise ValueError(f"mode must be 'torch' (grid_sample's convention) or 'sap' (point_rasterize's), got {mode!r}")
+
+
+def _grid_size(size, m):
+    try:
+        size = tuple(int(s) for s in size)
+    except TypeError:
+        size = ()
+    if len(size) != 3 or min(size) < (2 if m == _lib.GRID_SAP else 1) or size[0] * size[1] * size[2] >= 2 ** 31 - 1:
+        raise ValueError(f"grid size must be three positive integers (D, H, W) with D H W < 2^31 - 1, each >= 2 in 'sap' mode; "
+                         f"got {size}")
+    return size
+
+
+def _grid_check(first, coords, what, first_dims):
+    """the shared checks of splat and sample: `first` is values (B, C, N) or grid (B, C, D, H, W), coords (B, N, 3)"""
+    for t, name in ((first, what), (coords, "coords")):
+        if not torch.is_tensor(t) or not t.is_floating_point():
+            raise TypeError(f"{name} must be a floating-point tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if first.dim() != first_dims or first.shape[1] < 1 or first.shape[0] < 1:
+        raise ValueError(f"expected {what} with {first_dims} dimensions and B, C >= 1, got {tuple(first.shape)}")
+    if coords.dim() != 3 or coords.shape[2] != 3 or coords.shape[0] != first.shape[0]:
+        raise ValueError(f"expected coords (B, N, 3) with B = {first.shape[0]}, got {tuple(coords.shape)}")
+    if first.device != coords.device:
+        raise ValueError(f"{what} and coords are on different devices ({first.device}, {coords.device})")
+    if first.shape[0] > 65535:
+        raise ValueError(f"at most 65535 items per call, got {first.shape[0]}")
+
+
+def _splat_raw(values, coords, size, m):
+    """values (B, C, N), coords (B, N, 3), both fp32 and contiguous (the callers convert with _f32c) -> grid (B, C, D, H, W):
+    corners, a stable sort per item, the sums"""
+    B, C, N = values.shape
+    D, H, W = size
+    if N == 0:
+        return torch.zeros(B, C, D, H, W, dtype=torch.float32, device=values.device)
+    with torch.cuda.device(values.device):
+        keys = torch.empty(B, 8 * N, dtype=torch.int32, device=values.device)
+        w = torch.empty(B, 8 * N, dtype=torch.float32, device=values.device)
+        _lib.call("fsg_grid_corners_f32", _p(coords), B, N, D, H, W, m, _p(keys), _p(w), _stream())
+        skeys, perm = torch.sort(keys, dim=1, stable=True)
+        grid = torch.empty(B, C, D, H, W, dtype=torch.float32, device=values.device)
+        ws_bytes = _lib.lib.fsg_grid_splat_workspace_bytes(B, C, N)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=values.device)
+        _lib.call("fsg_grid_splat_sorted_f32", _p(values), _p(skeys), _p(perm), _p(w), B, C, N, D, H, W, _p(grid), _p(ws),
+                  ws_bytes, _stream())
+    return grid
+
+
+def _sample_raw(grid, coords, weights, m, want_sampled=True):
+    """grid (B, C, D, H, W), coords (B, N, 3), weights (B, C, N) or None, all fp32 and contiguous -> (sampled (B, C, N) or None,
+    grad_coords or None)"""
+    B, C, D, H, W = grid.shape
+    N = coords.shape[1]
+    sampled = torch.empty(B, C, N, dtype=torch.float32, device=grid.device) if want_sampled else None
+    gc = torch.empty(B, N, 3, dtype=torch.float32, device=grid.device) if weights is not None else None
+    if N > 0:
+        with torch.cuda.device(grid.device):
+            _lib.call("fsg_grid_sample_f32", _p(grid), _p(coords), _p(weights), B, C, N, D, H, W, m, _p(sampled), _p(gc),
+                      _stream())
+    return sampled, gc
+
+
+class _Splat(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, values, coords, size, m):
+        values, coords = _f32c(values), _f32c(coords)          # the kernels read fp32: any other floating type is converted
+        ctx.save_for_backward(values, coords)
+        ctx.m = m
+        return _splat_raw(values, coords, size, m)
+
+    @staticmethod
+    @_amp_bwd
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        values, coords = ctx.saved_tensors
+        need_v, need_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_v or need_c):
+            return None, None, None, None
+        gv, gc = _sample_raw(_f32c(g), coords, values if need_c else None, ctx.m, want_sampled=need_v)
+        return gv, gc, None, None
+
+
+class _Sample(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, grid, coords, m):
+        grid, coords = _f32c(grid), _f32c(coords)
+        ctx.save_for_backward(grid, coords)
+        ctx.m = m
+        return _sample_raw(grid, coords, None, m)[0]
+
+    @staticmethod
+    @_amp_bwd
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grid, coords = ctx.saved_tensors
+        g = _f32c(g)
+        gg = _splat_raw(g, coords, tuple(grid.shape[2:]), ctx.m) if ctx.needs_input_grad[0] else None
+        gc = _sample_raw(grid, coords, g, ctx.m, want_sampled=False)[1] if ctx.needs_input_grad[1] else None
+        return gg, gc, None
+
+
+def splat_to_grid(values, coords, size, mode):
+    """values (B, C, N) at coords (B, N, 3) -> grid (B, C, D, H, W), size = (D, H, W): the sum of the points' trilinear
+    contributions.  mode 'torch': coords (x -> W, y -> H, z -> D) in [-1, 1], the exact adjoint of F.grid_sample(mode='bilinear',
+    padding_mode='zeros', align_corners=False) (models/divroc.py:24-42); mode 'sap': coords (0 -> D, 1 -> H, 2 -> W) in [0, 1],
+    models/dpsr_utils.py:227-287 (point_rasterize).  Any floating-point input is converted to fp32, the result is fp32.
+    Gradients to values and coords (one gather launch); no double backward.
+    No floating-point atomics: the same input gives the same bits, an item gives the same bits alone and in a batch."""
+    m = _grid_mode(mode)
+    size = _grid_size(size, m)
+    _grid_check(values, coords, "values", 3)
+    if values.shape[2] != coords.shape[1]:
+        raise ValueError(f"values {tuple(values.shape)} and coords {tuple(coords.shape)} disagree about the number of points")
+    _need_gpu(values, coords)
+    return _Splat.apply(values, coords, size, m)
+
+
+def sample_grid(grid, coords, mode):
+    """grid (B, C, D, H, W) read at coords (B, N, 3) -> (B, C, N), trilinear, in the convention of `mode` (see splat_to_grid):
+    'torch' is F.grid_sample(..., align_corners=False, padding_mode='zeros'), 'sap' is models/dpsr_utils.py:156-199
+    (grid_interp).  Gradients to grid (a splat) and to coords (indices constant, torch's convention); no double backward."""
+    m = _grid_mode(mode)
+    _grid_check(grid, coords, "grid", 5)
+    _grid_size(grid.shape[2:], m)
+    _need_gpu(grid, coords)
+    return _Sample.apply(grid, coords, m)
+
+
+def _psr_raw(x, res, sig, adjoint):
+    B = x.shape[0]
+    R0, R1, R2 = res
+    out = torch.empty((B, R0, R1, R2 // 2 + 1) if not adjoint else (B, 3, R0, R1, R2 // 2 + 1), dtype=torch.complex64,
+                      device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("fsg_psr_spectral_f32", _p(x), B, R0, R1, R2, float(sig), int(adjoint), _p(out), _stream())
+    return out
+
+
+class _PSRSolve(torch.autograd.Function):
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, nhat, res, sig):
+        ctx.res, ctx.sig = res, sig
+        return _psr_raw(nhat.contiguous(), res, sig, False)
+
+    @staticmethod
+    @_amp_bwd
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _psr_raw(g.to(torch.complex64).contiguous(), ctx.res, ctx.sig, True), None, None
+
+
+def psr_spectral_solve(normal_field_hat, res, sig):
+    """models/dpsr_net.py:74-87 in one launch: normal_field_hat (B, 3, R0, R1, R2 / 2 + 1) complex64 = rfftn of the rasterised
+    normals over res = (R0, R1, R2) -> Phi (B, R0, R1, R2 / 2 + 1) complex64 = the Gaussian filter (sig), the divergence, the
+    division by the Laplacian and the zeroed DC term; irfftn(Phi, s=res) is the indicator grid.  The backward is the adjoint on
+    the same kernel."""
+    try:
+        res = tuple(int(r) for r in res)
+    except TypeError:
+        res = ()
+    if len(res) != 3 or min(res) < 1:
+        raise ValueError(f"res must be three positive integers, got {res}")
+    if not torch.is_tensor(normal_field_hat) or normal_field_hat.dtype != torch.complex64:
+        raise TypeError("normal_field_hat must be a complex64 tensor (torch.fft.rfftn of an fp32 field)")
+    want = (3, res[0], res[1], res[2] // 2 + 1)
+    if normal_field_hat.dim() != 5 or tuple(normal_field_hat.shape[1:]) != want or normal_field_hat.shape[0] < 1:
+        raise ValueError(f"expected normal_field_hat (B, {', '.join(map(str, want))}) for res {res}, got "
+                         f"{tuple(normal_field_hat.shape)}")
+    if not float(sig) >= 0:
+        raise ValueError(f"sig must be >= 0, got {sig}")
+    _need_gpu(normal_field_hat)
+    return _PSRSolve.apply(normal_field_hat, res, float(sig))

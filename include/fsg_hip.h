@@ -995,6 +995,47 @@ int fsg_mesh_sample_f32(const float *verts, const int32_t *faces, const int32_t 
 int fsg_mesh_sample_bwd_f32(const float *g, const int32_t *face, const float *w, const int32_t *faces, const int32_t *sdesc,
                             int N, int max_V, int n, float *grad_verts, fsg_stream_t stream);
 
+/* Point cloud <-> dense grid, and the spectral Poisson solve of DPSR (csrc/grid_points.hip).  Replace models/divroc.py:24-61
+ * (DiVRoC: a splat obtained by differentiating grid_sample against a zero grid, and its backward), models/dpsr_utils.py:156-199
+ * (grid_interp), :227-287 (point_rasterize with its (B N 8 C, 5) int64 scatter index) and models/dpsr_net.py:74-87
+ * (spectral_PSR between rfftn and irfftn).  All pointers DEVICE, all floating point fp32, any D, H, W.
+ *
+ * mode FSG_GRID_TORCH: coords (B, N, 3) = (x -> W, y -> H, z -> D) in [-1, 1], grid_sample's align_corners=False
+ *   unnormalisation t = ((x + 1) S - 1) / 2, trilinear, padding zeros: a corner outside the grid gives and receives nothing;
+ *   any coordinate is legal: a point without a corner in the grid (far outside, infinite or NaN on an axis) reads 0, adds
+ *   nothing and gets a zero gradient.  mode FSG_GRID_SAP: coords = (0 -> D, 1 -> H, 2 -> W) in [0, 1], cubesize =
+ *   1 / (S - 1), lower corner floor(p / cubesize), upper corner fmod(ceil(p / cubesize), S), weights |p - opposite corner| /
+ *   cubesize, every expression in fp32 in the reference's order (nodes, 0 and 1 reach the reference's voxels); every size >= 2;
+ *   points outside [0, 1] are outside the contract, their out-of-grid corners are dropped, nothing outside the grid is touched.
+ * Splat, values (B, C, N) -> grid (B, C, D, H, W) = sum of the trilinear contributions, in three steps:
+ *   fsg_grid_corners_f32 writes keys (B, 8 N) int32 (destination voxel z H W + y W + x, D H W for a dropped corner) and
+ *   w (B, 8 N), entry 8 n + corner;  the CALLER sorts every row of keys with a STABLE sort and keeps the permutation (int64,
+ *   position before the sort);  fsg_grid_splat_sorted_f32 zeroes the grid and sums every voxel's run in row order, a run cut
+ *   at every multiple of 64 row positions, the pieces added in position order.  No floating-point atomics: the same input gives
+ *   the same bits and an item gives the same bits alone and inside a batch.  workspace: the query below, 4-byte aligned.
+ * Sample: sampled (B, C, N) = trilinear reading of grid at coords (NULL: not written); with weights (B, C, N) also
+ *   grad_coords (B, N, 3) = sum_c weights[c] d sampled[c] / d coords, indices held constant: TORCH mode is grid_sample's
+ *   backward, SAP mode is autograd through grid_interp (torch's abs: 0 at 0).  weights and grad_coords are both NULL or both
+ *   given.  One launch, the 8 C corners are read once.  Splat and sample are adjoint; together they give every gradient of both.
+ * Spectral solve: in (B, 3, R0, R1, R2 / 2 + 1) complex64 = rfftn of the normal field -> out (B, R0, R1, R2 / 2 + 1) complex64,
+ *   Phi = sum_d c_d in_d, c_d = -i omega_d G / (-|omega|^2 + 1e-6), omega = 2 pi fftfreq (fp32), G = exp(-0.5 (2 sig |f| /
+ *   R0)^2) (fp64, rounded), Phi = 0 at the DC term.  adjoint = 1: in (B, R0, R1, R2 / 2 + 1) = grad Phi -> out (B, 3, ...) =
+ *   conj(c_d) grad Phi.  No permutes; in and out must differ.
+ * B <= 65535, N <= 2^27, D H W < 2^31 - 1.  Bad shapes, modes, NULL pointers or a short workspace are FSG_ERR_ARG before any
+ *   launch. */
+#define FSG_GRID_TORCH 0
+#define FSG_GRID_SAP 1
+int fsg_grid_corners_f32(const float *coords, int B, int N, int D, int H, int W, int mode, int32_t *keys, float *w,
+                         fsg_stream_t stream);
+size_t fsg_grid_splat_workspace_bytes(int B, int C, int N);
+int fsg_grid_splat_sorted_f32(const float *values, const int32_t *keys_sorted, const int64_t *perm, const float *w, int B, int C,
+                              int N, int D, int H, int W, float *grid, void *workspace, size_t workspace_bytes,
+                              fsg_stream_t stream);
+int fsg_grid_sample_f32(const float *grid, const float *coords, const float *weights, int B, int C, int N, int D, int H, int W,
+                        int mode, float *sampled, float *grad_coords, fsg_stream_t stream);
+int fsg_psr_spectral_f32(const float *in, int B, int R0, int R1, int R2, double sig, int adjoint, float *out,
+                         fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

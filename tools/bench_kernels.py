@@ -591,3 +591,113 @@ if "mesh" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "dpsr" in which:
+    # the DPSR front (csrc/grid_points.hip) beside the torch composition of the same math on the same device, fp32, with the peak
+    # extra device memory of both: 'torch' mode against F.grid_sample and its autograd adjoint, 'sap' mode against the
+    # reference-style scatter_add_ / gather (tests/dpsr_oracle.py), the spectral solve against the complex composition, and
+    # DPSR.forward / SoftMesh.psr_grid with their backward against the oracle's whole composition.  8 x 2048 points at 128^3,
+    # sigma 10, C in {3, 5}, one item alone, and a cloud whose points all share one cell.  The one-axis Gaussian derivative and
+    # the FFT stay torch's in both columns: their share of SoftMesh.psr_grid is reported on its own lines.
+    import json
+    import torch.nn.functional as TF
+    import dpsr_oracle as do
+    from fissure_segmentation_amd.models.dpsr_net import DPSR
+    from fissure_segmentation_amd.models.seg_logits_to_mesh import SoftMesh
+    from fissure_segmentation_amd.utils.image_utils import gaussian_differentiation
+
+    def measure(fn, iters=20, warm=3):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        med, _ = timeit(fn, iters, warm)
+        return round(med, 1), round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 2)
+
+    lines = []
+
+    def report(stage, ours, theirs, iters=20, **shape):
+        rec = dict(kernel="dpsr " + stage, **shape)
+        rec["hip_us"], rec["hip_peak_MiB"] = measure(ours, iters)
+        rec["torch_us"], rec["torch_peak_MiB"] = measure(theirs, iters)
+        rec["speedup"] = round(rec["torch_us"] / rec["hip_us"], 2)
+        print("DPSR " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+
+    res, sig, N = (128, 128, 128), 10, 2048
+    gen = torch.Generator().manual_seed(0)
+    for B, C, cloud_kind in [(8, 3, "uniform"), (8, 5, "uniform"), (1, 3, "uniform"), (1, 5, "uniform"), (8, 5, "one cell")]:
+        for mode in ("torch", "sap"):
+            if cloud_kind == "uniform":
+                lo, hi = (-1.0, 1.0) if mode == "torch" else (0.0, 1.0)
+                x = (torch.rand(B, N, 3, generator=gen) * (hi - lo) + lo).to(dev)
+            else:
+                x = do.one_cell_coords(mode).expand(B, -1, -1).contiguous().to(dev)
+            v = torch.randn(B, C, N, generator=gen).to(dev)
+            grid = torch.randn(B, C, *res, device=dev)
+            g = torch.randn(B, C, N, device=dev)
+            x5 = x.view(B, N, 1, 1, 3)
+            shape = dict(mode=mode, B=B, C=C, N=N, res=128, cloud=cloud_kind)
+
+            def torch_splat():
+                if mode == "sap":
+                    return do.splat(v, x, res, "sap")
+                z = torch.zeros(B, C, *res, device=dev, requires_grad=True)
+                return torch.autograd.grad(TF.grid_sample(z, x5, align_corners=False), z, v.view(B, C, N, 1, 1))[0]
+            report("splat", lambda: F.splat_to_grid(v, x, res, mode), torch_splat, **shape)
+            if cloud_kind == "one cell":
+                continue
+            xr = x.clone().requires_grad_(True)
+
+            def hip_sample():
+                s = F.sample_grid(grid, xr, mode)
+                return s, torch.autograd.grad(s, xr, g)
+
+            def torch_sample():
+                s = do.sample(grid, xr, "sap") if mode == "sap" else \
+                    TF.grid_sample(grid, xr.view(B, N, 1, 1, 3), align_corners=False).view(B, C, N)
+                return s, torch.autograd.grad(s, xr, g)
+            report("sample + coordinate gradient", hip_sample, torch_sample, **shape)
+    for B in (8, 1):
+        nhat = torch.fft.rfftn(torch.randn(B, 3, *res, device=dev), dim=(2, 3, 4))
+        report("spectral solve", lambda: F.psr_spectral_solve(nhat, res, sig), lambda: do.spectral(nhat, res, sig), B=B, res=128,
+               sig=sig)
+        s = do.sphere_case(B=B, N=N)
+        V, Nn = s["V"].to(dev).requires_grad_(True), s["N"].to(dev).requires_grad_(True)
+        gphi = torch.randn(B, *res, device=dev)
+        net = DPSR(res, sig).to(dev)
+        report("DPSR.forward + backward", lambda: torch.autograd.grad(net(V, Nn), (V, Nn), gphi),
+               lambda: torch.autograd.grad(do.dpsr(V, Nn, res, sig), (V, Nn), gphi), iters=10, B=B, N=N, res=128, sig=sig)
+        fsg._lib.start_timing()
+        for _ in range(10):
+            torch.autograd.grad(net(V, Nn), (V, Nn), gphi)
+        for name, t in fsg._lib.stop_timing().items():
+            rec = dict(kernel="dpsr DPSR.forward + backward: " + name, B=B, calls_per_step=len(t) // 10,
+                       median_us=round(1e3 * sorted(t)[len(t) // 2], 1))
+            print("DPSR " + json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+    for B, C in [(8, 3), (1, 3), (1, 5)]:
+        m = do.softmesh_case(B=B, K=C + 1, N=N)
+        lg, xc = m["logits"].to(dev).requires_grad_(True), m["coords"].to(dev)
+        gf = torch.randn(B * C, *res, device=dev)
+        sm = SoftMesh(10, res, sig).to(dev)
+        report("SoftMesh.psr_grid + backward", lambda: torch.autograd.grad(sm.psr_grid(lg, xc), lg, gf),
+               lambda: torch.autograd.grad(do.softmesh_field(lg, xc, res, 10, sig), lg, gf), iters=5, B=B, C=C, N=N, res=128, sig=sig)
+        seg = torch.randn(B, C, *res, device=dev, requires_grad=True)
+        gn = torch.randn(B, C, 3, *res, device=dev)
+
+        def conv_part():
+            n = torch.stack([gaussian_differentiation(seg, 10, 1, d, 'constant', 1.5) for d in (2, 1, 0)], 2)
+            return torch.autograd.grad(n, seg, gn)
+        fld = torch.randn(B * C, 3, *res, device=dev, requires_grad=True)
+        gh = torch.randn(B * C, *res, device=dev)
+
+        def fft_part():
+            h = torch.fft.rfftn(fld, dim=(2, 3, 4))
+            return torch.autograd.grad(torch.fft.irfftn(h[:, 0] + h[:, 1] + h[:, 2], s=res, dim=(1, 2, 3)), fld, gh)
+        for part, fn in (("Gaussian derivative (torch conv3d) fwd+bwd", conv_part), ("rfftn + irfftn fwd+bwd", fft_part)):
+            us, peak = measure(fn, 5)
+            rec = dict(kernel="dpsr SoftMesh.psr_grid share: " + part, B=B, C=C, res=128, torch_us=us, torch_peak_MiB=peak)
+            print("DPSR " + json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+    out_path = os.environ.get("FSG_DPSR_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
