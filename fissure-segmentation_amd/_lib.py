@@ -154,6 +154,11 @@ SIGNATURES = {
     "fsg_grid_splat_sorted_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_grid_sample_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "fsg_psr_spectral_f32": ([_P, _I, _I, _I, _I, ctypes.c_double, _I, _P, _P], _I),
+    "fsg_mc_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
+    "fsg_mc_count_f32": ([_P, _P, _L, _I, _I, _I, _I, _F, _I, _P, ctypes.c_size_t, _P, _P], _I),
+    "fsg_mc_count_labels_i32": ([_P, _P, _L, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P], _I),
+    "fsg_mc_emit_f32": ([_P, _I, _I, _I, _I, _F, _I, _F, _F, _F, _P, ctypes.c_size_t, _P, _L, _L, _P, _P, _P, _P], _I),
+    "fsg_mc_emit_labels_i32": ([_P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, ctypes.c_size_t, _P, _L, _L, _P, _P, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

@@ -83,6 +83,22 @@ static __device__ __forceinline__ float wave_max_nonneg_bcast_f(float v) {
     FSG_DPP_LADDER(FSG_DPP_FMAX)
     return wave_lane63_f(v);
 }
+// sum of one int per thread over a workgroup of NT threads, and each thread's exclusive prefix; `red` holds NT / 64 ints
+template <int NT>
+static __device__ __forceinline__ int block_excl_scan(int c, int *red, int &total) {
+    const int incl = wave_incl_scan(c);
+    __syncthreads();   // (the previous use of red is over)
+    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+        if (w < (int)(threadIdx.x >> 6)) before += red[w];
+        total += red[w];
+    }
+    return before + incl - c;
+}
 #undef FSG_DPP_ADD
 #undef FSG_DPP_FMAX
 #undef FSG_DPP_LADDER

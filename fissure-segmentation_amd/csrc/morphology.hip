@@ -322,22 +322,6 @@ __global__ __launch_bounds__(NT) void cc_merge_kernel(Dims d, int maxd, int *__r
     }
 }
 
-// sum of one int per thread over the workgroup, and each thread's exclusive prefix; `red` holds NT / 64 ints
-__device__ __forceinline__ int block_excl_scan(int c, int *red, int &total) {
-    const int incl = wave_incl_scan(c);
-    __syncthreads();   // (the previous use of red is over)
-    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        if (w < (int)(threadIdx.x >> 6)) before += red[w];
-        total += red[w];
-    }
-    return before + incl - c;
-}
-
 // root[v] = find(v) (parents are final: plain loads), and the roots of each chunk are counted
 __global__ __launch_bounds__(NT) void cc_flatten_kernel(Dims d, int nchunks, const int *__restrict__ parent_all,
                                                         int *__restrict__ root_all, int *__restrict__ counts) {
@@ -364,7 +348,7 @@ __global__ __launch_bounds__(NT) void cc_flatten_kernel(Dims d, int nchunks, con
             root[v] = a;
         }
         int total;
-        block_excl_scan(c, red, total);
+        block_excl_scan<NT>(c, red, total);
         if (threadIdx.x == 0) counts[(long)b * nchunks + ch] = total;
     }
 }
@@ -378,7 +362,7 @@ __global__ __launch_bounds__(NT) void cc_scan_kernel(int nchunks, int *__restric
         const int i = base + threadIdx.x;
         const int c = i < nchunks ? cnt[i] : 0;
         int total;
-        const int ex = block_excl_scan(c, red, total);
+        const int ex = block_excl_scan<NT>(c, red, total);
         if (i < nchunks) cnt[i] = carry + ex;
         carry += total;
     }
@@ -402,7 +386,7 @@ __global__ __launch_bounds__(NT) void cc_number_kernel(Dims d, int nchunks, cons
             c += is_root[k];
         }
         int total;
-        int rank = counts[(long)b * nchunks + ch] + block_excl_scan(c, red, total);
+        int rank = counts[(long)b * nchunks + ch] + block_excl_scan<NT>(c, red, total);
 #pragma unroll
         for (int k = 0; k < CHUNK / NT; ++k)
             if (is_root[k]) parent[v0 + k] = ++rank;

@@ -2,12 +2,13 @@
 out: no SimpleITK.  Convert an image with `torch.from_numpy(sitk.GetArrayFromImage(img).astype(int))` on the way in and
 `GetImageFromArray(t.cpu().numpy())` + `CopyInformation` on the way out, as the reference does around the same calls.
 `find_lobes` (:95-177) goes from fissures back to lobes with the ball morphology and connected components of
-csrc/morphology.hip; the marching-cubes part of the reference's module (compute_surface_mesh_marching_cubes) is not here, so
-the mesh list that find_lobes returns is empty."""
+csrc/morphology.hip; the mesh list it returns stays empty.  `compute_surface_mesh_marching_cubes` (:185-210) is a separate
+call on csrc/marching_cubes.hip: it gives the meshes the reference's find_lobes would have appended."""
 import numpy as np
 import torch
 
 from .. import functional as F_hip
+from ..mesh import Meshes
 
 
 def fill_lobes(lobes: torch.Tensor, mask: torch.Tensor, **solver) -> torch.Tensor:
@@ -87,3 +88,24 @@ def find_lobes(fissure_seg: torch.Tensor, lung_mask: torch.Tensor, exclude_rhf: 
         lut[order + 1] = new
         lobes = F_hip._apply_lut(labels, torch.from_numpy(lut).to(labels.device)[None], torch.int64)
     return lobes[0], [], True
+
+
+def compute_surface_mesh_marching_cubes(label_img: torch.Tensor, mask_image: torch.Tensor = None, max_label: int = None,
+                                        spacing=(1, 1, 1)):
+    """find_lobes.py:185-210 for tensors: one surface mesh per label 1..max_label of an integer label volume (D, H, W)
+    (max_label=None: the largest label, one host read), all labels in ONE batched launch sequence
+    (functional.marching_cubes_labels) -> a list of one-mesh `Meshes` with vertex normals pointing out of the object.
+    Vertices are in xyz order in physical units, spacing = (sx, sy, sz) = img.GetSpacing(), as the reference's are after its
+    flip.  mask_image (D, H, W): only cells whose 8 voxels are in the mask are meshed (dilate the mask so that it does not cut
+    the surface); this rule and the triangulation are ours, skimage's are unpinned.  A label without voxels gives a mesh without
+    vertices."""
+    if label_img.dim() != 3 or label_img.is_floating_point():
+        raise ValueError(f"compute_surface_mesh_marching_cubes: expected an integer label volume (D, H, W), got "
+                         f"{tuple(label_img.shape)} {label_img.dtype}")
+    F_hip._need_gpu(label_img, mask_image)
+    if max_label is None:
+        max_label = int(label_img.max())
+    if max_label < 1:
+        return []
+    verts, faces, normals, nv, nf = F_hip.marching_cubes_labels(label_img, 1, int(max_label), spacing=spacing, mask=mask_image)
+    return [Meshes([v], [f], [n]) for v, f, n in zip(verts.split(nv), faces.split(nf), normals.split(nv))]

@@ -3234,3 +3234,128 @@ def psr_spectral_solve(normal_field_hat, res, sig):
         raise ValueError(f"sig must be >= 0, got {sig}")
     _need_gpu(normal_field_hat)
     return _PSRSolve.apply(normal_field_hat, res, float(sig))
+
+
+# ------------------------------------------------------------------ marching cubes (csrc/marching_cubes.hip)
+def _mc_mask(mask, shape, what):
+    """mask or None -> (uint8 contiguous or None, item stride); a mask has the volume's shape, or (D, H, W) shared by all items"""
+    if mask is None:
+        return None, 0
+    if not torch.is_tensor(mask) or mask.is_floating_point() or tuple(mask.shape) not in (tuple(shape), tuple(shape[1:])):
+        raise ValueError(f"{what}: mask must be a bool or integer tensor of shape {tuple(shape)} or {tuple(shape[1:])}, got "
+                         f"{tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+    m = (mask != 0).to(torch.uint8).contiguous()
+    return m, (0 if mask.dim() == 3 else shape[1] * shape[2] * shape[3])
+
+
+def _mc_shape(shape, what):
+    B, D, H, W = shape
+    if B < 1 or min(D, H, W) < 2 or B > 65535 or B * D * H * W >= 2 ** 31:
+        raise ValueError(f"{what}: need B in 1..65535, every grid size >= 2 and B D H W < 2^31, got {tuple(shape)}")
+
+
+def _mc_run(count, emit, shape, dev, local, spacing):
+    """count (four launches), the one host read that sizes the outputs, emit (three launches).  count(ws, nbytes, totals) and
+    emit(local, sx, sy, sz, ws, nbytes, totals, nv, nf, verts, faces, normals) bind the volume."""
+    B, D, H, W = shape
+    with torch.cuda.device(dev):
+        nbytes = _lib.lib.fsg_mc_workspace_bytes(B, D, H, W)
+        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+        totals = torch.empty(4 * B + 1, dtype=torch.int64, device=dev)
+        count(ws, nbytes, totals)
+        host = totals[:2 * B + 1].tolist()                 # the readback: the result's size depends on the data
+        num_verts, num_faces, flag = host[0:2 * B:2], host[1:2 * B:2], host[2 * B]
+        if max(num_verts + num_faces) >= 2 ** 31:
+            raise ValueError("marching_cubes: an item has 2^31 or more vertices or faces")
+        nv, nf = sum(num_verts), sum(num_faces)
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+        normals = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        if flag == 0 and nv > 0:
+            emit(int(bool(local)), float(spacing[0]), float(spacing[1]), float(spacing[2]), ws, nbytes, totals, nv, nf, verts, faces,
+                 normals)
+    return verts, faces, normals, num_verts, num_faces, flag
+
+
+def marching_cubes(field, isolevel=0.0, return_local_coords=True, mask=None, validate=True):
+    """pytorch3d.ops.marching_cubes (models/dpsr_utils.py:60-61) with the vertex normals of Meshes.verts_normals_packed, on our
+    own case table (fissure_segmentation_amd/_mc_table.py; parity with pytorch3d is unpinned).  field (B, D, H, W), any
+    floating type (converted to fp32), every size >= 2 -> packed
+      verts (sum V, 3) fp32, columns (x, y, z) = position along (W, H, D): in [-1, 1] with return_local_coords (node i of an axis
+        of S nodes is 2 i / (S - 1) - 1), else in index units; one per grid edge that crosses the isolevel, ordered by
+        (item, z, y, x, axis) of the edge's lower node
+      faces (sum F, 3) int64, indices LOCAL to their item, ordered by (item, cell, table order)
+      normals (sum V, 3) fp32: the faces' (v1 - v0) x (v2 - v0) summed per vertex and divided by max(|n|, 1e-6); they point
+        toward increasing values
+      num_verts, num_faces: lists of B ints.
+    A node is inside iff value < isolevel.  mask (bool / integer, the field's shape or (D, H, W)): a cell emits iff its 8 nodes
+    are in the mask, and only vertices of emitting cells exist (this rule is ours).  validate=True raises ValueError on a
+    non-finite value (the flag rides on the count readback).  An item without a crossing has 0 vertices and faces.  The call reads
+    the totals back to size its outputs, so it cannot be captured into a graph.  No gradient: models/dpsr_utils.py's
+    DifferentiableMarchingCubes supplies the reference's.  Deterministic: the same input gives the same bits, alone or in a batch."""
+    if not torch.is_tensor(field) or not field.is_floating_point():
+        raise TypeError(f"field must be a floating-point tensor, got {field.dtype if torch.is_tensor(field) else type(field).__name__}")
+    if field.dim() != 4:
+        raise ValueError(f"marching_cubes: expected field (B, D, H, W), got {tuple(field.shape)}")
+    _mc_shape(field.shape, "marching_cubes")
+    m, mstride = _mc_mask(mask, field.shape, "marching_cubes")
+    iso = float(isolevel)
+    if iso != iso or iso in (float("inf"), float("-inf")):
+        raise ValueError(f"isolevel must be finite, got {isolevel!r}")
+    _need_gpu(field, m)
+    if m is not None and m.device != field.device:
+        raise ValueError(f"field and mask are on different devices ({field.device}, {m.device})")
+    f = _f32c(field)
+    B, D, H, W = f.shape
+
+    def count(ws, nbytes, totals):
+        _lib.call("fsg_mc_count_f32", _p(f), _p(m), mstride, B, D, H, W, iso, int(bool(validate)), _p(ws), nbytes, _p(totals),
+                  _stream())
+
+    def emit(local, sx, sy, sz, ws, nbytes, totals, nv, nf, verts, faces, normals):
+        _lib.call("fsg_mc_emit_f32", _p(f), B, D, H, W, iso, local, sx, sy, sz, _p(ws), nbytes, _p(totals), nv, nf, _p(verts),
+                  _p(faces), _p(normals), _stream())
+
+    with torch.no_grad():
+        verts, faces, normals, num_verts, num_faces, flag = _mc_run(count, emit, f.shape, f.device, return_local_coords, (1, 1, 1))
+    if flag:
+        raise ValueError("marching_cubes: the field holds a non-finite value (validate=False meshes it as it is: NaN is outside)")
+    return verts, faces, normals, num_verts, num_faces
+
+
+def marching_cubes_labels(labels, first_label, num_labels, spacing=(1, 1, 1), mask=None):
+    """One surface per label of ONE integer volume, in one batched call: labels (D, H, W), item b = the object
+    labels == first_label + b, meshed as the field (labels != first_label + b) at level 0.5 (every vertex is an edge midpoint,
+    normals point out of the object).  Vertices are in index units times spacing = (sx, sy, sz) for the (x, y, z) columns.  mask
+    (D, H, W) as in `marching_cubes`.  -> verts, faces, normals, num_verts, num_faces as `marching_cubes` returns them."""
+    if not torch.is_tensor(labels) or labels.is_floating_point() or labels.dim() != 3:
+        raise ValueError(f"marching_cubes_labels: expected an integer label volume (D, H, W), got "
+                         f"{(tuple(labels.shape), labels.dtype) if torch.is_tensor(labels) else type(labels).__name__}")
+    B = int(num_labels)
+    shape = (B,) + tuple(labels.shape)
+    _mc_shape(shape, "marching_cubes_labels")
+    try:
+        spacing = tuple(float(s) for s in spacing)
+    except TypeError:
+        spacing = ()
+    if len(spacing) != 3 or not all(0 < s < float("inf") for s in spacing):
+        raise ValueError(f"spacing must be three positive numbers (sx, sy, sz), got {spacing}")
+    if mask is not None and torch.is_tensor(mask) and mask.dim() != 3:
+        raise ValueError(f"marching_cubes_labels: the mask is shared by all labels, expected (D, H, W), got {tuple(mask.shape)}")
+    m, _ = _mc_mask(mask, shape, "marching_cubes_labels")
+    _need_gpu(labels, m)
+    if m is not None and m.device != labels.device:
+        raise ValueError(f"labels and mask are on different devices ({labels.device}, {m.device})")
+    lab = labels.to(torch.int32).contiguous()
+    first = int(first_label)
+    _, D, H, W = shape
+
+    def count(ws, nbytes, totals):
+        _lib.call("fsg_mc_count_labels_i32", _p(lab), _p(m), 0, first, B, D, H, W, _p(ws), nbytes, _p(totals), _stream())
+
+    def emit(local, sx, sy, sz, ws, nbytes, totals, nv, nf, verts, faces, normals):
+        _lib.call("fsg_mc_emit_labels_i32", _p(lab), first, B, D, H, W, local, sx, sy, sz, _p(ws), nbytes, _p(totals), nv, nf,
+                  _p(verts), _p(faces), _p(normals), _stream())
+
+    with torch.no_grad():
+        return _mc_run(count, emit, shape, lab.device, False, spacing)[:5]

@@ -9,8 +9,11 @@ per-vertex incidence lists the gradient needs) is built ONCE per face list on th
 faces tensor(s): a decoder's faces never change, so a training run builds it on its first step.  DESIGN.md has the
 definitions, the layout and the determinism rule.
 
-Not here: the cotangent / cotcurv Laplacian, a non-zero target edge length, textures and normals of `Meshes`, and the random
-stream of pytorch3d's sampler (the picks come from `torch.rand` through a fixed rule; which points are drawn for a given seed
+Vertex normals are CARRIED, not computed: `Meshes(verts, faces, verts_normals=...)` keeps what marching cubes produced
+(functional.marching_cubes), and asking a mesh that was given none raises NotImplementedError.
+
+Not here: the cotangent / cotcurv Laplacian, a non-zero target edge length, textures, vertex normals of arbitrary meshes, and the
+random stream of pytorch3d's sampler (the picks come from `torch.rand` through a fixed rule; which points are drawn for a given seed
 differs from pytorch3d's multinomial)."""
 import torch
 from torch.multiprocessing.reductions import StorageWeakRef
@@ -142,9 +145,10 @@ class _SampleStruct:
 # ------------------------------------------------------------------------------------------------------------- Meshes
 class Meshes:
     """A batch of triangle meshes: `Meshes(verts, faces)` with verts (B, V, 3) and faces (F, 3) (one face list for all) or
-    (B, F, 3), or with lists of per-mesh (V_i, 3) / (F_i, 3) tensors.  Faces hold vertex indices local to their mesh."""
+    (B, F, 3), or with lists of per-mesh (V_i, 3) / (F_i, 3) tensors.  Faces hold vertex indices local to their mesh.
+    verts_normals, optional, has the form of verts."""
 
-    def __init__(self, verts, faces):
+    def __init__(self, verts, faces, verts_normals=None):
         if torch.is_tensor(verts):
             if verts.dim() != 3 or verts.shape[2] != 3:
                 raise ValueError(f"verts must be (B, V, 3) or a list of (V_i, 3), got {tuple(verts.shape)}")
@@ -152,10 +156,13 @@ class Meshes:
                     (faces.dim() == 3 and faces.shape[0] != verts.shape[0]):
                 raise ValueError(f"faces must be (F, 3) or (B, F, 3) for verts {tuple(verts.shape)}, got "
                                  f"{tuple(faces.shape) if torch.is_tensor(faces) else type(faces).__name__}")
+            if verts_normals is not None and (not torch.is_tensor(verts_normals) or verts_normals.shape != verts.shape):
+                raise ValueError(f"verts_normals must have the shape of verts {tuple(verts.shape)}")
             self._padded, self._verts = verts, None
             self._faces_t, self._faces = faces, None
+            self._normals = verts_normals
             self._nv, self._nf = [verts.shape[1]] * verts.shape[0], [faces.shape[-2]] * verts.shape[0]
-            tensors = (verts, faces)
+            tensors = (verts, faces) + (() if verts_normals is None else (verts_normals,))
         else:
             verts, faces = list(verts), list(faces)
             if len(verts) != len(faces):
@@ -164,10 +171,16 @@ class Meshes:
                 if not (torch.is_tensor(v) and v.dim() == 2 and v.shape[1] == 3 and torch.is_tensor(f) and f.dim() == 2
                         and f.shape[1] == 3):
                     raise ValueError("list form: verts (V_i, 3) and faces (F_i, 3) per mesh")
+            if verts_normals is not None:
+                verts_normals = list(verts_normals)
+                if len(verts_normals) != len(verts) or any(not torch.is_tensor(n) or n.shape != v.shape
+                                                           for n, v in zip(verts_normals, verts)):
+                    raise ValueError("list form: verts_normals (V_i, 3) per mesh, matching verts")
             self._padded, self._verts = None, verts
             self._faces_t, self._faces = None, faces
+            self._normals = verts_normals
             self._nv, self._nf = [v.shape[0] for v in verts], [f.shape[0] for f in faces]
-            tensors = tuple(verts) + tuple(faces)
+            tensors = tuple(verts) + tuple(faces) + tuple(verts_normals or ())
         for f in ((self._faces_t,) if self._faces is None else self._faces):
             if f.is_floating_point() or f.dtype == torch.bool:
                 raise ValueError(f"faces must hold integer vertex indices, got {f.dtype}")
@@ -219,6 +232,37 @@ class Meshes:
             return torch.stack(self._verts) if self._verts else torch.zeros(0, 0, 3, device=self._device)
         return torch.nn.utils.rnn.pad_sequence(self._verts, batch_first=True)
 
+    def faces_padded(self):
+        """(B, max F, 3) int64, rows of -1 behind the shorter meshes (pytorch3d's padding)"""
+        fl = [f.to(torch.int64) for f in self.faces_list()]
+        if not fl:
+            return torch.zeros(0, 0, 3, dtype=torch.int64, device=self._device)
+        return torch.stack(fl) if len(set(self._nf)) <= 1 else torch.nn.utils.rnn.pad_sequence(fl, batch_first=True, padding_value=-1)
+
+    def _need_normals(self):
+        if self._normals is None:
+            raise NotImplementedError("this Meshes was given no verts_normals: vertex normals are only carried (marching cubes "
+                                      "produces them), computing them for an arbitrary mesh is not built")
+
+    def verts_normals_list(self):
+        self._need_normals()
+        return list(self._normals.unbind(0)) if self._verts is None else list(self._normals)
+
+    def verts_normals_packed(self):
+        self._need_normals()
+        if self._verts is None:
+            return self._normals.reshape(-1, 3)
+        return torch.cat(self._normals) if self._normals else torch.zeros(0, 3, device=self._device)
+
+    def verts_normals_padded(self):
+        """(B, max V, 3), zero rows behind the shorter meshes"""
+        self._need_normals()
+        if self._verts is None:
+            return self._normals
+        if len(set(self._nv)) <= 1:
+            return torch.stack(self._normals) if self._normals else torch.zeros(0, 0, 3, device=self._device)
+        return torch.nn.utils.rnn.pad_sequence(self._normals, batch_first=True)
+
     def __getitem__(self, index):
         if isinstance(index, int):
             index = [index]
@@ -227,15 +271,17 @@ class Meshes:
         elif torch.is_tensor(index):
             index = (torch.nonzero(index).reshape(-1) if index.dtype == torch.bool else index).tolist()
         v, f = self.verts_list(), self.faces_list()
-        return Meshes([v[i] for i in index], [f[i] for i in index])
+        n = None if self._normals is None else self.verts_normals_list()
+        return Meshes([v[i] for i in index], [f[i] for i in index], None if n is None else [n[i] for i in index])
 
     def to(self, device):
         device = torch.device(device)
         if device == self._device:
             return self
         if self._verts is None:
-            return Meshes(self._padded.to(device), self._faces_t.to(device))
-        return Meshes([v.to(device) for v in self._verts], [f.to(device) for f in self._faces])
+            return Meshes(self._padded.to(device), self._faces_t.to(device), None if self._normals is None else self._normals.to(device))
+        return Meshes([v.to(device) for v in self._verts], [f.to(device) for f in self._faces],
+                      None if self._normals is None else [n.to(device) for n in self._normals])
 
     # ---- what the kernels take
     def _face_tensors(self):
@@ -294,7 +340,8 @@ def join_meshes_as_batch(meshes):
     meshes = list(meshes)
     if len(meshes) == 1:
         return meshes[0]
-    return Meshes([v for m in meshes for v in m.verts_list()], [f for m in meshes for f in m.faces_list()])
+    normals = [n for m in meshes for n in m.verts_normals_list()] if meshes and all(m._normals is not None for m in meshes) else None
+    return Meshes([v for m in meshes for v in m.verts_list()], [f for m in meshes for f in m.faces_list()], normals)
 
 
 # ----------------------------------------------------------------------------------------------------------- sampling

@@ -3,7 +3,7 @@ Points), 3-D.  The rasterisation of the normals and the reading of the indicator
 of csrc/grid_points.hip, the work between rfftn and irfftn (:74-87, about ten passes over the complex spectrum in the
 reference) is one kernel (functional.psr_spectral_solve); the FFTs are torch's, the shift and scale (:91-103) a short torch
 composition through which gradients flow as in the reference (through the offset and through |phi[0, 0, 0]|).
-`DPSRNet` (:107-185) is not mirrored: it needs marching cubes and point-cloud normal estimation."""
+`DPSRNet` (:107-185) is not mirrored: it needs point-cloud normal estimation (marching cubes is in models/dpsr_utils.py)."""
 import torch
 from torch import nn
 

@@ -1036,6 +1036,42 @@ int fsg_grid_sample_f32(const float *grid, const float *coords, const float *wei
 int fsg_psr_spectral_f32(const float *in, int B, int R0, int R1, int R2, double sig, int adjoint, float *out,
                          fsg_stream_t stream);
 
+/* Marching cubes on a dense grid (csrc/marching_cubes.hip; the case table csrc/mc_table.h is generated by tools/gen_mc_table.py).
+ * Replace pytorch3d.ops.marching_cubes and Meshes.verts_normals_padded as DifferentiableMarchingCubes calls them
+ * (models/dpsr_utils.py:60-64) and skimage.measure.marching_cubes of compute_surface_mesh_marching_cubes
+ * (data_processing/find_lobes.py).  All pointers DEVICE.  Parity with those two libraries is unpinned (neither is available):
+ * the table, the orders and the mask rule below are this library's own.
+ *
+ * field (B, D, H, W) fp32, every size >= 2, B D H W < 2^31, B <= 65535.  A node is inside iff value < isolevel (fp32; NaN is
+ *   outside).  mask (uint8, nonzero = in; NULL = all) has mask_item_stride D H W (one per item) or 0 (shared); a cell emits
+ *   triangles iff all 8 of its corner nodes are in the mask, a grid edge carries a vertex iff it crosses the isolevel and one of
+ *   the <= 4 cells round it emits.  The labels form takes ONE int32 volume (D, H, W) for all items: item b is the object
+ *   labels == first_label + b, cut as the field (labels != first_label + b) at 0.5, so normals point out of the object.
+ * count: four launches -> workspace (the query below, 8-byte aligned; it must reach the emit call unchanged) and totals, int64
+ *   (4 B + 1): [2 b] vertices and [2 b + 1] triangles of item b, [2 B] nonzero iff validate and a field value is not finite,
+ *   [2 B + 1 + 2 b], [2 B + 2 + 2 b] the rows where item b starts in the packed outputs.  The caller reads totals (the one
+ *   readback; the sizes depend on the data, so the pair cannot be captured into a graph) and must not emit when a per-item
+ *   total exceeds 2^31 - 1.
+ * emit: three launches -> verts (total_verts, 3) fp32 in (x, y, z) = index along (W, H, D), faces (total_faces, 3) int64 indices
+ *   LOCAL to their item, normals (total_verts, 3) fp32.  Vertex order (item, z, y, x of the lower node of the edge, axis x < y < z),
+ *   face order (item, cell, table order).  position = p_a + t (p_b - p_a), t = (isolevel - v_a) / (v_b - v_a), p the node
+ *   coordinate: 2 i / (S - 1) - 1 with local_coords, else i * (sx, sy, sz).  normal = sum over the vertex's faces of
+ *   (v1 - v0) x (v2 - v0) in output coordinates, in (cell z, y, x, table order) order, divided by max(|n|, 1e-6); it points
+ *   toward increasing field values.  Rows at or past total_verts / total_faces are never written.
+ * No floating-point atomics and none that decide an order: the same input gives the same bits, an item the same bits alone and
+ *   inside a batch.  Bad shapes, NULL pointers, a short or misaligned workspace are FSG_ERR_ARG before any launch. */
+size_t fsg_mc_workspace_bytes(int B, int D, int H, int W);
+int fsg_mc_count_f32(const float *field, const uint8_t *mask, int64_t mask_item_stride, int B, int D, int H, int W, float isolevel,
+                     int validate, void *workspace, size_t workspace_bytes, int64_t *totals, fsg_stream_t stream);
+int fsg_mc_count_labels_i32(const int32_t *labels, const uint8_t *mask, int64_t mask_item_stride, int first_label, int B, int D,
+                            int H, int W, void *workspace, size_t workspace_bytes, int64_t *totals, fsg_stream_t stream);
+int fsg_mc_emit_f32(const float *field, int B, int D, int H, int W, float isolevel, int local_coords, float sx, float sy, float sz,
+                    const void *workspace, size_t workspace_bytes, const int64_t *totals, int64_t total_verts, int64_t total_faces,
+                    float *verts, int64_t *faces, float *normals, fsg_stream_t stream);
+int fsg_mc_emit_labels_i32(const int32_t *labels, int first_label, int B, int D, int H, int W, int local_coords, float sx, float sy,
+                           float sz, const void *workspace, size_t workspace_bytes, const int64_t *totals, int64_t total_verts,
+                           int64_t total_faces, float *verts, int64_t *faces, float *normals, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

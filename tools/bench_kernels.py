@@ -701,3 +701,91 @@ if "dpsr" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "mc" in which:
+    # marching cubes (csrc/marching_cubes.hip): HIP-event medians of the whole call (its one host read included) and of its two
+    # C-ABI halves, vertex and face counts, bytes moved against the compulsory bytes (the field once, the outputs once), peak
+    # extra device memory, the numpy oracle on the CPU for scale, and SoftMesh.meshes beside SoftMesh.psr_grid (forward +
+    # backward) from the same run.  No device composition of marching cubes exists to race (pytorch3d and scikit-image are not
+    # installed), so there is no second column.
+    import json
+    import time
+    import numpy as np
+    import dpsr_oracle as do
+    import mc_oracle as mo
+    from fissure_segmentation_amd.models.seg_logits_to_mesh import SoftMesh
+
+    def measure(fn, iters=10, warm=2):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        med, _ = timeit(fn, iters, warm)
+        return round(med, 1), round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 2)
+
+    lines = []
+
+    def emit_line(rec):
+        print("MC " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+
+    def stage_times(fn, reps=5):
+        fsg._lib.start_timing()
+        for _ in range(reps):
+            fn()
+        return {k: round(1e3 * sorted(v)[len(v) // 2], 1) for k, v in fsg._lib.stop_timing().items() if k.startswith("fsg_mc_")}
+
+    res, sig, N = (128, 128, 128), 10, 2048
+    fields = {}
+    for B, C in [(1, 1), (8, 3)]:
+        m = do.softmesh_case(B=B, K=C + 1, N=N)
+        sm = SoftMesh(10, res, sig).to(dev)
+        with torch.no_grad():
+            fields[B * C] = sm.psr_grid(m["logits"].to(dev), m["coords"].to(dev)).contiguous()
+    for n_fields, field in fields.items():
+        v, f, n, nv, nf = F.marching_cubes(field)
+        nodes = field.numel()
+        out_bytes = v.numel() * 4 * 2 + f.numel() * 8
+        # count: field 8 corner reads (once from HBM, the rest cache hits) + 1 B case + 7 B cases + 2 B code per node; emit: 2 B code
+        # twice + 1 B case twice per node, the field at the crossing edges, the outputs once, the vertices again for the normals
+        moved = nodes * (4 + 1 + 1 + 2 + 2 + 2 + 1 + 1) + out_bytes + sum(nf) * 3 * 12
+        us, peak = measure(lambda: F.marching_cubes(field))
+        rec = dict(kernel="mc marching_cubes (count + host read + emit)", fields=n_fields, res=128, hip_us=us, hip_peak_MiB=peak,
+                   verts=sum(nv), faces=sum(nf), compulsory_MB=round((nodes * 4 + out_bytes) / 1e6, 2),
+                   moved_MB_model=round(moved / 1e6, 2), launches=stage_times(lambda: F.marching_cubes(field)))
+        if n_fields == 1:
+            t0 = time.perf_counter()
+            mo.marching_cubes(field.cpu().numpy(), dtype=np.float32)
+            rec["cpu_oracle_numpy_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+            rec["cpu_threads"] = torch.get_num_threads()
+        emit_line(rec)
+    lab = torch.zeros(256, 256, 320, dtype=torch.int32, device=dev)
+    zz, yy, xx = torch.meshgrid(torch.arange(256, device=dev), torch.arange(256, device=dev), torch.arange(320, device=dev), indexing="ij")
+    for lb, (cz, cy, cx) in enumerate([(80, 80, 90), (80, 170, 90), (170, 80, 90), (128, 100, 230), (128, 180, 230)], 1):
+        lab[((zz - cz) ** 2 + (yy - cy) ** 2 + ((xx - cx) * 0.8) ** 2) < 40 ** 2] = lb
+    del zz, yy, xx
+    v, f, n, nv, nf = F.marching_cubes_labels(lab, 1, 5)
+    us, peak = measure(lambda: F.marching_cubes_labels(lab, 1, 5))
+    out_bytes = v.numel() * 8 + f.numel() * 8
+    emit_line(dict(kernel="mc marching_cubes_labels (count + host read + emit)", labels=5, shape=[256, 256, 320], hip_us=us,
+                   hip_peak_MiB=peak, verts=sum(nv), faces=sum(nf), compulsory_MB=round((lab.numel() * 4 + out_bytes) / 1e6, 2),
+                   launches=stage_times(lambda: F.marching_cubes_labels(lab, 1, 5))))
+    del lab
+    for B, C in [(8, 3), (1, 3)]:
+        m = do.softmesh_case(B=B, K=C + 1, N=N)
+        lg, xc = m["logits"].to(dev).requires_grad_(True), m["coords"].to(dev)
+        gf = torch.randn(B * C, *res, device=dev)
+        sm = SoftMesh(10, res, sig).to(dev)
+
+        def meshes_fb():
+            mm = sm.meshes(lg, xc)
+            return torch.autograd.grad(mm.verts_packed().square().sum(), lg)
+        psr_us, psr_peak = measure(lambda: torch.autograd.grad(sm.psr_grid(lg, xc), lg, gf), 5)
+        mesh_us, mesh_peak = measure(meshes_fb, 5)
+        rec = dict(kernel="mc SoftMesh.meshes fwd+bwd beside SoftMesh.psr_grid fwd+bwd", B=B, C=C, N=N, res=128, psr_grid_us=psr_us,
+                   psr_grid_peak_MiB=psr_peak, meshes_us=mesh_us, meshes_peak_MiB=mesh_peak,
+                   marching_cubes_share=round((mesh_us - psr_us) / mesh_us, 3))
+        if mesh_us - psr_us > psr_us:
+            rec["note"] = "THE MARCHING-CUBES STAGE IS SLOWER THAN THE WHOLE PSR FRONT"
+        emit_line(rec)
+    out_path = os.environ.get("FSG_MC_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
