@@ -2057,6 +2057,117 @@ def fps(xyz, offset, new_offset, m):
     return idx
 
 
+# ------------------------------------------------------------------ point-cloud normals (csrc/pcl_normals.hip)
+def _neighborhood_size(neighborhood_size):
+    K = int(neighborhood_size)
+    if not 2 <= K <= _lib.PCL_NORMALS_MAX_K:
+        raise ValueError(f"neighborhood_size must be in 2..{_lib.PCL_NORMALS_MAX_K}, got {neighborhood_size}")
+    return K
+
+
+def _check_neighbours(idx, off, n, K):
+    """the host-side look at a caller's neighbour lists (one synchronisation): the offsets end at n and do not decrease, and
+    every column the kernel reads (the first k_s of a row) names a point of the row's own segment"""
+    rows = torch.arange(n, device=idx.device)
+    seg = torch.searchsorted(off, rows.to(torch.int32), right=True).clamp_(max=off.shape[0] - 1)
+    en = off[seg].long()
+    st = torch.where(seg > 0, off[(seg - 1).clamp_(min=0)].long(), torch.zeros_like(en))
+    ks = (en - st - 1).clamp_(min=1, max=K)
+    read = torch.arange(K, device=idx.device)[None] < ks[:, None]
+    i = idx.long()
+    bad_idx = (read & ((i < st[:, None]) | (i >= en[:, None]))).any()
+    bad_off = (off[-1] != n) | (off[0] < 0) | (off[1:] < off[:-1]).any()
+    bad_idx, bad_off = torch.stack([bad_idx, bad_off]).tolist()
+    if bad_off:
+        raise ValueError(f"offset must be non-decreasing cumulative segment ends finishing at n = {n}")
+    if bad_idx:
+        raise ValueError("idx holds an index outside its row's segment (or outside the cloud) in a column that is read")
+
+
+def _pcl_normals_raw(xyz, off, K, disambiguate, idx, want_frames):
+    """xyz (n, 3) fp32 contiguous, off (b) int32, idx (n, K) int32 -> normals (n, 3), curvatures (n, 3), frames (n, 3, 3) | None"""
+    n = xyz.shape[0]
+    normals = torch.empty(n, 3, dtype=torch.float32, device=xyz.device)
+    curv = torch.empty(n, 3, dtype=torch.float32, device=xyz.device)
+    frames = torch.empty(n, 3, 3, dtype=torch.float32, device=xyz.device) if want_frames else None
+    with torch.cuda.device(xyz.device):
+        _lib.call("fsg_pcl_normals_f32", _p(xyz), _p(idx), _p(off), off.shape[0], n, K, int(bool(disambiguate)), _p(normals),
+                  _p(curv), _p(frames), _stream())
+    return normals, curv, frames
+
+
+def _pcl_packed(xyz, offset, neighborhood_size, disambiguate_directions, idx, validate, want_frames):
+    K = _neighborhood_size(neighborhood_size)
+    if not torch.is_tensor(xyz) or not xyz.is_floating_point() or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"expected packed points xyz (n, 3), got {tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    if not torch.is_tensor(offset) or offset.is_floating_point() or offset.dim() != 1 or offset.shape[0] < 1:
+        raise ValueError("offset must be a 1-D integer tensor of cumulative segment ends")
+    _need_gpu(xyz, offset, idx)
+    with torch.no_grad():
+        x, off = _f32c(xyz), offset.to(torch.int32).contiguous()
+        n = x.shape[0]
+        if idx is None:
+            idx = knn_segment(K, x, x, off, off)[0] if n else torch.empty(0, K, dtype=torch.int32, device=x.device)
+        else:
+            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or tuple(idx.shape) != (n, K):
+                raise ValueError(f"idx must be an integer tensor of shape ({n}, {K}): the first neighborhood_size columns of "
+                                 f"knn_segment's lists")
+            idx = idx.to(torch.int32).contiguous()
+            if validate and n:
+                _check_neighbours(idx, off, n, K)
+        return _pcl_normals_raw(x, off, K, disambiguate_directions, idx, want_frames)
+
+
+def pointcloud_frames_packed(xyz, offset, neighborhood_size, disambiguate_directions=True, idx=None, validate=True):
+    """The local PCA frame of every point of a packed cloud (fsg_pcl_normals_f32): xyz (n, 3), offset (b,) cumulative segment
+    ends -> curvatures (n, 3), the eigenvalues of the neighbourhood covariance in ascending order, and frames (n, 3, 3) whose
+    COLUMNS are (normal, y, z): the eigenvector of the smallest eigenvalue, z x normal, the eigenvector of the largest.
+
+    Per point: the k nearest points of its own segment, itself included; C = mean of (x_j - mean)(x_j - mean)^T over them.  A
+    segment of n_s points uses k_s = min(neighborhood_size, n_s - 1) (at least 1): a short segment gets a smaller neighbourhood
+    instead of an error.  With disambiguate_directions a vector v is negated when fewer than half of the k neighbours have
+    v . (x_j - p) > 0 (applied to the normal and to z); on a convex surface this points the normals INWARDS, as pytorch3d's
+    rule does.  Parity with pytorch3d is unpinned (restated, not compared).
+
+    idx (n, neighborhood_size): neighbour lists in knn_segment's layout (ascending distance, self first, indices into xyz);
+    without it knn_segment runs (queries = the points).  Only the first k_s columns of a row are read.  validate=True checks a
+    given idx (and the offsets) on the host, one synchronisation: an index outside the row's segment raises ValueError; with
+    validate=False a bad index is clamped into the cloud by the kernel and gives a wrong frame, not a fault.
+    neighborhood_size outside 2..64 raises ValueError.  No autograd: the outputs are constants (detached), as the reference
+    uses them.  Deterministic: the same input gives the same bits."""
+    _, curv, frames = _pcl_packed(xyz, offset, neighborhood_size, disambiguate_directions, idx, validate, True)
+    return curv, frames
+
+
+def _dense_cloud(pointclouds, neighborhood_size):
+    K = _neighborhood_size(neighborhood_size)
+    if not torch.is_tensor(pointclouds) or pointclouds.dim() != 3 or pointclouds.shape[2] != 3:
+        raise ValueError(f"expected pointclouds (B, N, 3), got "
+                         f"{tuple(pointclouds.shape) if torch.is_tensor(pointclouds) else type(pointclouds).__name__}")
+    B, N, _ = pointclouds.shape
+    if K >= N:
+        raise ValueError(f"neighborhood_size ({K}) must be smaller than the number of points per cloud ({N})")
+    _need_gpu(pointclouds)
+    offset = torch.arange(1, B + 1, dtype=torch.int32, device=pointclouds.device) * N
+    return K, B, N, offset
+
+
+def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size=50, disambiguate_directions=True):
+    """pytorch3d.ops.estimate_pointcloud_local_coord_frames for a (B, N, 3) tensor -> curvatures (B, N, 3), local_coord_frames
+    (B, N, 3, 3); see pointcloud_frames_packed (every cloud is one segment).  2 <= neighborhood_size <= 64 and < N."""
+    K, B, N, offset = _dense_cloud(pointclouds, neighborhood_size)
+    _, curv, frames = _pcl_packed(pointclouds.reshape(B * N, 3), offset, K, disambiguate_directions, None, False, True)
+    return curv.view(B, N, 3), frames.view(B, N, 3, 3)
+
+
+def estimate_pointcloud_normals(pointclouds, neighborhood_size=50, disambiguate_directions=True):
+    """pytorch3d.ops.estimate_pointcloud_normals for a (B, N, 3) tensor -> normals (B, N, 3), the first column of the frames of
+    estimate_pointcloud_local_coord_frames (the same bits).  Constants: no gradient reaches the points."""
+    K, B, N, offset = _dense_cloud(pointclouds, neighborhood_size)
+    normals, _, _ = _pcl_packed(pointclouds.reshape(B * N, 3), offset, K, disambiguate_directions, None, False, False)
+    return normals.view(B, N, 3)
+
+
 # ------------------------------------------------------------------ zeroed scratch of a backward pass, one fill
 class ZeroArena:
     """Backward kernels that accumulate with atomics (grouping, interpolation, the attention layer's dk / dv / dp) need zeroed

@@ -1072,6 +1072,25 @@ int fsg_mc_emit_labels_i32(const int32_t *labels, int first_label, int B, int D,
                            float sz, const void *workspace, size_t workspace_bytes, const int64_t *totals, int64_t total_verts,
                            int64_t total_faces, float *verts, int64_t *faces, float *normals, fsg_stream_t stream);
 
+/* Point-cloud normal estimation on packed clouds (csrc/pcl_normals.hip).  Replaces pytorch3d.ops.estimate_pointcloud_normals and
+ * estimate_pointcloud_local_coord_frames as models/dpsr_net.py:173-175 calls them; parity with pytorch3d is unpinned (the
+ * library is not available), the semantics below are restated from its ops/points_normals.py.  All pointers DEVICE.
+ *
+ * xyz (n, 3) fp32 packed, offset (b) int32 cumulative segment ends (as fsg_knn_segment_f32 takes them; empty segments allowed),
+ * idx (n, K) int32 neighbour lists in that kernel's layout: row q holds points of q's segment in ascending distance, q itself
+ * first.  A point of a segment of n_s points uses k_s = max(1, min(K, n_s - 1)) neighbours (itself included) and reads only
+ * the first k_s columns of its row; the columns beyond are never touched.  An index outside [0, n) is clamped into the cloud
+ * (it cannot fault); that it lies in the right segment is the caller's business.
+ *   C = mean_j (x_j - mean)(x_j - mean)^T over the k_s neighbours; curvatures (n, 3) = its eigenvalues ascending; normals (n, 3)
+ *   = the unit eigenvector of the smallest, z = that of the largest.  With disambiguate != 0 a vector v is negated iff
+ *   #{j : v . (x_j - p) > 0} < k_s / 2 (applied to the normal and to z; on a convex surface the normal then points INWARDS).
+ *   frames (n, 3, 3) or NULL: columns (normal, y = z x normal, z).
+ * Rank-deficient C (coincident, collinear, planar neighbours) gives finite orthonormal vectors.  A non-finite coordinate makes
+ * the rows that list it non-finite and nothing else.  fp32, no atomics: the same input gives the same bits.
+ * 2 <= K <= 64, b >= 1, n <= 2^28; bad shapes and NULL pointers are FSG_ERR_ARG before any launch. */
+int fsg_pcl_normals_f32(const float *xyz, const int32_t *idx, const int32_t *offset, int b, int n, int K, int disambiguate,
+                        float *normals, float *curvatures, float *frames, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
