@@ -275,6 +275,13 @@ def experiments():
     return _experiments
 
 
+def workspace(entry, *dims, device):
+    """the scratch that the `<entry>*` entry points ask for at these dims (`<entry>_workspace_bytes(*dims)`): a uint8 tensor of
+    that many bytes (numel() is the byte count), or None -- a null pointer -- when the query returns 0"""
+    nbytes = getattr(lib, entry + "_workspace_bytes")(*dims)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
 def call(name, *args):
     if _timing is None:
         rc = getattr(lib, name)(*args)

@@ -6,7 +6,6 @@
 //   x (M,C) row-major, C in {32,64,128,256,512}; thread (row slot, channel): every access is a contiguous 4*C-byte row.
 //   Train-mode statistics: per-thread fp64 sum / sum of squares, one record per workgroup, one wave per channel folds
 //   them in a fixed order (reproducible; no E[x^2]-E[x]^2 cancellation at fp32 scale).
-#include <stdlib.h>
 
 #include "fsg_common.h"
 
@@ -310,12 +309,6 @@ inline int grid_elems(long total4) {
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
-inline bool bnr_three_launches() {     // FSG_BNR_THREE_LAUNCHES=1: statistics / finalize / apply as separate launches at every size
-    static int v = -1;
-    if (v < 0) v = getenv("FSG_BNR_THREE_LAUNCHES") ? 1 : 0;
-    return v == 1;
-}
-
 }  // namespace
 
 extern "C" size_t fsg_bn_rows_workspace_bytes(long M, int C) {
@@ -331,7 +324,7 @@ extern "C" int fsg_bn_rows_fwd_f32(const float *x, const float *residual, const 
     FSG_REQUIRE(M > 0 && ok_c(C), "fsg_bn_rows_fwd_f32: bad shape M=%ld C=%d (C in {32,64,128,256,512})", M, C);
     FSG_REQUIRE(!training || workspace, "fsg_bn_rows_fwd_f32: training needs the workspace");
     hipStream_t st = (hipStream_t)stream;
-    if (training && M <= SMALL_M && !bnr_three_launches()) {
+    if (training && M <= SMALL_M) {
         hipLaunchKernelGGL(bnr_small_fwd_kernel, dim3(C / 4), dim3(SMALL_NT), 0, st, x, residual, gamma, beta, (int)M, C, eps,
                            momentum, relu, out, mean, rstd, running_mean, running_var);
         FSG_CHECK_LAUNCH("fsg_bn_rows_fwd_f32/small");
@@ -361,7 +354,7 @@ extern "C" int fsg_bn_rows_bwd_f32(const float *grad_out, const float *x, const 
     FSG_REQUIRE(!relu || out, "fsg_bn_rows_bwd_f32: the ReLU mask needs the forward output");
     FSG_REQUIRE(M > 0 && ok_c(C), "fsg_bn_rows_bwd_f32: bad shape M=%ld C=%d", M, C);
     hipStream_t st = (hipStream_t)stream;
-    if (M <= SMALL_M && !bnr_three_launches()) {
+    if (M <= SMALL_M) {
         hipLaunchKernelGGL(bnr_small_bwd_kernel, dim3(C / 4), dim3(SMALL_NT), 0, st, grad_out, x, out, gamma, mean, rstd, (int)M, C,
                            relu, training ? (float)(1.0 / (double)M) : 0.f, grad_x, grad_residual, grad_gamma, grad_beta);
         FSG_CHECK_LAUNCH("fsg_bn_rows_bwd_f32/small");

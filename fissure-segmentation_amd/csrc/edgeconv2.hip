@@ -16,7 +16,6 @@
 // MFMA products per tile: dz1 = dy2 W2 (-> du1 = dz1 f'(u1), written once to HBM, and the dbeta1/dgamma1 sums) and
 // dW2 += dy2^T z1 (accumulated in registers over all tiles of the workgroup).  dP/dQ then come from the
 // reverse-graph gather over du1 (no float atomics anywhere).
-#include <stdlib.h>
 
 #include "edgeconv_internal.h"
 
@@ -1140,43 +1139,27 @@ __global__ __launch_bounds__(256, (NP == 3 && RT == 4) ? 1 : 2) void ec2s_bwd_ke
 
 }  // namespace
 
-static int ec2_env_int(const char *name) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
-}
-
-// C2 = 64 runs on the split-bf16 kernels (FSG_EC2_OLD=1: the fp32-MFMA kernels above, kept for C2 = 128 and as a cross-check)
-static int ec2_old_env = -1;
+// C2 = 64 runs on the split-bf16 kernels; the fp32-MFMA kernels above are kept for C2 = 128 and as a cross-check
+static int ec2_use_fp32_mfma = 0;
 // tests: switch the C2 = 64 path between the split-bf16 kernels (0) and the fp32-MFMA kernels (1) inside one process
 // (tests/test_gpu_parity.py::test_ec2s_is_fp32_grade holds the former to the latter's error against fp64)
-extern "C" void fsg_debug_ec2_use_fp32_mfma(int on) { ec2_old_env = on ? 1 : 0; }
-static bool ec2_split(int C2) {
-    if (ec2_old_env < 0) ec2_old_env = ec2_env_int("FSG_EC2_OLD") > 0 ? 1 : 0;
-    return C2 == 64 && !ec2_old_env;
-}
+extern "C" void fsg_debug_ec2_use_fp32_mfma(int on) { ec2_use_fp32_mfma = on ? 1 : 0; }
+static bool ec2_split(int C2) { return C2 == 64 && !ec2_use_fp32_mfma; }
 
 // tiles of the split kernels: RT * 32 edge rows = TP points; 128 rows when that cuts the padding by more than 15 % (k = 40:
-// 40 of 64 rows against 120 of 128), 64 rows otherwise; `wgs` workgroups over the B clouds
+// 40 of 64 rows against 120 of 128), 64 rows otherwise; 768 (forward) / 512 (backward) workgroups over the B clouds
 static void ec2s_tiling(int k, int B, int N, bool bwd, bool bf16, int &RT, int &TP, int &G) {
-    static int rt_env = -1, fwd_wgs = -1, bwd_wgs = -1;
-    if (rt_env < 0) {
-        rt_env = ec2_env_int("FSG_EC2S_RT");
-        fwd_wgs = ec2_env_int("FSG_EC2S_FWD_WGS");
-        bwd_wgs = ec2_env_int("FSG_EC2S_BWD_WGS");
-    }
     const int tp2 = 64 / k, tp4 = 128 / k;
     const float u2 = tp2 * k / 64.f, u4 = tp4 * k / 128.f;
     RT = u4 > 1.15f * u2 ? 4 : 2;
     // the forward with three pieces per operand: 128-row tiles hold one workgroup per CU (82 KB of LDS) and lose more than the
     // padding costs (k = 40, 32 x 2048: 472 vs 545 us); the backward and the one-piece kernels keep the rule above
     if (!bwd && !bf16) RT = 2;
-    if (rt_env == 2 || rt_env == 4) RT = rt_env;
     TP = RT == 4 ? tp4 : tp2;
     if (TP < 1) TP = 1;
     if (TP > 16) TP = 16;      // the kernels stage a tile's Q rows with one 16-byte piece per thread
     const int ntiles = (N + TP - 1) / TP;
-    const int wgs = bwd ? (bwd_wgs > 0 ? bwd_wgs : 512) : (fwd_wgs > 0 ? fwd_wgs : 768);
-    G = wgs / (B > 0 ? B : 1);
+    G = (bwd ? 512 : 768) / (B > 0 ? B : 1);
     if (G < 1) G = 1;
     if (G > ntiles) G = ntiles;
 }
@@ -1190,13 +1173,7 @@ static size_t ec2s_bwd_lds(int NP, int RT, int TP) {
 }
 
 static void ec2_tiling(int k, int C2, int &TP, int &Rpad, int &G, int B, int N) {
-    static int rmax_env = -1;
-    if (rmax_env < 0) {
-        const char *e = getenv("FSG_EC2_FWD_RMAX");
-        rmax_env = e ? atoi(e) : 0;
-    }
-    const int rmax = rmax_env > 0 ? rmax_env : 64;   // measured: 64..128 rows/tile 160 us, 192 rows 191 us (C2 = 64)
-    TP = rmax / k;
+    TP = 64 / k;   // 64 edge rows per tile -- measured: 64..128 rows/tile 160 us, 192 rows 191 us (C2 = 64)
     if (TP < 1) TP = 1;
     Rpad = (TP * k + 31) & ~31;
     const int ntiles = (N + TP - 1) / TP;
@@ -1309,14 +1286,8 @@ extern "C" int fsg_edgeconv2_fwd_bf16(const float *pq, const int32_t *idx, const
 
 static void ec2_bwd_tiling(int k, int C2, int &TP, int &Rpad, int &G, int B, int N) {
     // 64 edge rows per tile: two row tiles x two column tiles = one MFMA pair per wave in every phase (balanced), and
-    // ~52 KB of LDS, i.e. three workgroups per CU (FSG_EC2_BWD_RMAX overrides for experiments)
-    static int rmax_env = -1;
-    if (rmax_env < 0) {
-        const char *e = getenv("FSG_EC2_BWD_RMAX");
-        rmax_env = e ? atoi(e) : 0;
-    }
-    const int rmax = rmax_env > 0 ? rmax_env : 64;
-    TP = rmax / k;
+    // ~52 KB of LDS, i.e. three workgroups per CU
+    TP = 64 / k;
     if (TP < 1) TP = 1;
     Rpad = (TP * k + 31) & ~31;
     const int ntiles = (N + TP - 1) / TP;

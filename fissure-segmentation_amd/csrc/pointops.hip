@@ -6,7 +6,6 @@
 // v0: one lane per query (kNN), one workgroup per cloud (FPS), lanes along channels (gather /
 // aggregate).  Distances use the direct form d = fma(dz,dz, fma(dy,dy, dx*dx)) like oracle/fsg_oracle.c.
 #include "knn_internal.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -79,48 +78,12 @@ __device__ __forceinline__ unsigned long long wave_argmax_key(float bv, int bj) 
     return ((unsigned long long)hi << 32) | lo;   // wave-uniform
 }
 
-// Farthest point sampling of one segment by ONE wave: the segment's points and running minimum distances live in
-// registers (PPL per lane, point j = start + lane + 64 r), the coordinates also in LDS so that the next pivot is a
-// broadcast LDS read instead of a dependent global load; an iteration is PPL distance updates + a 6-step shuffle
-// arg-max, no barrier.  Same arithmetic and tie rule (largest distance, lowest index) as the scalar reference.
-template <int PPL>
-__device__ __forceinline__ void fps_one_wave(const float *__restrict__ xyz, int st, int len, int qs, int qe,
-                                             int32_t *__restrict__ idx, float *lds) {
-    const int lane = threadIdx.x & 63;
-    float px[PPL], py[PPL], pz[PPL], md[PPL];
-#pragma unroll
-    for (int r = 0; r < PPL; ++r) {
-        const int j = lane + 64 * r;
-        const bool ok = j < len;
-        px[r] = ok ? xyz[3L * (st + j)] : 0.f;
-        py[r] = ok ? xyz[3L * (st + j) + 1] : 0.f;
-        pz[r] = ok ? xyz[3L * (st + j) + 2] : 0.f;
-        md[r] = 1e10f;
-        if (ok) { lds[3 * j] = px[r]; lds[3 * j + 1] = py[r]; lds[3 * j + 2] = pz[r]; }
-    }
-    __builtin_amdgcn_wave_barrier();
-    int cur = 0;  // local index of the pivot
-    if (lane == 0) idx[qs] = st;
-    for (int t = qs + 1; t < qe; ++t) {
-        const float cx = lds[3 * cur], cy = lds[3 * cur + 1], cz = lds[3 * cur + 2];
-        float bv = -1.f;
-        int bj = 0x7fffffff;
-#pragma unroll
-        for (int r = 0; r < PPL; ++r) {
-            const int j = lane + 64 * r;
-            const float d = sqdist3(px[r], py[r], pz[r], cx, cy, cz);
-            const float v = fminf(d, md[r]);
-            md[r] = v;
-            if (j < len && v > bv) { bv = v; bj = j; }
-        }
-        cur = 0x7fffffff - (int)(unsigned)wave_argmax_key(bv, bj);
-        if (lane == 0) idx[t] = st + cur;
-    }
-}
-
-// Same, one WORKGROUP of FW waves per segment (segments up to 64*FW*PPL points): every wave keeps PPL points per lane in
-// registers, the per-wave arg-max goes through LDS and one barrier per iteration.  Shorter serial chain than the
-// single-wave version for the 2048-point segments of BASELINE config 3 (4 instead of 32 distance updates per lane).
+// Farthest point sampling of one segment by one WORKGROUP of FW waves (segments up to 64*FW*PPL points): the segment's points
+// and running minimum distances live in registers (PPL per lane, point j = start + tid + 64 FW r), the coordinates also in
+// LDS so that the next pivot is a broadcast LDS read instead of a dependent global load; an iteration is PPL distance updates +
+// a 6-step DPP arg-max per wave, then the per-wave arg-max goes through LDS and one barrier.  Same arithmetic and tie rule
+// (largest distance, lowest index) as the scalar reference.  A single wave per segment was the first design: its serial
+// chain is 32 instead of 4 distance updates per lane for the 2048-point segments of BASELINE config 3.
 constexpr int FW = 8;
 template <int PPL>
 __device__ __forceinline__ void fps_multi_wave(const float *__restrict__ xyz, int st, int len, int qs, int qe,
@@ -187,24 +150,14 @@ __global__ __launch_bounds__(FW * 64) void fps_kernel_mw(const float *__restrict
 
 __global__ __launch_bounds__(BLOCK) void fps_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ offset,
                                                      const int32_t *__restrict__ new_offset, float *__restrict__ md,
-                                                     int32_t *__restrict__ idx, int mw_done) {
+                                                     int32_t *__restrict__ idx) {
     __shared__ float wv[BLOCK / 64];
     __shared__ int wj[BLOCK / 64];
-    __shared__ float pts[2048 * 3];
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int st = s ? offset[s - 1] : 0, en = offset[s];
     const int qs = s ? new_offset[s - 1] : 0, qe = new_offset[s];
-    if (qe > qs && en <= st && !mw_done)       // (see fps_kernel_mw, which has done it when it ran)
-        for (int t = qs + tid; t < qe; t += BLOCK) idx[t] = 0;
-    if (qe <= qs || en <= st) return;
-    if (en - st <= 2048) {
-        if (mw_done) return;   // already sampled by fps_kernel_mw (eight waves per segment)
-        // register-resident single-wave path (uniform per workgroup: the other waves just leave)
-        if (wave != 0) return;
-        if (en - st <= 512) fps_one_wave<8>(xyz, st, en - st, qs, qe, idx, pts);
-        else fps_one_wave<32>(xyz, st, en - st, qs, qe, idx, pts);
-        return;
-    }
+    // fps_kernel_mw, which always runs first, has sampled the segments of up to 2048 points and written index 0 for the empty ones
+    if (qe <= qs || en - st <= 2048) return;
     for (int j = st + tid; j < en; j += BLOCK) md[j] = 1e10f;
     int cur = st;
     if (tid == 0) idx[qs] = cur;
@@ -403,13 +356,9 @@ extern "C" int fsg_knn_segment_f32(const float *xyz, const float *new_xyz, const
     if (m == 0) return FSG_OK;
     hipStream_t st = (hipStream_t)stream;
     // production path: 32 queries per workgroup on the dense kNN's wave-cooperative selection (knn_rows_mfma.hip);
-    // the one-thread-per-query kernel below stays as the fallback (nsample > 32) and as a cross-check
-    // (FSG_KNN_SEGMENT_SCALAR=1)
-    static const bool scalar_only = getenv("FSG_KNN_SEGMENT_SCALAR") != nullptr;
-    if (!scalar_only) {
-        const int rc = fsg_knn_segment_rows_launch(xyz, new_xyz, offset, new_offset, b, n, m, nsample, idx, dist2, st);
-        if (rc != FSG_ERR_UNSUPPORTED) return rc;
-    }
+    // the one-thread-per-query kernel below stays as the fallback (nsample > 32)
+    const int rc = fsg_knn_segment_rows_launch(xyz, new_xyz, offset, new_offset, b, n, m, nsample, idx, dist2, st);
+    if (rc != FSG_ERR_UNSUPPORTED) return rc;
     dim3 grid(fsg_cdiv(m, BLOCK)), block(BLOCK);
 #define FSG_KNNSEG(NS) \
     hipLaunchKernelGGL(knn_segment_kernel<NS>, grid, block, 0, st, xyz, new_xyz, offset, new_offset, b, m, nsample, idx, dist2)
@@ -429,14 +378,10 @@ extern "C" int fsg_fps_f32(const float *xyz, const int32_t *offset, const int32_
     FSG_REQUIRE(b > 0 && n > 0, "fsg_fps_f32: bad shape b=%d n=%d", b, n);
     // segments of up to 2048 points: eight waves per segment, points in registers; longer ones: the generic kernel, which
     // skips what the first launch already sampled.  n <= 2048 means no segment can be longer: one launch.
-    static const bool one_wave = getenv("FSG_FPS_ONE_WAVE") != nullptr;   // cross-check: the single-wave path
-    if (!one_wave) {
-        hipLaunchKernelGGL(fps_kernel_mw, dim3(b), dim3(FW * 64), 0, (hipStream_t)stream, xyz, offset, new_offset, idx);
-        FSG_CHECK_LAUNCH("fsg_fps_f32/mw");
-    }
-    if (one_wave || n > 2048) {
-        hipLaunchKernelGGL(fps_kernel, dim3(b), dim3(BLOCK), 0, (hipStream_t)stream, xyz, offset, new_offset, tmp, idx,
-                           one_wave ? 0 : 1);
+    hipLaunchKernelGGL(fps_kernel_mw, dim3(b), dim3(FW * 64), 0, (hipStream_t)stream, xyz, offset, new_offset, idx);
+    FSG_CHECK_LAUNCH("fsg_fps_f32/mw");
+    if (n > 2048) {
+        hipLaunchKernelGGL(fps_kernel, dim3(b), dim3(BLOCK), 0, (hipStream_t)stream, xyz, offset, new_offset, tmp, idx);
         FSG_CHECK_LAUNCH("fsg_fps_f32");
     }
     return FSG_OK;

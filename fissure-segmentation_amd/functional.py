@@ -50,8 +50,11 @@ def no_autocast():
 
 # bf16 OPERAND MODE (BASELINE configs 3-5 name bf16 as their compute type).  What it changes: the operands of the dense
 # contractions -- the per-edge 64 x C2 product of the two-layer EdgeConv (fsg_edgeconv2_{fwd,bwd}_bf16 on
-# v_mfma_f32_32x32x16_bf16) and the point-wise / Linear GEMMs that go to the vendor library -- are rounded to bf16,
-# accumulation stays fp32.  What it never changes: the graph build (always fp32: indices equal the fp32 CPU path), BatchNorm
+# v_mfma_f32_32x32x16_bf16) and, with `set_bf16_linear(True)`, the Linear layers' products on the hand-written GEMMs -- are
+# rounded to bf16, accumulation stays fp32.  The products that go to the vendor library stay fp32: with bf16 operands every
+# call pays a cast pass over its fp32 activations and gradients, and the config-4 step was measured SLOWER on MI355X (4.64 vs
+# 4.17 ms); the hand-written kernels convert their operands on the way out of LDS at no extra traffic.
+# What the mode never changes: the graph build (always fp32: indices equal the fp32 CPU path), BatchNorm
 # statistics, selection, every stored activation and every gradient tensor (fp32).  Switched on explicitly
 # (`set_mfma_operands("bf16")` / `with mfma_operands("bf16")`) or by an ambient `torch.autocast("cuda", torch.bfloat16)`
 # around a model forward; the backward of every op follows the mode its forward ran in.
@@ -80,39 +83,8 @@ def bf16_operands():
     return _mfma_mode == "bf16"
 
 
-# The vendor GEMMs (point-wise head, Linear layers) can run with bf16 operands too, but every call then pays a cast pass
-# over its fp32 activations and gradients (all stored tensors stay fp32): measured on MI355X at the config-4 shape the
-# step got SLOWER (4.64 vs 4.17 ms), so this half of the mode is a separate opt-in (FSG_BF16_VENDOR_GEMM=1 /
-# `set_bf16_vendor_gemm(True)`); the hand-written kernels convert their operands on the way out of LDS at no extra traffic.
-_bf16_vendor = _os.environ.get("FSG_BF16_VENDOR_GEMM", "0") == "1"
-
-
-def set_bf16_vendor_gemm(flag):
-    global _bf16_vendor
-    _bf16_vendor = bool(flag)
-
-
-def _bf16_gemm():
-    return _mfma_mode == "bf16" and _bf16_vendor
-
-
 def _ambient_bf16():
     return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
-
-
-_MM_OUT_DTYPE = True
-
-
-def _bf16_mm(a, b):
-    """a (M,K) @ b (K,N) with bf16 operands and fp32 accumulation -> fp32 (vendor GEMM, hipBLASLt)"""
-    global _MM_OUT_DTYPE
-    a16, b16 = a.to(torch.bfloat16), b.to(torch.bfloat16)
-    if _MM_OUT_DTYPE:
-        try:
-            return torch.mm(a16, b16, out_dtype=torch.float32)
-        except (TypeError, RuntimeError):
-            _MM_OUT_DTYPE = False
-    return torch.mm(a16, b16).float()
 
 
 _deterministic = bool(_os.environ.get("FSG_DETERMINISTIC"))
@@ -169,8 +141,8 @@ def knn_graph(x, k, c_knn=None, fix_diag=True, drop_first=False, return_dist=Fal
             _lib.call("fsg_knn_dense_prepared_f32", _p(x_pm), B, N, C, k, flags, _p(idx), None, _p(ws), ws.numel() * ws.element_size(),
                       _stream())
         return idx
-    ws_bytes = _lib.lib.fsg_knn_dense_workspace_bytes(B, N, c_knn)
-    xx = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x.device)
+    xx = _lib.workspace("fsg_knn_dense", B, N, c_knn, device=x.device)
+    ws_bytes = xx.numel() if xx is not None else 0
     if pq_weight is not None:
         rows = pq_weight.shape[0]
         if (C == c_knn and c_knn <= 4 and tuple(pq_weight.shape) == (rows, C) and 256 % rows == 0 and not return_dist and
@@ -237,10 +209,9 @@ def knn_edge_features(x, k, knn_only_over_coords=False):
     idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
     edge = torch.empty(B, 2 * C, N, k, dtype=torch.float32, device=x.device)
     c_knn = 3 if knn_only_over_coords else C
-    ws_bytes = _lib.lib.fsg_knn_dense_workspace_bytes(B, N, c_knn)
-    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x.device)
+    ws = _lib.workspace("fsg_knn_dense", B, N, c_knn, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.call("fsg_knn_gather_fused_ws_f32", _p(xc), B, C, N, k, c_knn, _p(idx), _p(edge), _p(ws), ws_bytes, _stream())
+        _lib.call("fsg_knn_gather_fused_ws_f32", _p(xc), B, C, N, k, c_knn, _p(idx), _p(edge), _p(ws), ws.numel(), _stream())
     return edge, idx
 
 
@@ -264,8 +235,7 @@ def gemm_small(a, sa_i, sa_k, b, sb_k, sb_j, bias, I, J, K, rowsum=False, defer=
     the returned tensors are complete when `loss.backward()` returns -- for weight gradients, which nothing reads before.
     bf16=True: operands rounded to bf16 inside the kernel, bf16 matrix instruction, fp32 accumulation (fsg_gemm_small_bf16)."""
     out = torch.empty(I, J, dtype=torch.float32, device=a.device)
-    nbytes = _lib.lib.fsg_gemm_small_workspace_bytes(I, J, K)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device) if nbytes else None
+    ws = _lib.workspace("fsg_gemm_small", I, J, K, device=a.device)
     rs = torch.empty(I, dtype=torch.float32, device=a.device) if rowsum else None
     with torch.cuda.device(a.device):
         if defer and bias is None:
@@ -364,7 +334,7 @@ class _LinearPM(torch.autograd.Function):
     def forward(ctx, x, w, b):
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
-        ctx.bf16 = ctx.pw16 = False
+        ctx.pw16 = False
         tw, tb = _grad_targets(w), (_grad_targets(b) if b is not None else ())
         ctx.defer_targets = tw + tb if (tw is not None and tb is not None) else None
         x2 = x.reshape(-1, x.shape[-1])
@@ -383,12 +353,6 @@ class _LinearPM(torch.autograd.Function):
             y = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)      # final shape: no view leaves the Function
             pw_linear_bf16(x2, w, b, out=y.view(-1, N))
             return y
-        ctx.bf16 = _bf16_gemm() and x.is_cuda
-        if ctx.bf16:
-            y = _bf16_mm(x2, w.t())
-            if b is not None:
-                y += b
-            return y.view(*x.shape[:-1], N)
         return torch.nn.functional.linear(x, w, b)
 
     @staticmethod
@@ -423,10 +387,10 @@ class _LinearPM(torch.autograd.Function):
                 gb = _bias_grad(g2)
             return gx, gw, gb
         if ctx.needs_input_grad[0]:
-            gx = _linear_dx(g2, w, bf16=ctx.bf16).view_as(x)
+            gx = _linear_dx(g2, w).view_as(x)
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            gw = _linear_dw(g2, x2, bf16=ctx.bf16, with_bias_grad=want_gb, defer=_may_defer(ctx.defer_targets))
+            gw = _linear_dw(g2, x2, with_bias_grad=want_gb, defer=_may_defer(ctx.defer_targets))
             if isinstance(gw, tuple):      # the small-GEMM path hands the bias gradient (row sums of dY^T) over with the product
                 gw, gb = gw
         if want_gb and gb is None:
@@ -434,26 +398,21 @@ class _LinearPM(torch.autograd.Function):
         return gx, gw, gb
 
 
-def _linear_dx(g2, w, out=None, bf16=False):
+def _linear_dx(g2, w, out=None):
     """dX = dY W for dY (M,N), W (N,K); `out`: accumulate into an existing (M,K) gradient instead (one GEMM with beta = 1)"""
     N, K = w.shape
     M = g2.shape[0]
-    if bf16:
-        r = _bf16_mm(g2, w)
-        return r if out is None else out.add_(r)
     if out is not None:
         return out.addmm_(g2, w)
     return gemm_small(g2, N, 1, w, K, 1, None, M, K, N) if _small(M, K, N, g2, w) else g2 @ w
 
 
-def _linear_dw(g2, x2, bf16=False, with_bias_grad=False, defer=False):
+def _linear_dw(g2, x2, with_bias_grad=False, defer=False):
     """dW = dY^T X: a tiny output behind a long reduction (see _LinearPM).  with_bias_grad: the small-GEMM path returns
     (dW, db) -- db = column sums of dY as a by-product of the same launch; the other paths return dW alone.
     defer: the caller knows that nothing reads the result inside this backward pass (gemm_small(defer=True))"""
     M, N = g2.shape
     K = x2.shape[1]
-    if bf16:
-        return _bf16_mm(g2.t(), x2)
     S = 16 if (M % 16 == 0 and M >= 4096) else 1
     if _small(N, K, M, g2, x2):
         return gemm_small(g2, 1, N, x2, K, 1, None, N, K, M, rowsum=with_bias_grad, defer=defer)
@@ -518,10 +477,6 @@ class _LinearPM2(torch.autograd.Function):
     def forward(ctx, x, w1, w2):
         ctx.save_for_backward(x, w1, w2)
         x2 = x.reshape(-1, x.shape[-1])
-        ctx.bf16 = _bf16_gemm() and x.is_cuda
-        if ctx.bf16:
-            x16 = x2.to(torch.bfloat16)
-            return _bf16_mm(x16, w1.t()), _bf16_mm(x16, w2.t())
         return torch.nn.functional.linear(x2, w1), torch.nn.functional.linear(x2, w2)
 
     @staticmethod
@@ -534,10 +489,10 @@ class _LinearPM2(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             for g, w in zip(gs, (w1, w2)):
                 if g is not None:
-                    gx = _linear_dx(g, w, bf16=ctx.bf16) if gx is None else _linear_dx(g, w, out=gx, bf16=ctx.bf16)
+                    gx = _linear_dx(g, w) if gx is None else _linear_dx(g, w, out=gx)
             gx = gx.view_as(x) if gx is not None else None
-        gw1 = _linear_dw(gs[0], x2, bf16=ctx.bf16) if (gs[0] is not None and ctx.needs_input_grad[1]) else None
-        gw2 = _linear_dw(gs[1], x2, bf16=ctx.bf16) if (gs[1] is not None and ctx.needs_input_grad[2]) else None
+        gw1 = _linear_dw(gs[0], x2) if (gs[0] is not None and ctx.needs_input_grad[1]) else None
+        gw2 = _linear_dw(gs[1], x2) if (gs[1] is not None and ctx.needs_input_grad[2]) else None
         return gx, gw1, gw2
 
 
@@ -616,11 +571,7 @@ class _LinearReLU(torch.autograd.Function):
     @_amp_fwd
     def forward(ctx, x, w, b):
         x2 = x.reshape(-1, x.shape[-1])
-        ctx.bf16 = _bf16_gemm() and x.is_cuda
-        if ctx.bf16:
-            out = torch.relu_(_bf16_mm(x2, w.t()).add_(b))
-        else:
-            out = torch._addmm_activation(b, x2, w.t(), use_gelu=False)
+        out = torch._addmm_activation(b, x2, w.t(), use_gelu=False)
         ctx.save_for_backward(x, w, out)
         return out.view(*x.shape[:-1], w.shape[0])
 
@@ -630,8 +581,8 @@ class _LinearReLU(torch.autograd.Function):
         x, w, out = ctx.saved_tensors
         g2 = torch.ops.aten.threshold_backward(g.reshape(-1, g.shape[-1]).contiguous(), out, 0)
         x2 = x.reshape(-1, x.shape[-1])
-        gx = _linear_dx(g2, w, bf16=ctx.bf16).view_as(x) if ctx.needs_input_grad[0] else None
-        gw = _linear_dw(g2, x2, bf16=ctx.bf16) if ctx.needs_input_grad[1] else None
+        gx = _linear_dx(g2, w).view_as(x) if ctx.needs_input_grad[0] else None
+        gw = _linear_dw(g2, x2) if ctx.needs_input_grad[1] else None
         gb = _bias_grad(g2) if ctx.needs_input_grad[2] else None
         return gx, gw, gb
 
@@ -803,26 +754,37 @@ def with_deferred_bn_counters(forward):
     return wrapped
 
 
+def _bn_step(bn):
+    """training flag + momentum of one BatchNorm module for this call (bumps num_batches_tracked like torch)."""
+    training = bn.training or bn.running_mean is None
+    momentum = 0.0
+    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        momentum = bump_bn_counter(bn)
+    return training, float(momentum)
+
+
+def _bn_args(bn):
+    """one BatchNorm module -> (weight, bias, running_mean | None, running_var | None, training, momentum, eps) of this call:
+    the running statistics are handed on when the call updates them (training, tracked) or reads them (eval)"""
+    training, momentum = _bn_step(bn)
+    stats = bn.track_running_stats or not training
+    return (bn.weight, bn.bias, bn.running_mean if stats else None, bn.running_var if stats else None, training, momentum,
+            float(bn.eps))
+
+
+def _bn_eval_stats(rm, rv, eps):
+    """(mean, invstd) of an eval-mode BatchNorm from its running statistics"""
+    return rm.detach().float().contiguous(), torch.rsqrt(rv.detach().float() + eps).contiguous()
+
+
 # ------------------------------------------------------------------ fused EdgeConv (models/dgcnn.py:234-241)
-
-# Building the reverse graphs on a side stream during the forward was MEASURED SLOWER inside the replayed hipGraph
-# (2.06 vs 1.83 ms/step on MI355X: the fork/join edges cost more than the ~30 us builder hides), so it is opt-in.
-_ASYNC_CSR = _os.environ.get("FSG_ASYNC_CSR", "0") == "1"
-_side_streams = {}
-
-
-def _side_stream(device):
-    st = _side_streams.get(device)
-    if st is None:
-        st = _side_streams[device] = torch.cuda.Stream(device=device)
-    return st
-
-
+# (the reverse graphs are built on the main stream: building them on a side stream during the forward was MEASURED SLOWER inside
+# the replayed hipGraph -- 2.06 vs 1.83 ms/step on MI355X: the fork/join edges cost more than the ~30 us builder hides)
 def _build_csr(idx):
     B, N, k = idx.shape
     rowptr = torch.empty(B, N + 1, dtype=torch.int32, device=idx.device)
     col = torch.empty(B, N * k, dtype=torch.int32, device=idx.device)
-    ws = torch.empty(_lib.lib.fsg_graph_reverse_csr_workspace_bytes(B, N, k) // 4, dtype=torch.int32, device=idx.device)
+    ws = _lib.workspace("fsg_graph_reverse_csr", B, N, k, device=idx.device)
     with torch.cuda.device(idx.device):
         _lib.call("fsg_graph_reverse_csr", _p(idx), B, N, k, _p(rowptr), _p(col), _p(ws), _stream())
     return rowptr, col
@@ -833,7 +795,7 @@ def knn_prep_workspace(B, N, C, device):
     knn_graph(..., prepared=(ws, x_pm))); None when the shape is outside the prepared path (then build the graph as usual)"""
     if C != 64 or N % 64 != 0 or not (1024 <= N <= 8192):
         return None
-    return torch.empty(_lib.lib.fsg_knn_dense_workspace_bytes(B, N, C), dtype=torch.uint8, device=device)
+    return _lib.workspace("fsg_knn_dense", B, N, C, device=device)
 
 
 def build_reverse_graphs(graphs):
@@ -854,38 +816,11 @@ def build_reverse_graphs(graphs):
         g._fsg_csr = (rowptr[i * B:(i + 1) * B], col[i * B:(i + 1) * B])
 
 
-def prefetch_reverse_graph(idx):
-    """Start building the reverse graph of `idx` on a side stream (the builder runs 8 workgroups: ~30 us of an otherwise
-    idle GPU if it sat on the main stream).  The backward joins the side stream before its first use; inside a hipGraph
-    capture this becomes a parallel branch.  Only called when a backward pass will follow."""
-    if getattr(idx, "_fsg_csr", None) is not None or getattr(idx, "_fsg_csr_pending", None) is not None:
-        return
-    main = torch.cuda.current_stream(idx.device)
-    side = _side_stream(idx.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        rowptr, col = _build_csr(idx)
-        done = torch.cuda.Event()
-        done.record(side)
-    for t in (rowptr, col):
-        t.record_stream(main)
-    idx.record_stream(side)
-    idx._fsg_csr_pending = (rowptr, col, done)
-
-
 def reverse_graph(idx):
     """CSR-by-destination of a kNN graph, cached on the index tensor (a static graph is shared by all layers)."""
     cached = getattr(idx, "_fsg_csr", None)
     if cached is None:
-        pending = getattr(idx, "_fsg_csr_pending", None)
-        if pending is not None:
-            rowptr, col, done = pending
-            torch.cuda.current_stream(idx.device).wait_event(done)
-            idx._fsg_csr_pending = None
-            cached = (rowptr, col)
-        else:
-            cached = _build_csr(idx)
-        idx._fsg_csr = cached
+        cached = idx._fsg_csr = _build_csr(idx)
     return cached
 
 
@@ -933,11 +868,10 @@ class _EdgeConv1(torch.autograd.Function):
             ssum = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
             mean = torch.empty(Co, dtype=torch.float32, device=dev)
             invstd = torch.empty(Co, dtype=torch.float32, device=dev)
-            ws = torch.empty(_lib.lib.fsg_edgeconv1_workspace_bytes(B, N, Co) // 4, dtype=torch.float32, device=dev)
+            ws = _lib.workspace("fsg_edgeconv1", B, N, Co, device=dev)
         else:
             ssum, ws = None, None
-            mean = running_mean.detach().float().contiguous()
-            invstd = torch.rsqrt(running_var.detach().float() + eps).contiguous()
+            mean, invstd = _bn_eval_stats(running_mean, running_var, eps)
         with torch.cuda.device(dev):
             _lib.call("fsg_edgeconv1_fwd_f32", _p(pq), _p(idx), _p(gamma), _p(beta),
                       _p(running_mean if training else None), _p(running_var if training else None), B, N, k, Co,
@@ -996,20 +930,11 @@ def edgeconv1(x, idx, conv_weight, bn, slope, x_pm=None, both=False, w_cat=None,
         pq = _LinearPMGiven.apply(x_pm.to(torch.float32), w_cat, pq_given)
     else:
         pq = linear_pm(x_pm.to(torch.float32).contiguous(), w_cat)               # (B,N,2Co): one plain GEMM
-    training = bn.training or bn.running_mean is None
-    momentum = 0.0
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        momentum = bump_bn_counter(bn)
-    track = training and bn.track_running_stats
+    bn_args = _bn_args(bn)
     if idx.dtype != torch.int32:
         idx = idx.to(torch.int32)
     idx = idx.contiguous()
-    if torch.is_grad_enabled() and pq.requires_grad and _ASYNC_CSR:
-        prefetch_reverse_graph(idx)
-    res = _EdgeConv1.apply(pq, idx, bn.weight, bn.bias,
-                           bn.running_mean if (track or not training) else None,
-                           bn.running_var if (track or not training) else None, training, float(momentum),
-                           float(bn.eps), float(slope), knn_ws, w_next if knn_ws is not None else None)
+    res = _EdgeConv1.apply(pq, idx, *bn_args, float(slope), knn_ws, w_next if knn_ws is not None else None)
     return _edgeconv_outputs(res, both, w_next is not None)
 
 
@@ -1032,9 +957,9 @@ class _EdgeConv2(torch.autograd.Function):
             mean1, invstd1, mean2, invstd2 = new(64), new(64), new(C2), new(C2)
         else:
             ssum1 = ssum2 = None
-            mean1, invstd1 = rm1.detach().float().contiguous(), torch.rsqrt(rv1.detach().float() + eps1).contiguous()
-            mean2, invstd2 = rm2.detach().float().contiguous(), torch.rsqrt(rv2.detach().float() + eps2).contiguous()
-        ws = new(_lib.lib.fsg_edgeconv2_workspace_bytes(B, N, k, C2), dtype=torch.uint8)
+            mean1, invstd1 = _bn_eval_stats(rm1, rv1, eps1)
+            mean2, invstd2 = _bn_eval_stats(rm2, rv2, eps2)
+        ws = _lib.workspace("fsg_edgeconv2", B, N, k, C2, device=dev)
         t = bool(training)
         ctx.bf16 = bf16_operands()
         with torch.cuda.device(dev):
@@ -1065,7 +990,7 @@ class _EdgeConv2(torch.autograd.Function):
         gpq, gw2 = torch.empty_like(pq), torch.empty_like(w2)
         dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
         dg2, db2 = torch.empty_like(g2), torch.empty_like(b2)
-        ws = torch.empty(_lib.lib.fsg_edgeconv2_bwd_workspace_bytes(B, N, k, C2), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace("fsg_edgeconv2_bwd", B, N, k, C2, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_edgeconv2_bwd_bf16" if ctx.bf16 else "fsg_edgeconv2_bwd_f32", _p(g), _p(g_pm), ld1, _p(g_pm2), ld2,
                       _p(pq), _p(idx), _p(rowptr), _p(col),
@@ -1078,15 +1003,6 @@ class _EdgeConv2(torch.autograd.Function):
 
 def edgeconv2_supported(c_mid, c_out, k):
     return c_mid == 64 and c_out in (64, 128) and k <= 64
-
-
-def _bn_step(bn):
-    """training flag + momentum of one BatchNorm module for this call (bumps num_batches_tracked like torch)."""
-    training = bn.training or bn.running_mean is None
-    momentum = 0.0
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        momentum = bump_bn_counter(bn)
-    return training, float(momentum)
 
 
 def _edgeconv_outputs(res, both, want_pq_next):
@@ -1127,8 +1043,6 @@ def edgeconv2(x, idx, conv1_weight, bn1, conv2_weight, bn2, slope, x_pm=None, bo
     if idx.dtype != torch.int32:
         idx = idx.to(torch.int32)
     idx = idx.contiguous()
-    if torch.is_grad_enabled() and pq.requires_grad and _ASYNC_CSR:
-        prefetch_reverse_graph(idx)
     res = _EdgeConv2.apply(pq, idx, w2, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
                            bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, t1, m1, m2,
                            float(bn1.eps), float(bn2.eps), float(slope), knn_ws, w_next if knn_ws is not None else None)
@@ -1174,9 +1088,9 @@ def pw_weight_images(specs):
 # bf16 operands for the nn.Linear products (forward, dX, dW on fsg_pw_linear_bf16 / fsg_pw_tn_bf16) are a SEPARATE opt-in of the
 # bf16 mode: measured on the PointTransformer (BASELINE config 3, 2 x 2048 points against the fp32 oracle) they cost accuracy --
 # mean |logit error| 0.095, max 0.86, parameter-gradient cosine 0.36 through its 60 BatchNorms and 18 softmax layers -- and time
-# (9.0 vs 8.3 ms per step: three more small launches per Linear).  FSG_BF16_LINEAR=1 / set_bf16_linear(True) /
-# bench.py --workload c3 --dtype bf16 switch them on.
-_bf16_linear = _os.environ.get("FSG_BF16_LINEAR", "0") == "1"
+# (9.0 vs 8.3 ms per step: three more small launches per Linear).  set_bf16_linear(True) / bench.py --workload c3 --dtype bf16
+# switch them on.
+_bf16_linear = False
 
 
 def set_bf16_linear(flag):
@@ -1220,11 +1134,10 @@ def pw_tn_bf16(g, x, rows_per_slice=None):
     a.L1, a.ldl1, a.N1a, a.N1b, a.lpro = g.data_ptr(), g.stride(0), N, 0, 0
     a.R, a.ldr, a.N2, a.rpro = x.data_ptr(), x.stride(0), K, 0
     a.M, a.rows_per_cloud, a.rows_per_slice = M, 0, rows_per_slice
-    nbytes = _lib.lib.fsg_pw_tn_workspace_bytes(N, K, M, rows_per_slice)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("fsg_pw_tn", N, K, M, rows_per_slice, device=dev)
     out = torch.empty(N, K, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.call("fsg_pw_tn_bf16", ctypes.byref(a), 3, _p(ws), nbytes, _p(out), K, _stream())
+        _lib.call("fsg_pw_tn_bf16", ctypes.byref(a), 3, _p(ws), ws.numel(), _p(out), K, _stream())
     return out
 
 
@@ -1273,13 +1186,12 @@ def pw_tn(tile, C1, ldc1, C2=None, ldc2=0, defer=None, **kw):
         setattr(a, k, v)
     dev = C1.device
     N1 = a.N1a + a.N1b + (1 if a.ones else 0)
-    nbytes = _lib.lib.fsg_pw_tn_workspace_bytes(N1, a.N2, a.M, a.rows_per_slice)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("fsg_pw_tn", N1, a.N2, a.M, a.rows_per_slice, device=dev)
     with torch.cuda.device(dev):
         if defer is None:
-            _lib.call("fsg_pw_tn_f32", ctypes.byref(a), tile, _p(ws), nbytes, _p(C1), ldc1, _p(C2), ldc2, _stream())
+            _lib.call("fsg_pw_tn_f32", ctypes.byref(a), tile, _p(ws), ws.numel(), _p(C1), ldc1, _p(C2), ldc2, _stream())
         else:
-            _lib.call("fsg_pw_tn_f32", ctypes.byref(a), tile, _p(ws), nbytes, None, 0, None, 0, _stream())
+            _lib.call("fsg_pw_tn_f32", ctypes.byref(a), tile, _p(ws), ws.numel(), None, 0, None, 0, _stream())
             defer.append((ws, C1, ldc1, C2, ldc2, (a.M + a.rows_per_slice - 1) // a.rows_per_slice, N1, a.N2, a.N1a))
 
 
@@ -1311,8 +1223,7 @@ def _pw_bn_finalize(rec, R, ldn, c0, C, shift, B, bn, training, momentum, with_e
         track = bn.track_running_stats and bn.running_mean is not None
         rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
     else:
-        mean = bn.running_mean.detach().float().contiguous()
-        invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps).contiguous()
+        mean, invstd = _bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
         rm = rv = None
     with torch.cuda.device(dev):
         _lib.call("fsg_pw_bn_finalize_f32", _p(rec), R, ldn, c0, C, _p(shift), B, int(training), _p(bn.weight), _p(bn.bias),
@@ -1376,8 +1287,7 @@ class _SegHead(torch.autograd.Function):
             track = bn_g.track_running_stats and bn_g.running_mean is not None
             rm_g, rv_g = (bn_g.running_mean, bn_g.running_var) if track else (None, None)
         else:
-            mean_g = bn_g.running_mean.detach().float().contiguous()
-            inv_g = torch.rsqrt(bn_g.running_var.detach().float() + bn_g.eps).contiguous()
+            mean_g, inv_g = _bn_eval_stats(bn_g.running_mean, bn_g.running_var, bn_g.eps)
             rm_g = rv_g = None
         with torch.cuda.device(dev):
             _lib.call("fsg_pw_bn_finalize_max_f32", _p(rec0), R0, CG + C0, 0, CG, B, int(tr_g), _p(bn_g.weight), _p(bn_g.bias),
@@ -1496,10 +1406,13 @@ class _SegHead(torch.autograd.Function):
               M=M, rows_per_cloud=Npts, rows_per_slice=_tn_rps(M))
         pw_tn_reduce(folds)             # dW3, dW2, dW1, [dW0_levels ; G]
         dlv = torch.empty(M, KL, **f32)
-        pw_rowgemm(PRO_BNBWD, PW_STORE | PW_BIAS, 5 if (_PW_WIDE and KL == 192) else 4, A1=da0, Y1=y0, A2=levels, lda1=C0, lda2=levels.stride(0), K1=C0, K2=KL,
+        # the 64 x 192 tile (5) for the (B N, 448) x (448, 192) input-gradient product of the first head layer: its BatchNorm-backward
+        # prologue + split is then done once per row instead of once per column tile (38.8 -> 33.1 us).  The 64 x 256 tile for the
+        # 256-wide products was measured SLOWER (24.9 vs 20.7 us, 25.5 vs 21.3 us: 120 KB of LDS = one workgroup per CU)
+        pw_rowgemm(PRO_BNBWD, PW_STORE | PW_BIAS, 5 if KL == 192 else 4, A1=da0, Y1=y0, A2=levels, lda1=C0, lda2=levels.stride(0), K1=C0, K2=KL,
                    Bimg=img_lv, M=M, N=KL, rows_per_cloud=Npts, alpha=al_0, delta=de_0, P=P0, Q=Q0, tstride=C0, slope=slope,
                    C=dlv, ldc=KL, store_n0=0, bias=npvec)
-        sws = torch.empty(_lib.lib.fsg_pw_scatter_rows_workspace_bytes(B, CG) // 4, dtype=torch.int32, device=dev)
+        sws = _lib.workspace("fsg_pw_scatter_rows", B, CG, device=dev)
         call("fsg_pw_scatter_rows_f32", _p(coef), _p(arg), _p(Wg), Wg.stride(0), B, CG, KL, Npts, _p(dlv), KL, _p(sws))
         dWg = torch.empty(CG, KL, **f32)
         call("fsg_pw_gf_dw_f32", _p(coef), _p(arg), _p(levels), levels.stride(0), _p(s), _p(Wg), Wg.stride(0), _p(G), _p(Pg), _p(Qg),
@@ -1507,21 +1420,14 @@ class _SegHead(torch.autograd.Function):
         return (dlv, None, None, None, None, None, dWg, dgg, dbg, dW0, dg0, db0, dW1, dg1, db1, dW2, dg2, db2, dW3, db3)
 
 
-_fused_head = _os.environ.get("FSG_FUSED_HEAD", "1") != "0"
-_TN_RPS = int(_os.environ.get("FSG_TN_RPS", "0"))        # rows per slice of the weight-gradient contractions (0: by size; tuning knob)
+_fused_head = True
 
 
 def _tn_rps(M):
     """rows per slice of the head's weight-gradient contractions: 128 up to 16384 rows (512 workgroups per product, two resident per
     CU: config 2 0.956 vs 0.960 ms per step at 256, 1.005 at 64), 256 above (config 4: 2.07 vs 2.10 ms at 128; 32 x 2048 static:
     3.19 vs 3.24 -- twice the partial products to write and fold)"""
-    return _TN_RPS if _TN_RPS > 0 else (128 if M <= 16384 else 256)
-
-
-# the 64 x 192 tile for the (B N, 448) x (448, 192) input-gradient product of the first head layer: its BatchNorm-backward
-# prologue + split is then done once per row instead of once per column tile (38.8 -> 33.1 us).  The 64 x 256 tile for the
-# 256-wide products was measured SLOWER (24.9 vs 20.7 us, 25.5 vs 21.3 us: 120 KB of LDS = one workgroup per CU)
-_PW_WIDE = _os.environ.get("FSG_PW_WIDE", "1") != "0"
+    return 128 if M <= 16384 else 256
 
 
 def set_fused_head(flag):
@@ -1578,9 +1484,9 @@ class _BNAct(torch.autograd.Function):
         if training:
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             invstd = torch.empty(C, dtype=torch.float32, device=dev)
-            ws = torch.empty(_lib.lib.fsg_bn_act_workspace_bytes(M, C) // 4, dtype=torch.float32, device=dev)
+            ws = _lib.workspace("fsg_bn_act", M, C, device=dev)
         else:
-            mean, invstd, ws = rm.detach().float().contiguous(), torch.rsqrt(rv.detach().float() + eps).contiguous(), None
+            (mean, invstd), ws = _bn_eval_stats(rm, rv, eps), None
         with torch.cuda.device(dev):
             _lib.call("fsg_bn_act_fwd_f32", _p(y), _p(gamma), _p(beta), _p(rm if training else None),
                       _p(rv if training else None), M, C, int(training), momentum, eps, slope, _p(out), _p(mean),
@@ -1597,7 +1503,7 @@ class _BNAct(torch.autograd.Function):
         g = _f32c(g)
         gy = torch.empty_like(y)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws = torch.empty(_lib.lib.fsg_bn_act_workspace_bytes(M, C) // 4, dtype=torch.float32, device=y.device)
+        ws = _lib.workspace("fsg_bn_act", M, C, device=y.device)
         with torch.cuda.device(y.device):
             _lib.call("fsg_bn_act_bwd_f32", _p(g), _p(y), _p(gamma), _p(beta), _p(mean), _p(invstd), M, C, int(training),
                       slope, _p(gy), _p(dgamma), _p(dbeta), _p(ws), _stream())
@@ -1618,8 +1524,8 @@ class _BNActMax(torch.autograd.Function):
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             invstd = torch.empty(C, dtype=torch.float32, device=dev)
         else:
-            mean, invstd = rm.detach().float().contiguous(), torch.rsqrt(rv.detach().float() + eps).contiguous()
-        ws = torch.empty(_lib.lib.fsg_bn_act_max_workspace_bytes(B, N, C) // 4, dtype=torch.float32, device=dev)
+            mean, invstd = _bn_eval_stats(rm, rv, eps)
+        ws = _lib.workspace("fsg_bn_act_max", B, N, C, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_bn_act_max_fwd_f32", _p(y), _p(gamma), _p(beta), _p(rm if training else None),
                       _p(rv if training else None), B, N, C, int(training), momentum, eps, slope, _p(out), _p(ysel),
@@ -1645,11 +1551,7 @@ class _BNActMax(torch.autograd.Function):
 def bn_act_max(y, bn, slope):
     """max over dim 1 of LeakyReLU(slope)(BatchNorm(y)) for y (B, N, C) -> (B, C), without the (B,N,C) activation."""
     _need_gpu(y)
-    training, momentum = _bn_step(bn)
-    track = training and bn.track_running_stats
-    return _BNActMax.apply(y, bn.weight, bn.bias, bn.running_mean if (track or not training) else None,
-                           bn.running_var if (track or not training) else None, training, momentum, float(bn.eps),
-                           float(slope))
+    return _BNActMax.apply(y, *_bn_args(bn), float(slope))
 
 
 class _BNActMaxAvg(torch.autograd.Function):
@@ -1665,8 +1567,8 @@ class _BNActMaxAvg(torch.autograd.Function):
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             invstd = torch.empty(C, dtype=torch.float32, device=dev)
         else:
-            mean, invstd = rm.detach().float().contiguous(), torch.rsqrt(rv.detach().float() + eps).contiguous()
-        ws = torch.empty(_lib.lib.fsg_bn_act_maxavg_workspace_bytes(B, N, C) // 4, dtype=torch.float32, device=dev)
+            mean, invstd = _bn_eval_stats(rm, rv, eps)
+        ws = _lib.workspace("fsg_bn_act_maxavg", B, N, C, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_bn_act_maxavg_fwd_f32", _p(y), _p(gamma), _p(beta), _p(rm if training else None),
                       _p(rv if training else None), B, N, C, int(training), momentum, eps, slope, _p(out), _p(arg),
@@ -1683,7 +1585,7 @@ class _BNActMaxAvg(torch.autograd.Function):
         g = _f32c(g)
         gy = torch.empty_like(y)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws = torch.empty(_lib.lib.fsg_bn_act_maxavg_workspace_bytes(B, N, C) // 4, dtype=torch.float32, device=y.device)
+        ws = _lib.workspace("fsg_bn_act_maxavg", B, N, C, device=y.device)
         with torch.cuda.device(y.device):
             _lib.call("fsg_bn_act_maxavg_bwd_f32", _p(g), _p(y), _p(arg), _p(gamma), _p(beta), _p(mean), _p(invstd),
                       B, N, C, int(training), slope, _p(gy), _p(dgamma), _p(dbeta), _p(ws), _stream())
@@ -1694,11 +1596,7 @@ def bn_act_maxavg(y, bn, slope):
     """cat(max, mean) over dim 1 of LeakyReLU(slope)(BatchNorm(y)) for y (B, N, C) -> (B, 2C), without the (B,N,C)
     activation (models/dgcnn_opensrc.py:158-164)."""
     _need_gpu(y)
-    training, momentum = _bn_step(bn)
-    track = training and bn.track_running_stats
-    return _BNActMaxAvg.apply(y, bn.weight, bn.bias, bn.running_mean if (track or not training) else None,
-                              bn.running_var if (track or not training) else None, training, momentum, float(bn.eps),
-                              float(slope))
+    return _BNActMaxAvg.apply(y, *_bn_args(bn), float(slope))
 
 
 def bn_act_supported(y, bn):
@@ -1708,11 +1606,7 @@ def bn_act_supported(y, bn):
 def bn_act(y, bn, slope):
     """LeakyReLU(slope)(BatchNorm1d(y)) for point-major rows y (M, C): one fused HIP stage (slope 1: BN only)."""
     _need_gpu(y)
-    training, momentum = _bn_step(bn)
-    track = training and bn.track_running_stats
-    return _BNAct.apply(y, bn.weight, bn.bias, bn.running_mean if (track or not training) else None,
-                        bn.running_var if (track or not training) else None, training, momentum, float(bn.eps),
-                        float(slope))
+    return _BNAct.apply(y, *_bn_args(bn), float(slope))
 
 
 # ------------------------------------------------------------------ BatchNorm (+ residual) (+ ReLU) over packed rows
@@ -1729,9 +1623,9 @@ class _BNRows(torch.autograd.Function):
         if training:
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             rstd = torch.empty(C, dtype=torch.float32, device=dev)
-            ws = torch.empty(_lib.lib.fsg_bn_rows_workspace_bytes(M, C) // 8, dtype=torch.float64, device=dev)
+            ws = _lib.workspace("fsg_bn_rows", M, C, device=dev)
         else:
-            mean, rstd, ws = rm.detach().float().contiguous(), torch.rsqrt(rv.detach().float() + eps).contiguous(), None
+            (mean, rstd), ws = _bn_eval_stats(rm, rv, eps), None
         with torch.cuda.device(dev):
             _lib.call("fsg_bn_rows_fwd_f32", _p(x), _p(res), _p(gamma), _p(beta), _p(rm if training else None),
                       _p(rv if training else None), M, C, int(training), momentum, eps, int(relu), _p(out), _p(mean),
@@ -1749,7 +1643,7 @@ class _BNRows(torch.autograd.Function):
         gx = torch.empty_like(x)
         gres = torch.empty_like(x) if has_res else None
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
-        ws = torch.empty(_lib.lib.fsg_bn_rows_workspace_bytes(M, C) // 8, dtype=torch.float64, device=x.device)
+        ws = _lib.workspace("fsg_bn_rows", M, C, device=x.device)
         with torch.cuda.device(x.device):
             _lib.call("fsg_bn_rows_bwd_f32", _p(g), _p(x), _p(out), _p(gamma), _p(mean), _p(rstd), M, C, int(training),
                       int(relu), _p(gx), _p(gres), _p(dgamma), _p(dbeta), _p(ws), _stream())
@@ -1765,13 +1659,11 @@ def bn_rows(x, bn, relu=True, residual=None):
     """[relu]( BatchNorm1d(x) [+ residual] ) for packed point rows x (M, C): one fused HIP stage (3 launches forward,
     3 backward) instead of ATen's 4-5 + 3-5.  Same running-statistics semantics as torch.nn.BatchNorm1d."""
     _need_gpu(x)
-    training, momentum = _bn_step(bn)
-    track = training and bn.track_running_stats
+    bn_args = _bn_args(bn)
     x = x if x.is_contiguous() else x.contiguous()
     if residual is not None and not residual.is_contiguous():
         residual = residual.contiguous()
-    return _BNRows.apply(x, residual, bn.weight, bn.bias, bn.running_mean if (track or not training) else None,
-                         bn.running_var if (track or not training) else None, training, momentum, float(bn.eps), relu)
+    return _BNRows.apply(x, residual, *bn_args, relu)
 
 
 # ------------------------------------------------------------------ Chamfer (losses/chamfer_loss.py:19)
@@ -1799,7 +1691,7 @@ class _ChamferNN(torch.autograd.Function):
         gx, gy = torch.zeros_like(xc), torch.zeros_like(yc)
         ws = None
         if deterministic():
-            ws = torch.empty(_lib.lib.fsg_chamfer_nn_bwd_workspace_bytes(B, N, M) // 4, dtype=torch.int32, device=xc.device)
+            ws = _lib.workspace("fsg_chamfer_nn_bwd", B, N, M, device=xc.device)
         with torch.cuda.device(xc.device):
             _lib.call("fsg_chamfer_nn_bwd_f32", _p(xc), _p(yc), _p(a), _p(_f32c(gd)), B, N, M, _p(gx), _p(gy), _p(ws),
                       _stream())
@@ -1913,11 +1805,10 @@ class _SSMDecodeAffine(torch.autograd.Function):
         dev = wc.device
         dw = torch.empty_like(wc)
         dv, ds, dt = (torch.empty(B, 3, dtype=torch.float32, device=dev) for _ in range(3)) if vc is not None else (None,) * 3
-        nbytes = _lib.lib.fsg_ssm_decode_bwd_workspace_bytes(B, P, M)
-        ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+        ws = _lib.workspace("fsg_ssm_decode_bwd", B, P, M, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_ssm_decode_bwd_f32", _p(_f32c(g)), _p(wc), _p(mc), _p(ec), _p(vc), _p(sc), B, P, M, _p(dw), _p(dv),
-                      _p(ds), _p(dt), _p(ws), nbytes, _stream())
+                      _p(ds), _p(dt), _p(ws), ws.numel(), _stream())
         return dw, None, None, dv, ds, dt
 
 
@@ -1967,11 +1858,10 @@ def cpd_estep(X, TY, sigma2, w=0.):
         Pt1 = torch.empty(B, N, dtype=torch.float32, device=dev)
         PX = torch.empty(B, M, 3, dtype=torch.float32, device=dev)
         Np = torch.empty(B, dtype=torch.float32, device=dev)
-        nbytes = _lib.lib.fsg_cpd_estep_workspace_bytes(B, N, M)
-        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_cpd_estep", B, N, M, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_cpd_estep_f32", _p(xc), 3 * N if xc.dim() == 3 else 0, _p(yc), _p(sc), float(w), B, N, M, _p(P1),
-                      _p(Pt1), _p(PX), _p(Np), _p(ws), nbytes, _stream())
+                      _p(Pt1), _p(PX), _p(Np), _p(ws), ws.numel(), _stream())
     return P1, Pt1, PX, Np
 
 
@@ -1987,7 +1877,7 @@ class _NNULoss(torch.autograd.Function):
         grad = torch.empty_like(logits) if need_grad else None      # keeps the (possibly point-major) strides
         if grad is not None and grad.stride() != logits.stride():
             grad = torch.empty_strided(logits.shape, logits.stride(), dtype=torch.float32, device=dev)
-        ws = torch.empty(_lib.lib.fsg_nnu_loss_workspace_bytes(C) // 8, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_nnu_loss", C, device=dev)
         gs = grad.stride() if grad is not None else (0, 0, 0)
         with torch.cuda.device(dev):
             _lib.call("fsg_nnu_loss_f32", _p(logits), logits.stride(0), logits.stride(1), logits.stride(2), _p(target),
@@ -2496,7 +2386,7 @@ class _PTAttn(torch.autograd.Function):
         out = torch.empty(n, c, dtype=torch.float32, device=dev)
         u1 = torch.empty(n, ns, cs, dtype=torch.float32, device=dev)
         sm = torch.empty(n, ns, cs, dtype=torch.float32, device=dev)
-        ws = torch.empty(_lib.lib.fsg_pt_attn_workspace_bytes(n, ns, c) // 8 + 1, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_pt_attn", n, ns, c, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_pt_attn_fwd_f32", _p(p), _p(idx), _p(qkv), ctypes.c_void_p(qkv.data_ptr() + 4 * c),
                       ctypes.c_void_p(qkv.data_ptr() + 8 * c), c3, ctypes.byref(prm), n, ns, c, int(training), _p(out),
@@ -2529,7 +2419,7 @@ class _PTAttn(torch.autograd.Function):
         zbuf = _take_zeros(ctx.zeros, n * 3 * c + (n * 3 if need_dp else 0), dev)
         dqkv = zbuf[:n * 3 * c].view(n, 3 * c)
         dp = zbuf[n * 3 * c:].view(n, 3) if need_dp else None
-        ws = torch.empty(_lib.lib.fsg_pt_attn_workspace_bytes(n, ns, c) // 8 + 1, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_pt_attn", n, ns, c, device=dev)
         g = _f32c(g)
         with torch.cuda.device(dev):
             _lib.call("fsg_pt_attn_bwd_f32", _p(p), _p(idx), _p(qkv), ctypes.c_void_p(qkv.data_ptr() + 4 * c),
@@ -2648,7 +2538,7 @@ def mind_mean(img, dilation, sigma, shifts, box):
         v, (B, D, H, W) = _volume(img)
         nch, sh, _ = _mind_tables(shifts, None)
         w, n = _host_floats(gaussian_taps(sigma))
-        ws = torch.empty(_lib.lib.fsg_mind_stats_workspace_bytes(B, D, H, W) // 4 + 1, dtype=torch.float32, device=v.device)
+        ws = _lib.workspace("fsg_mind_stats", B, D, H, W, device=v.device)
         mean = torch.empty(1, dtype=torch.float32, device=v.device)
         with torch.cuda.device(v.device):
             _lib.call("fsg_mind_stats_f32", _p(v), B, D, H, W, int(dilation), nch, int(box), sh, w, n, _p(ws), _p(mean), _stream())
@@ -2857,8 +2747,8 @@ def _rw_solve(im, labels, mask, edge_weights, tol, max_iter, check_every, num_la
         K = int(num_labels)
         if not 1 <= K <= _lib.RW_MAX_LABELS:
             raise ValueError(f"random_walk_solve: {K} labels; the kernels are built for 1..{_lib.RW_MAX_LABELS} (and need a seed)")
-        nbytes = _lib.lib.fsg_random_walk_workspace_bytes(B, K, D, H, W)
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_random_walk", B, K, D, H, W, device=dev)
+        nbytes = ws.numel()
         stop = torch.empty(B * K, dtype=torch.int32, device=dev)
         relres = torch.empty(B * K, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
@@ -3070,12 +2960,11 @@ def _cc_bits(bits, W, connectivity):
     """bit plane -> (labels (B, D, H, W) int32, n (B) int32 on the device): no host read"""
     B, D, H, _ = bits.shape
     dev = bits.device
-    nbytes = _lib.lib.fsg_cc_workspace_bytes(B, D, H, W)
-    ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+    ws = _lib.workspace("fsg_cc", B, D, H, W, device=dev)
     labels = torch.empty(B, D, H, W, dtype=torch.int32, device=dev)
     n = torch.empty(B, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.call("fsg_cc_label_bits", _p(bits), B, D, H, W, int(connectivity), _p(labels), _p(n), _p(ws), nbytes, _stream())
+        _lib.call("fsg_cc_label_bits", _p(bits), B, D, H, W, int(connectivity), _p(labels), _p(n), _p(ws), ws.numel(), _stream())
     return labels, n
 
 
@@ -3211,10 +3100,9 @@ def _splat_raw(values, coords, size, m):
         _lib.call("fsg_grid_corners_f32", _p(coords), B, N, D, H, W, m, _p(keys), _p(w), _stream())
         skeys, perm = torch.sort(keys, dim=1, stable=True)
         grid = torch.empty(B, C, D, H, W, dtype=torch.float32, device=values.device)
-        ws_bytes = _lib.lib.fsg_grid_splat_workspace_bytes(B, C, N)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=values.device)
+        ws = _lib.workspace("fsg_grid_splat", B, C, N, device=values.device)
         _lib.call("fsg_grid_splat_sorted_f32", _p(values), _p(skeys), _p(perm), _p(w), B, C, N, D, H, W, _p(grid), _p(ws),
-                  ws_bytes, _stream())
+                  ws.numel(), _stream())
     return grid
 
 
@@ -3370,8 +3258,8 @@ def _mc_run(count, emit, shape, dev, local, spacing):
     emit(local, sx, sy, sz, ws, nbytes, totals, nv, nf, verts, faces, normals) bind the volume."""
     B, D, H, W = shape
     with torch.cuda.device(dev):
-        nbytes = _lib.lib.fsg_mc_workspace_bytes(B, D, H, W)
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+        ws = _lib.workspace("fsg_mc", B, D, H, W, device=dev)
+        nbytes = ws.numel()
         totals = torch.empty(4 * B + 1, dtype=torch.int64, device=dev)
         count(ws, nbytes, totals)
         host = totals[:2 * B + 1].tolist()                 # the readback: the result's size depends on the data

@@ -355,11 +355,10 @@ class _MeshSample(torch.autograd.Function):
         pts = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
         face = torch.empty(N, n, dtype=torch.int32, device=dev)
         w = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
-        nbytes = _lib.lib.fsg_mesh_sample_workspace_bytes(N, st.max_F)
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_mesh_sample", N, st.max_F, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_mesh_sample_f32", _p(vc), _p(st.faces), _p(st.sdesc), N, st.max_F, _p(uc), n, _p(pts), _p(face),
-                      _p(w), _p(ws), nbytes, _stream())
+                      _p(w), _p(ws), ws.numel(), _stream())
         ctx.st, ctx.n = st, n
         ctx.save_for_backward(face, w)
         ctx.mark_non_differentiable(face, w)
@@ -404,11 +403,10 @@ class _MeshReg(torch.autograd.Function):
         terms = torch.empty(st.N, 3, dtype=torch.float32, device=dev)
         mean = torch.empty(3, dtype=torch.float32, device=dev)
         grads = torch.empty(3, st.total_verts, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        nbytes = _lib.lib.fsg_mesh_reg_workspace_bytes(st.N, st.max_V)
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_mesh_reg", st.N, st.max_V, device=dev)
         with torch.cuda.device(dev):
             _lib.call("fsg_mesh_reg_f32", _p(vc), st.total_verts, _p(st.desc), st.N, st.max_V, _p(st.nbr_off), _p(st.nbr),
-                      _p(st.pairs), _p(st.inc_off), _p(st.inc), _p(terms), _p(mean), _p(grads), _p(ws), nbytes, _stream())
+                      _p(st.pairs), _p(st.inc_off), _p(st.inc), _p(terms), _p(mean), _p(grads), _p(ws), ws.numel(), _stream())
         ctx.N = st.N
         if grads is not None:
             ctx.save_for_backward(grads)

@@ -51,8 +51,7 @@ class PointSegmentationModelBase(LoadableModel, ABC):
             logits = self(x).contiguous()
             if logits.shape != (R * B, self.num_classes, S) or logits.dtype != torch.float32:
                 raise RuntimeError(f"unexpected logits {tuple(logits.shape)} {logits.dtype} from {type(self).__name__}")
-            ws = torch.empty(_lib.lib.fsg_ensemble_accumulate_workspace_bytes(R, n_pts) // 4, dtype=torch.int32,
-                             device=pc.device)
+            ws = _lib.workspace("fsg_ensemble_accumulate", R, n_pts, device=pc.device)
             P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
             _lib.call("fsg_ensemble_accumulate_f32", P(logits), R, B, self.num_classes, S, P(chunk), n_pts, P(acc), P(ws),
                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))

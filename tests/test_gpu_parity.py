@@ -624,8 +624,8 @@ def test_bn_rows_fused_vs_torch(fsg, device, M, C, relu, res, train):
 
 @pytest.mark.parametrize("sizes", [[2048] * 8, [512, 100, 7, 513], [3000, 64, 2049], [1, 2, 65]])
 def test_fps_exact(fsg, device, sizes):
-    """farthest point sampling (pointops.py:16-39), a quarter of every segment: single-wave register path (<= 512 and
-    <= 2048 points) and the workgroup path, bit-exact incl. ties (duplicated points -> lowest index)."""
+    """farthest point sampling (pointops.py:16-39), a quarter of every segment: the eight-wave register path (segments of
+    <= 512, <= 1024 and <= 2048 points) and the generic workgroup kernel for longer ones, bit-exact incl. ties (duplicated points -> lowest index)."""
     xyz, _, off = packed(21, sizes)
     xyz[len(xyz) // 2] = xyz[0]
     xyz[-1] = xyz[len(xyz) // 3]

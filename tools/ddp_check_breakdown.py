@@ -64,8 +64,7 @@ if recompute:
         g = torch.cat([p.grad.reshape(-1) for p in net.parameters()])
         tot = g if tot is None else tot + g
     eager = (tot / world).cpu().numpy()
-    print("eager recompute vs dumped avg_grad: rel L2", np.linalg.norm(eager - got) / np.linalg.norm(got),
-          "(FSG_FUSED_HEAD=%s FSG_EC2_OLD=%s)" % (os.environ.get("FSG_FUSED_HEAD"), os.environ.get("FSG_EC2_OLD")))
+    print("eager recompute vs dumped avg_grad: rel L2", np.linalg.norm(eager - got) / np.linalg.norm(got))
     got = eager
 print("total rel L2", np.linalg.norm(got - want) / np.linalg.norm(want))
 off = 0

@@ -1,5 +1,7 @@
 """Accuracy of the fused two-layer EdgeConv (csrc/edgeconv2.hip) against an fp64 composition of the same layers on the same
-graph: python tools/ec2_accuracy.py [B C N k]  (FSG_EC2_OLD=1: the fp32-MFMA kernels; default: the split-bf16 kernels)."""
+graph: python tools/ec2_accuracy.py [--fp32-mfma] [--bf16] [B C N k]  (--fp32-mfma: the fp32-MFMA kernels through
+fsg_debug_ec2_use_fp32_mfma; default: the split-bf16 kernels; --bf16: the bf16 operand mode)."""
+import argparse
 import os
 import sys
 
@@ -9,7 +11,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fissure_segmentation_amd as fsg  # noqa: E402
 from fissure_segmentation_amd.norm import BatchNorm2d  # noqa: E402
 
-B, C, N, k = (int(a) for a in sys.argv[1:5]) if len(sys.argv) >= 5 else (8, 3, 2048, 20)
+ap = argparse.ArgumentParser()
+ap.add_argument("--fp32-mfma", action="store_true")
+ap.add_argument("--bf16", action="store_true")
+ap.add_argument("shape", nargs="*", type=int, default=[8, 3, 2048, 20], metavar="B C N k")
+args = ap.parse_args()
+B, C, N, k = args.shape
+fsg._lib.lib.fsg_debug_ec2_use_fp32_mfma(int(args.fp32_mfma))
+fsg.functional.set_mfma_operands("bf16" if args.bf16 else "f32")
 dev = torch.device("cuda:0")
 torch.manual_seed(5)
 x = torch.rand(B, C, N, device=dev)
@@ -46,7 +55,7 @@ yd = block(block(e, w1, g1, b1), w2, g2, b2).max(2)[0].permute(0, 2, 1)      # (
 yd.backward(gr.double())
 want = dict(out=yd.detach(), grad_x=xd.grad, grad_w1=w1.grad.view(64, 2 * C, 1, 1), grad_w2=w2.grad.view(64, 64, 1, 1), grad_g1=g1.grad,
             grad_b1=b1.grad, grad_g2=g2.grad, grad_b2=b2.grad)
-print("kernels:", "fp32 MFMA (FSG_EC2_OLD)" if os.environ.get("FSG_EC2_OLD") else "split bf16", "bf16 operands" if os.environ.get("FSG_MFMA_OPERANDS") else "")
+print("kernels:", "fp32 MFMA" if args.fp32_mfma else "split bf16", "bf16 operands" if args.bf16 else "")
 for n in got:
     a, b = got[n].double(), want[n]
     print(f"{n:8s} max|err| / max|ref| = {float((a - b).abs().max() / b.abs().max()):9.3e}   rel L2 = {float((a - b).norm() / b.norm()):9.3e}")
