@@ -36,6 +36,8 @@ def install_reference_aliases():
         "data_processing.random_walk": ".data_processing.random_walk", "data_processing.find_lobes": ".data_processing.find_lobes",
         "utils.image_utils": ".utils.image_utils", "utils.general_utils": ".utils.general_utils",
         "utils.image_ops": ".utils.image_ops",
+        "data_processing.surface_fitting": ".data_processing.surface_fitting",
+        "data_processing.surface_fitting_optimization": ".data_processing.surface_fitting_optimization",
         "models.divroc": ".models.divroc", "models.dpsr_utils": ".models.dpsr_utils", "models.dpsr_net": ".models.dpsr_net",
         "models.seg_logits_to_mesh": ".models.seg_logits_to_mesh", "losses.dpsr_loss": ".losses.dpsr_loss",
     }

@@ -62,6 +62,8 @@ SIGNATURES = {
     "fsg_chamfer_nn_bwd_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
     "fsg_chamfer_nn_bwd_f32": ([_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
     "fsg_point_mesh_dist_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    "fsg_mesh_labelmap_dist_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P], _I),
+    "fsg_mesh_labelmap_cover_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P], _I),
     "fsg_ensemble_accumulate_workspace_bytes": ([_I, _L], ctypes.c_size_t),
     "fsg_ensemble_accumulate_f32": ([_P, _I, _I, _I, _I, _P, _L, _P, _P, _P], _I),
     "fsg_sample_transform_f32": ([_P, _I, _I, _L, _P, _I, _P, _P, _P], _I),

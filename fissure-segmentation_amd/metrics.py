@@ -8,8 +8,10 @@ stands where the reference builds an open3d ray-casting scene on the CPU; distan
 scores and `_symmetric_point_distances` are plain torch on whatever device their inputs are on.  Nothing here is
 differentiable.
 
-Not included: `label_label_assd` and `label_mesh_assd` (metrics.py:45-55, 79-93) -- they start from `mask_to_points` and
-the image spacing of the voxel pipeline, which this package does not mirror.
+`label_mesh_assd` (metrics.py:45-55) starts from `utils.general_utils.mask_to_points`; the way back from meshes to label
+maps, for `batch_dice`, is data_processing/surface_fitting.py and surface_fitting_optimization.py.
+
+Not included: `label_label_assd` (metrics.py:79-93), the distance between the point clouds of two label maps.
 """
 import numpy as np
 import torch
@@ -130,6 +132,16 @@ def pseudo_symmetric_point_to_mesh_distance(points, mesh, n_samples=10 ** 6, gen
     with torch.no_grad():
         dist_mesh_to_points = F_hip.chamfer_nn(samples[None], pts[None].contiguous())[0][0].sqrt()
     return _symmetric_point_distances(dist_pts_to_mesh, dist_mesh_to_points)
+
+
+def label_mesh_assd(labelmap, mesh, spacing=(1., 1., 1.), n_samples=10 ** 6, generator=None):
+    """Surface distance between the foreground of a label map (D, H, W; every non-zero voxel, as the world point
+    index[::-1] * spacing with `spacing` in (x, y, z)) and a mesh with vertices in (x, y, z).
+    -> mean, standard deviation, Hausdorff, 95 % Hausdorff, and the (N, 3) points.  `n_samples` and `generator` go to
+    `pseudo_symmetric_point_to_mesh_distance`.  The label map is a tensor on the GPU, like every tensor handed to a distance."""
+    from .utils.general_utils import mask_to_points
+    points = mask_to_points(labelmap, spacing)
+    return (*pseudo_symmetric_point_to_mesh_distance(points, mesh, n_samples, generator), points)
 
 
 def batch_dice(prediction, target, n_labels):

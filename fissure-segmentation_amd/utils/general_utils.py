@@ -66,6 +66,27 @@ def inverse_affine_transform(point_cloud, scaling, rotation_mat, affine_translat
     return linalg.solve(rotation_mat, centred.T).T                  # one 3 x 3 solve for all rows, no explicit inverse
 
 
+# ------------------------------------------------------------------ label maps <-> point clouds (plain torch, any device)
+def mask_to_points(mask, spacing=(1., 1., 1.)):
+    """Same contract as utils/general_utils.py:151-154: the non-zero voxels of `mask` (D, H, W) as world points (N, 3) in
+    (x, y, z): index, flipped, times `spacing` (given x, y, z).  On the device of the mask."""
+    xyz = torch.nonzero(mask).flip(-1)
+    return xyz * torch.tensor(spacing, device=mask.device)       # int64 x fp32 -> fp32, like the reference
+
+
+def points_to_label_map(pts, labels, out_shape, spacing):
+    """Same contract as utils/general_utils.py:212-233: world points (N, 3) in (x, y, z) with one label each -> (label map of
+    `out_shape` (D, H, W) in the dtype of the labels, voxel index (N, 3) in (z, y, x) of every point): divide by `spacing`
+    (x, y, z), flip, round, clamp into the volume, scatter (where points share a voxel, one of their labels stays).  On the
+    device of the points."""
+    zyx = (pts / torch.tensor(spacing, device=pts.device)).flip(-1).round().long()
+    last = torch.tensor(tuple(out_shape), device=zyx.device) - 1
+    zyx = torch.minimum(zyx.clamp_min(0), last)
+    label_map = torch.zeros(tuple(out_shape), dtype=labels.dtype, device=labels.device)
+    label_map[tuple(zyx.unbind(1))] = labels.reshape(-1)
+    return label_map, zyx
+
+
 # ------------------------------------------------------------------ voxel <-> grid coordinates, patches (plain torch, any device)
 ALIGN_CORNERS = False
 

@@ -333,6 +333,29 @@ int fsg_point_mesh_dist_f32(const float *pts, const float *verts, const int32_t 
                             int Bf, float *dist2, int32_t *face, float *closest, fsg_stream_t stream);
 
 /*
+ * Triangle meshes -> voxel label maps: replace mesh2labelmap_dist (data_processing/surface_fitting_optimization.py:332-358)
+ * and the surface sampling of o3d_mesh_to_labelmap / mesh2labelmap_sampling (data_processing/surface_fitting.py:144-169,
+ * :19-39).  All meshes of a call are packed: verts (V,3) fp32 in the axis order of the volume (d0, d1, d2), faces (F,3) int32
+ * into verts, labels (F,) int32 = the mesh m >= 0 of every face.  One wave per face scans the voxels of the face's bounding
+ * box, which is clipped to the volume in float before any index is formed; coordinates outside the volume, Inf included,
+ * are legal, and a face with a NaN vertex takes part in nothing.  Face indices are NOT checked against V (the caller does).
+ * Faces without area are legal (their longest edge, or the point).  V, F, d0, d1, d2 > 0, d0 d1 d2 < 2^31, spacings positive
+ * and finite; all of this is checked before anything is launched.
+ *
+ * fsg_mesh_labelmap_dist_f32: voxel (i0,i1,i2) has the centre (i0 s0, i1 s1, i2 s2); out (d0,d1,d2) int64 = 1 + m of the
+ *   mesh of smallest distance (the arithmetic of fsg_point_mesh_dist_f32; the lowest m on an exact tie) if that distance is
+ *   <= dist_threshold (>= 0; compared as squares) and mask (d0,d1,d2) uint8, NULL = all set, is non-zero there; else 0.
+ *   keys: d0 d1 d2 uint64 of scratch, initialised here.  Memset + two launches; bitwise reproducible.
+ * fsg_mesh_labelmap_cover_f32: cell (i0,i1,i2) is the box [i s, (i + 1) s) per axis; out = the highest 1 + m among the
+ *   meshes with a triangle that intersects the cell (separating axes), 0 if none.  Memset + one launch, no scratch.
+ */
+int fsg_mesh_labelmap_dist_f32(const float *verts, const int32_t *faces, const int32_t *labels, int V, int F, int d0, int d1,
+                               int d2, float s0, float s1, float s2, float dist_threshold, const uint8_t *mask, uint64_t *keys,
+                               int64_t *out, fsg_stream_t stream);
+int fsg_mesh_labelmap_cover_f32(const float *verts, const int32_t *faces, const int32_t *labels, int V, int F, int d0, int d1,
+                                int d2, float s0, float s1, float s2, int64_t *out, fsg_stream_t stream);
+
+/*
  * Segmentation loss, value and gradient: replaces losses/nnu_loss.py:6-19, i.e.
  * nn.CrossEntropyLoss(class_weights) + GDL(softmax over dim 1, batch_dice=True, do_bg=True, smooth=1, weights 1/volume)
  * of losses/dice_loss.py:24-96 (the criterion train.py:38 builds for the default --loss nnunet).
