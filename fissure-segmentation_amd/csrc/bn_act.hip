@@ -3,7 +3,12 @@
 // include/fsg_hip.h: fsg_bn_act_{fwd,bwd}_f32.   HBM-bound: forward = 2 reads + 1 write of the (M,C) block,
 // backward = 4 reads + 1 write; lanes run along channels (C % 64 == 0) so every access is a 256-byte row segment.
 // Statistics: per-workgroup shifted sums -> (n, mean, M2) records merged with Chan's formula in fp64
-// (bn_merge_finalize_kernel of edgeconv.hip), i.e. no E[x^2]-E[x]^2 cancellation (MIOpen's BN loses ~1e-2 there).
+// (bn_finalize_kernel of edgeconv.hip), i.e. no E[x^2]-E[x]^2 cancellation (MIOpen's BN loses ~1e-2 there).
+// The sums of bn_act over the rows of a workgroup (bnact_stats_kernel: shifted sum and sum of squares, merge of the four
+// waves; bnact_bwd_reduce_kernel: sum h, sum h yhat) are carried in fp64 and rounded to fp32 once, when the record is
+// written.  With fp32 running sums the running variance of 210 rows of N(1, 2^2) was 3.6e-7 off its fp64 value
+// (ATen 1.7e-7; 7e-8 now) and, where d_beta cancels to 2 % of sum |h|, its error showed in dy at 2.5e-6 of the
+// summands (ATen 3e-7; 5.6e-7 now): tests/test_bn_family_gpu.py, measured on an MI355X.
 #include "edgeconv_internal.h"
 
 namespace {
@@ -12,45 +17,46 @@ constexpr int ROWS = 128;  // rows per workgroup in the reduction kernels
 
 __global__ __launch_bounds__(256) void bnact_stats_kernel(const float *__restrict__ y, long M, int C,
                                                            float *__restrict__ partials) {
-    __shared__ float red[3][4][64];
+    __shared__ double red[3][4][64];
     const int cg = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = cg * 64 + lane;
     const long r0 = (long)blockIdx.y * ROWS;
     const long r1 = r0 + ROWS < M ? r0 + ROWS : M;
-    float shift = 0.f, s1 = 0.f, s2 = 0.f, cnt = 0.f;
+    float shift = 0.f;
+    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
     if (r0 + wave < r1) shift = y[(r0 + wave) * C + c];
 #pragma unroll 4
     for (long r = r0 + wave; r < r1; r += 4) {
-        const float d = y[r * C + c] - shift;
+        const double d = (double)y[r * C + c] - (double)shift;
         s1 += d;
-        s2 = __builtin_fmaf(d, d, s2);
-        cnt += 1.f;
+        s2 = __builtin_fma(d, d, s2);
+        cnt += 1.0;
     }
-    float mean = 0.f, m2 = 0.f;
-    if (cnt > 0.f) {
-        mean = shift + s1 / cnt;
-        m2 = fmaxf(s2 - s1 * s1 / cnt, 0.f);
+    double mean = 0.0, m2 = 0.0;
+    if (cnt > 0.0) {
+        mean = (double)shift + s1 / cnt;
+        m2 = fmax(s2 - s1 * s1 / cnt, 0.0);
     }
     red[0][wave][lane] = cnt;
     red[1][wave][lane] = mean;
     red[2][wave][lane] = m2;
     __syncthreads();
     if (wave == 0) {
-        float n = red[0][0][lane], mu = red[1][0][lane], M2 = red[2][0][lane];
+        double n = red[0][0][lane], mu = red[1][0][lane], M2 = red[2][0][lane];
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
-            const float nb = red[0][w][lane];
-            if (nb > 0.f) {
-                const float tot = n + nb, delta = red[1][w][lane] - mu;
+            const double nb = red[0][w][lane];
+            if (nb > 0.0) {
+                const double tot = n + nb, delta = red[1][w][lane] - mu;
                 mu += delta * (nb / tot);
                 M2 += red[2][w][lane] + delta * delta * (n * nb / tot);
                 n = tot;
             }
         }
         float *pr = partials + (long)blockIdx.y * 3 * C;
-        pr[c] = n;
-        pr[C + c] = mu;
-        pr[2 * C + c] = M2;
+        pr[c] = (float)n;
+        pr[C + c] = (float)mu;
+        pr[2 * C + c] = (float)M2;
     }
 }
 
@@ -79,28 +85,28 @@ __global__ __launch_bounds__(256) void bnact_bwd_reduce_kernel(const float *__re
                                                                 const float *__restrict__ mean,
                                                                 const float *__restrict__ invstd, long M, int C,
                                                                 float slope, float *__restrict__ partials) {
-    __shared__ float red[2][4][64];
+    __shared__ double red[2][4][64];
     const int cg = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = cg * 64 + lane;
     const long r0 = (long)blockIdx.y * ROWS;
     const long r1 = r0 + ROWS < M ? r0 + ROWS : M;
     const float r = invstd[c], mu = mean[c], a = gamma[c] * r, b = beta[c] - mu * a;
-    float sb = 0.f, sg = 0.f;
+    double sb = 0.0, sg = 0.0;
 #pragma unroll 4
     for (long rr = r0 + wave; rr < r1; rr += 4) {
         const float yv = y[rr * C + c];
         const float u = __builtin_fmaf(yv, a, b);
         const float h = gout[rr * C + c] * (u > 0.f ? 1.f : slope);
-        sb += h;
-        sg = __builtin_fmaf(h, (yv - mu) * r, sg);
+        sb += (double)h;
+        sg = __builtin_fma((double)h, (double)((yv - mu) * r), sg);
     }
     red[0][wave][lane] = sb;
     red[1][wave][lane] = sg;
     __syncthreads();
     if (wave == 0) {
         float *pr = partials + (long)blockIdx.y * 2 * C;
-        pr[c] = red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane];
-        pr[C + c] = red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane];
+        pr[c] = (float)(red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane]);
+        pr[C + c] = (float)(red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane]);
     }
 }
 
@@ -376,7 +382,8 @@ extern "C" int fsg_bn_act_fwd_f32(const float *y, const float *gamma, const floa
                                   float slope, float *out, float *mean, float *invstd, float *workspace,
                                   fsg_stream_t stream) {
     FSG_REQUIRE(y && gamma && beta && out && mean && invstd, "fsg_bn_act_fwd_f32: NULL pointer");
-    FSG_REQUIRE(M > 0 && C > 0 && C % 64 == 0, "fsg_bn_act_fwd_f32: bad shape M=%ld C=%d (C must be a multiple of 64)", M, C);
+    FSG_REQUIRE(M > 0 && C > 0 && C % 64 == 0 && (M + ROWS - 1) / ROWS <= 65535,
+                "fsg_bn_act_fwd_f32: bad shape M=%ld C=%d (C must be a multiple of 64)", M, C);
     FSG_REQUIRE(!training || workspace, "fsg_bn_act_fwd_f32: training needs the workspace");
     hipStream_t st = (hipStream_t)stream;
     if (training) {
@@ -399,7 +406,8 @@ extern "C" int fsg_bn_act_bwd_f32(const float *grad_out, const float *y, const f
                                   fsg_stream_t stream) {
     FSG_REQUIRE(grad_out && y && gamma && beta && mean && invstd && grad_y && grad_gamma && grad_beta && workspace,
                 "fsg_bn_act_bwd_f32: NULL pointer");
-    FSG_REQUIRE(M > 0 && C > 0 && C % 64 == 0, "fsg_bn_act_bwd_f32: bad shape M=%ld C=%d", M, C);
+    FSG_REQUIRE(M > 0 && C > 0 && C % 64 == 0 && (M + ROWS - 1) / ROWS <= 65535,
+                "fsg_bn_act_bwd_f32: bad shape M=%ld C=%d (C must be a multiple of 64)", M, C);
     hipStream_t st = (hipStream_t)stream;
     const int R = fsg_cdiv(M, ROWS);
     hipLaunchKernelGGL(bnact_bwd_reduce_kernel, dim3(C / 64, R), dim3(256), 0, st, grad_out, y, gamma, beta, mean, invstd,
@@ -425,7 +433,8 @@ extern "C" int fsg_bn_act_max_fwd_f32(const float *y, const float *gamma, const 
                                       float slope, float *out, float *ysel, int32_t *arg, float *mean, float *invstd,
                                       float *workspace, fsg_stream_t stream) {
     FSG_REQUIRE(y && gamma && beta && out && ysel && arg && mean && invstd && workspace, "fsg_bn_act_max_fwd_f32: NULL pointer");
-    FSG_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0, "fsg_bn_act_max_fwd_f32: bad shape B=%d N=%d C=%d", B, N, C);
+    FSG_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0 && (long)B * fsg_cdiv(N, ROWS) <= 65535,
+                "fsg_bn_act_max_fwd_f32: bad shape B=%d N=%d C=%d (C must be a multiple of 64)", B, N, C);
     hipStream_t st = (hipStream_t)stream;
     const int tiles = fsg_cdiv(N, ROWS), R = B * tiles;
     float *partials = workspace;
@@ -450,7 +459,8 @@ extern "C" int fsg_bn_act_max_bwd_f32(const float *grad_out, const float *y, con
                                       float *grad_beta, fsg_stream_t stream) {
     FSG_REQUIRE(grad_out && y && ysel && arg && gamma && beta && mean && invstd && grad_y && grad_gamma && grad_beta,
                 "fsg_bn_act_max_bwd_f32: NULL pointer");
-    FSG_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0, "fsg_bn_act_max_bwd_f32: bad shape B=%d N=%d C=%d", B, N, C);
+    FSG_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0 && (long)B * fsg_cdiv(N, ROWS) <= 65535,
+                "fsg_bn_act_max_bwd_f32: bad shape B=%d N=%d C=%d (C must be a multiple of 64)", B, N, C);
     const int tiles = fsg_cdiv(N, ROWS);
     hipLaunchKernelGGL(bnmax_bwd_kernel, dim3(C / 64, B * tiles), dim3(256), 0, (hipStream_t)stream, grad_out, y, ysel, arg,
                        gamma, beta, mean, invstd, B, N, C, training, slope, grad_y, grad_gamma, grad_beta);

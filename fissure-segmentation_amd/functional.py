@@ -766,6 +766,8 @@ def _bn_step(bn):
 def _bn_args(bn):
     """one BatchNorm module -> (weight, bias, running_mean | None, running_var | None, training, momentum, eps) of this call:
     the running statistics are handed on when the call updates them (training, tracked) or reads them (eval)"""
+    if bn.weight is None or bn.bias is None:
+        raise ValueError("the fused BatchNorm stages need weight and bias: got a BatchNorm with affine=False")
     training, momentum = _bn_step(bn)
     stats = bn.track_running_stats or not training
     return (bn.weight, bn.bias, bn.running_mean if stats else None, bn.running_var if stats else None, training, momentum,
@@ -1660,9 +1662,11 @@ def bn_rows(x, bn, relu=True, residual=None):
     3 backward) instead of ATen's 4-5 + 3-5.  Same running-statistics semantics as torch.nn.BatchNorm1d."""
     _need_gpu(x)
     bn_args = _bn_args(bn)
+    if x.dtype != torch.float32:                  # the kernels read fp32 rows (the other fused stages widen in _f32c)
+        x = x.float()
     x = x if x.is_contiguous() else x.contiguous()
-    if residual is not None and not residual.is_contiguous():
-        residual = residual.contiguous()
+    if residual is not None and (residual.dtype != torch.float32 or not residual.is_contiguous()):
+        residual = residual.float().contiguous()
     return _BNRows.apply(x, residual, *bn_args, relu)
 
 

@@ -256,7 +256,8 @@ int fsg_edgeconv2_bwd_bf16(const float *grad_out, const float *grad_out_pm, int6
  * point-wise head (models/dgcnn.py:282-323 ConvBlock: conv -> BatchNorm -> LeakyReLU; slope 1 = no activation,
  * slope 0 = ReLU).  Forward: y -> out, plus mean/invstd (outputs when training, inputs otherwise) and the in-place
  * running-statistics update; backward: grad_out, y -> grad_y, grad_gamma, grad_beta.
- * workspace: fsg_bn_act_workspace_bytes(M, C) bytes.
+ * workspace: fsg_bn_act_workspace_bytes(M, C) bytes.  One statistics record per 128 rows: ceil(M / 128) <= 65535
+ * (M <= 8388480), anything larger is rejected as a bad shape.
  */
 size_t fsg_bn_act_workspace_bytes(long M, int C);
 int fsg_bn_act_fwd_f32(const float *y, const float *gamma, const float *beta, float *running_mean, float *running_var,
@@ -271,6 +272,8 @@ int fsg_bn_act_bwd_f32(const float *grad_out, const float *y, const float *gamma
  * (models/dgcnn.py:134-137: SharedFullyConnected(192,1024) -> AdaptiveMaxPool1d(1)) without materialising the
  * (B*N, C) activation.  y (B,N,C) pre-norm rows -> out (B,C); saved: ysel (B,C) selected pre-norm value, arg (B,C)
  * its point index.  Backward: grad_out (B,C) -> grad_y (B,N,C) (dense: BN statistics terms), grad_gamma, grad_beta.
+ * One record per (cloud, 128 points): B * ceil(N / 128) <= 65535, anything larger is rejected as a bad shape
+ * (fsg_bn_act_maxavg_* below has the same limit).
  */
 size_t fsg_bn_act_max_workspace_bytes(int B, int N, int C);
 int fsg_bn_act_max_fwd_f32(const float *y, const float *gamma, const float *beta, float *running_mean,
