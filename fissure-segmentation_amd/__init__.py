@@ -43,3 +43,11 @@ def install_reference_aliases():
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)
+    # the reference keeps `pointcloud_surface_fitting` in data_processing/surface_fitting.py, this package in a module of its own:
+    # under the reference's name both are found (a module object that carries the names of the two)
+    import types
+    both = types.ModuleType("data_processing.surface_fitting", "fissure_segmentation_amd.data_processing.surface_fitting + "
+                            "fissure_segmentation_amd.data_processing.pointcloud_surface_fitting")
+    for ours in (".data_processing.pointcloud_surface_fitting", ".data_processing.surface_fitting"):
+        both.__dict__.update({k: v for k, v in vars(importlib.import_module(ours, __name__)).items() if not k.startswith("_")})
+    sys.modules["data_processing.surface_fitting"] = both

@@ -162,6 +162,13 @@ SIGNATURES = {
     "fsg_mc_emit_f32": ([_P, _I, _I, _I, _I, _F, _I, _F, _F, _F, _P, ctypes.c_size_t, _P, _L, _L, _P, _P, _P, _P], _I),
     "fsg_mc_emit_labels_i32": ([_P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, ctypes.c_size_t, _P, _L, _L, _P, _P, _P, _P], _I),
     "fsg_pcl_normals_f32": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], _I),
+    "fsg_orient_normals_workspace_bytes": ([_I, _I], ctypes.c_size_t),
+    "fsg_orient_normals_f32": ([_P, _P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P], _I),
+    "fsg_face_union_i32": ([_P, _P, _I, _P, _P, _P], _I),
+    "fsg_cluster_stats_f64": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], _I),
+    "fsg_mesh_keep_flags_u8": ([_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P], _I),
+    "fsg_mesh_face_flags_u8": ([_P, _I, _I, _P, _P, _P, _P, _P], _I),
+    "fsg_mesh_compact_f32": ([_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync
@@ -170,6 +177,7 @@ for _name, (_args, _res) in SIGNATURES.items():
 GRID_TORCH, GRID_SAP = 0, 1   # include/fsg_hip.h: FSG_GRID_*
 MORPH_MAX_RADIUS = 8   # csrc/morphology.hip: MAXR
 PCL_NORMALS_MAX_K = 64   # include/fsg_hip.h: fsg_pcl_normals_f32 (what fsg_knn_segment_f32 can deliver)
+ORIENT_MAX_POINTS = 1 << 20   # include/fsg_hip.h: fsg_orient_normals_f32 (20 bits per endpoint in the edge key)
 RW_BINARY, RW_INTENSITY, RW_MAX_LABELS = 0, 1, 8   # include/fsg_hip.h: FSG_RW_*; csrc/random_walk.hip builds K = 1..8
 KNN_FIX_DIAG, KNN_DROP_FIRST, KNN_FORCE_ROWS, KNN_FORCE_MFMA, KNN_MAX_K = 1, 2, 4, 8, 64
 # debug / cross-check bits of the kNN `flags` (csrc/knn_internal.h has the meanings; any other bit is rejected by the library)

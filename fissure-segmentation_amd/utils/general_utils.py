@@ -1,4 +1,5 @@
-"""Drop-in for the kNN part of the reference's utils/general_utils.py (:43-53, :315-327)."""
+"""Drop-in for the kNN part of the reference's utils/general_utils.py (:43-53, :315-327), its label map <-> point cloud helpers
+and its mesh clean-up (:157-209: `mask_out_verts_from_mesh`, `remove_all_but_biggest_component`)."""
 import numpy as np
 import torch
 
@@ -135,3 +136,73 @@ def sample_patches_at_kpts(img: torch.Tensor, kpts_grid: torch.Tensor, patch_siz
     grid = (lattice + kpts_grid.view(n, 1, 1, 1, 3)).reshape(1, n, p ** 3, 1, 3)
     out = nn_f.grid_sample(img, grid, mode='nearest' if p % 2 else 'bilinear', padding_mode='border', align_corners=ALIGN_CORNERS)
     return out.view(1, n, p, p, p)
+
+
+# ------------------------------------------------------------------ mesh clean-up (csrc/mesh_cleanup.hip through functional)
+def _as_meshes(mesh, who):
+    """`mesh.Meshes`, a (verts, faces) pair or an object with .vertices / .triangles (open3d's TriangleMesh) -> Meshes; host
+    arrays go to the current GPU"""
+    from ..mesh import Meshes
+    from ..metrics import _as_tensor, _mesh_raw
+    if isinstance(mesh, Meshes):
+        return mesh
+    verts, faces = _mesh_raw(mesh)
+    verts = _as_tensor(verts, torch.float32)
+    return Meshes([verts], [_as_tensor(faces, torch.int32, verts.device)])
+
+
+def mask_out_verts_from_mesh(mesh, mask, spacing):
+    """utils/general_utils.py:157-168: drop the vertices of `mesh` (and the faces that name one) whose voxel
+    floor(v / spacing), clamped from above into the volume, is not set in `mask` (D, H, W) bool; vertices in (x, y, z), spacing
+    (sx, sy, sz), the mask indexed [z, y, x].
+
+    The reference edits an open3d mesh IN PLACE and returns nothing; this takes a `fissure_segmentation_amd.mesh.Meshes` (a batch
+    shares the mask) or one (verts, faces) pair and RETURNS the new `Meshes`.  A vertex with a negative coordinate is dropped,
+    where the reference's negative index would wrap around to the far side of the volume."""
+    if not torch.is_tensor(mask):
+        mask = torch.as_tensor(np.asarray(mask))
+    meshes = _as_meshes(mesh, "mask_out_verts_from_mesh")
+    return F_hip.mesh_remove_vertices(meshes, mask=(mask != 0).to(meshes.device), spacing=spacing)
+
+
+def remove_all_but_biggest_component(mesh, right=None, center_x=None):
+    """utils/general_utils.py:171-209: keep only the edge-connected cluster of triangles with the largest area and drop the
+    vertices nothing refers to any more.  With `right` and `center_x` both given, a cluster whose distinct-vertex mean lies on the
+    wrong side of x = center_x (x > center_x when right, x < center_x when not right) takes part with the value -1 / area instead
+    of its area, so the biggest of them still wins when no cluster is on the wanted side; the first maximum wins.
+
+    Takes a `Meshes` or one (verts, faces) pair and RETURNS the new `Meshes` (the reference edits in place).  A batch applies the
+    rule per mesh; `right` may be a sequence with one entry per mesh.  A mesh without vertices or faces comes back unchanged."""
+    meshes = _as_meshes(mesh, "remove_all_but_biggest_component")
+    B = len(meshes)
+    nv, nf = meshes._nv, meshes._nf
+    if not any(v and f for v, f in zip(nv, nf)):
+        return meshes
+    with torch.no_grad():
+        clusters, _ = F_hip.mesh_face_components(meshes)
+        area, num, vsum, counts = F_hip.mesh_component_stats(meshes, clusters)
+        dev = area.device
+        C = sum(counts)
+        cluster_mesh = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(counts).to(dev), output_size=C)
+        value = area
+        if center_x is not None and right is not None:
+            r = torch.as_tensor(right, dtype=torch.bool).to(dev).reshape(-1)
+            if r.numel() not in (1, B):
+                raise ValueError(f"right must be one bool or one per mesh ({B}), got {r.numel()}")
+            r = r.expand(B)[cluster_mesh]
+            cx = vsum[:, 0] / num
+            wrong = torch.where(r, cx > float(center_x), cx < float(center_x))
+            value = torch.where(wrong, -1 / area, area)
+        first = torch.tensor([sum(counts[:m]) for m in range(B)]).to(dev)
+        table = torch.full((B, max(counts)), float("-inf"), dtype=torch.float64, device=dev)
+        table[cluster_mesh, torch.arange(C, device=dev) - first[cluster_mesh]] = value
+        chosen = table.argmax(1)                                    # the first maximal value, like numpy's
+        face_mesh = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(nf).to(dev), output_size=sum(nf))
+        out = F_hip.mesh_remove_vertices(meshes, face_keep=clusters.long() == chosen[face_mesh], drop_unreferenced=True)
+    if all(v and f for v, f in zip(nv, nf)):
+        return out
+    from ..mesh import Meshes
+    keep_old = [not (v and f) for v, f in zip(nv, nf)]              # the reference returns early on these
+    pick = lambda new, old: [o if k else n for n, o, k in zip(new, old, keep_old)]     # noqa: E731
+    normals = None if meshes._normals is None else pick(out.verts_normals_list(), meshes.verts_normals_list())
+    return Meshes(pick(out.verts_list(), meshes.verts_list()), pick(out.faces_list(), meshes.faces_list()), normals)

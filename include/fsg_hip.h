@@ -1117,6 +1117,56 @@ int fsg_mc_emit_labels_i32(const int32_t *labels, int first_label, int B, int D,
 int fsg_pcl_normals_f32(const float *xyz, const int32_t *idx, const int32_t *offset, int b, int n, int K, int disambiguate,
                         float *normals, float *curvatures, float *frames, fsg_stream_t stream);
 
+/* Surface fitting of labelled point clouds: consistent normal orientation and mesh clean-up (csrc/mesh_cleanup.hip; DESIGN.md
+ * "Surface fitting").  All pointers DEVICE.  Only integer atomics whose result does not depend on their order are used: the
+ * same input gives the same bits.  Bad shapes, NULL pointers, a short or misaligned workspace are FSG_ERR_ARG before any launch.
+ *
+ * fsg_orient_normals_f32 replaces pcd.orient_normals_consistent_tangent_plane(100) of data_processing/surface_fitting.py:62-64.
+ *   xyz, normals (n, 3) fp32 packed (normals need not be unit), idx (n, K) int32 in fsg_knn_segment_f32's layout (self first;
+ *   an index outside the row's segment is clamped into it), offset (b) int32 cumulative segment ends.  Per segment of n_s points
+ *   the undirected graph {u, idx[u, j]}, 1 <= j < k_s = min(K, n_s - 1), with weights max(0, 1 - |n_u . n_v|); its minimum
+ *   spanning forest under the key (fp32 bits of w >> 8, min(u, v), max(u, v)) by Boruvka rounds (64-bit atomic min per
+ *   component), orientation carried as union-find with parity.  Per connected component of that graph: the member of largest
+ *   z (lowest index on ties) ends with n_z >= 0, every other member follows by parity along the forest.  open3d adds Euclidean
+ *   MST edges to connect the graph; this does not: every component is oriented on its own.
+ *   out (n, 3) = normals with the sign bit flipped or not, signs (n) int8 = +1 / -1, comp (n) int32 = the smallest member of the
+ *   point's component.  ceil(log2 n) + 1 rounds of four launches are always issued, rounds after the last merge return at once:
+ *   no host read.  2 <= K <= 64, n <= 2^20 (20 bits per endpoint in the key), workspace 16-byte aligned.
+ * fsg_face_union_i32 replaces mesh.cluster_connected_triangles() of utils/general_utils.py:177.  sorted_keys (3 F) int64: the
+ *   keys min(a, b) * V + max(a, b) of the half-edges (3 f + e: edge e of face f) in ascending order, half_edge (3 F) int64 the
+ *   permutation that sorts them.  Faces with an equal key are united (an edge with more than two faces links all of them):
+ *   parent (F) int32 is scratch, root (F) int32 = the smallest face of every face's cluster.
+ * fsg_cluster_stats_f64 replaces cluster_area and the np.unique / np.mean of utils/general_utils.py:177-195.  verts (V, 3),
+ *   faces (F, 3) int32 into verts; sorted_clusters (F) int32 = the cluster (0 .. C - 1) of every face in ascending order and
+ *   face_order (F) int64 the stable permutation that sorts them; sorted_vertex_keys (3 F) int64 = cluster * V + vertex of every
+ *   face corner, ascending.  -> area (C) fp64 = sum of 0.5 |(v1 - v0) x (v2 - v0)|, num_verts (C) int64 and vert_sum (C, 3)
+ *   fp64 over the DISTINCT vertices of the cluster's faces (a vertex of two clusters counts in both).  One launch, fixed order.
+ * fsg_mesh_keep_flags_u8 replaces the flags of mask_out_verts_from_mesh (utils/general_utils.py:157-167) and of
+ *   TriangleMesh.crop (data_processing/surface_fitting.py:71-74).  verts (V, 3) in (x, y, z), vert_offset (B + 1) int32 the first
+ *   vertex of every mesh; keep = keep_in (NULL = all) AND lo <= v <= hi of boxes (B, 6) fp32 (NULL = no box; per mesh lo xyz,
+ *   hi xyz) AND mask[iz, iy, ix] (NULL = no mask) of a (D, H, W) uint8 volume at i = floor(v / spacing), clamped from above as
+ *   the reference does; a negative index (or NaN) is OUTSIDE, where the reference's indexing would wrap around.
+ * fsg_mesh_face_flags_u8 / fsg_mesh_compact_f32 replace remove_vertices_by_mask, remove_triangles_by_mask and
+ *   remove_unreferenced_vertices (utils/general_utils.py:168, :207-209).  A face survives iff its three vertices do and
+ *   face_keep (NULL = all) is set; vert_used marks the vertices of surviving faces.  The caller scans the flags it wants to
+ *   keep (exclusive prefix sums vert_new, face_new, int64); compact writes survivors in their old order, faces re-indexed and
+ *   LOCAL to their mesh (int64), normals alongside when given. */
+size_t fsg_orient_normals_workspace_bytes(int n, int K);
+int fsg_orient_normals_f32(const float *xyz, const float *normals, const int32_t *idx, const int32_t *offset, int b, int n, int K,
+                           void *workspace, size_t workspace_bytes, float *out, int8_t *signs, int32_t *comp, fsg_stream_t stream);
+int fsg_face_union_i32(const int64_t *sorted_keys, const int64_t *half_edge, int F, int32_t *parent, int32_t *root,
+                       fsg_stream_t stream);
+int fsg_cluster_stats_f64(const float *verts, const int32_t *faces, const int32_t *sorted_clusters, const int64_t *face_order,
+                          const int64_t *sorted_vertex_keys, int V, int F, int C, double *area, int64_t *num_verts, double *vert_sum,
+                          fsg_stream_t stream);
+int fsg_mesh_keep_flags_u8(const float *verts, int V, const int32_t *vert_offset, int B, const uint8_t *keep_in, const float *boxes,
+                           const uint8_t *mask, int D, int H, int W, float sx, float sy, float sz, uint8_t *keep, fsg_stream_t stream);
+int fsg_mesh_face_flags_u8(const int32_t *faces, int V, int F, const uint8_t *vert_keep, const uint8_t *face_keep, uint8_t *face_out,
+                           uint8_t *vert_used, fsg_stream_t stream);
+int fsg_mesh_compact_f32(const float *verts, const float *normals, const int32_t *faces, int V, int F, const int32_t *vert_offset,
+                         int B, const uint8_t *vert_flag, const int64_t *vert_new, const uint8_t *face_flag, const int64_t *face_new,
+                         float *verts_out, float *normals_out, int64_t *faces_out, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

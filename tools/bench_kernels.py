@@ -895,3 +895,140 @@ if "normals" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "surffit" in which:
+    # surface fitting (csrc/mesh_cleanup.hip): consistent normal orientation, mesh clean-up and the whole fit_label_surfaces, each
+    # beside a HOST baseline measured in the same run on the same graphs -- scipy.sparse.csgraph's minimum_spanning_tree /
+    # breadth_first_order / connected_components plus numpy (tests/surface_fit_oracle.py); torch has no composition for either
+    # graph problem, so there is no device column.  Device figures are HIP-event medians (whole call, its launches and plumbing
+    # included), host figures wall clock.  The whole fit has no host counterpart (open3d is not installed): beside it stand the host
+    # figures of its two graph steps on the same data.
+    import json
+    import time
+    import numpy as np
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import breadth_first_order, connected_components, minimum_spanning_tree
+    import surface_fit_oracle as so
+    from fissure_segmentation_amd.data_processing import pointcloud_surface_fitting as sf
+    from fissure_segmentation_amd.mesh import Meshes
+    from fissure_segmentation_amd.utils import general_utils as gu
+
+    lines = []
+
+    def emit_line(rec):
+        print("SURFFIT " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); out = fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        return round(statistics.median(ts), 1), out
+
+    def host_orient(xyz, normals, idx, off):
+        """scipy's minimum spanning tree of the same graph (integer weights 1 + the key's weight bits), a breadth-first walk per
+        component for the signs, the root rule"""
+        n = len(xyz)
+        u, v, _, wb, _ = so.graph_edges(normals, idx, off)
+        mst = minimum_spanning_tree(coo_matrix(((wb + 1).astype(np.float64), (u, v)), shape=(n, n)).tocsr())
+        ncomp, lab = connected_components(mst, directed=False)
+        signs = np.zeros(n, np.int8)
+        for c in range(ncomp):
+            members = np.nonzero(lab == c)[0]
+            z = xyz[members, 2]
+            top = int(members[np.nonzero(z == z.max())[0][0]])
+            order, pred = breadth_first_order(mst, top, directed=False)
+            flip = so.dot32(normals, order[1:], pred[order[1:]]) < 0
+            par = np.zeros(n, bool)
+            for node, p, f in zip(order[1:].tolist(), pred[order[1:]].tolist(), flip.tolist()):
+                par[node] = par[p] ^ f
+            s0 = -1 if normals[top, 2] < 0 else 1
+            signs[order] = np.where(par[order], -s0, s0)
+        return signs, ncomp
+
+    K = 64
+    for segments in (1, 3):
+        parts = [so.ellipsoid(20000, 30 + s)[0] + np.float32(3 * s) for s in range(segments)]
+        xyz, off = np.concatenate(parts), (np.arange(1, segments + 1) * 20000).astype(np.int32)
+        x, o = torch.from_numpy(xyz).to(dev), torch.from_numpy(off).to(dev)
+        idx = F.knn_segment(K, x, x, o, o)[0]
+        normals = F._pcl_packed(x, o, 30, False, None, False, False)[0]
+        med, mn = timeit(lambda: F.orient_normals_consistent(x, normals, o, K, idx=idx), iters=20, warm=3)
+        out, signs, comp = F.orient_normals_consistent(x, normals, o, K, idx=idx)
+        nh, ih = normals.cpu().numpy(), idx.cpu().numpy()
+        t0 = time.perf_counter()
+        hs, ncomp = host_orient(xyz, nh, ih, off)
+        host_us = (time.perf_counter() - t0) * 1e6
+        rec = dict(kernel="surffit orient_normals_consistent", segments=segments, points=len(xyz), K=K, hip_us=round(med, 1),
+                   hip_min_us=round(mn, 1), knn_segment_us=round(timeit(lambda: F.knn_segment(K, x, x, o, o), 10, 2)[0], 1),
+                   host_scipy_us=round(host_us, 1), speedup_vs_host=round(host_us / med, 1), components=int(ncomp),
+                   components_hip=int(comp.unique().numel()), flipped=int((signs < 0).sum()),
+                   signs_equal_host_share=round(float((signs.cpu().numpy() == hs).mean()), 6))
+        if segments == 1:      # the exact oracle (Kruskal in the kernel's key order, a Python loop): equality, not a time
+            t0 = time.perf_counter()
+            want = so.orient(xyz, nh, ih, off)
+            rec["oracle_kruskal_python_us"] = round((time.perf_counter() - t0) * 1e6, 1)
+            rec["signs_equal_oracle"] = bool(np.array_equal(signs.cpu().numpy(), want["signs"]))
+            rec["components_equal_oracle"] = bool(np.array_equal(comp.cpu().numpy(), want["comp"]))
+        fsg._lib.start_timing()
+        for _ in range(5):
+            F.orient_normals_consistent(x, normals, o, K, idx=idx)
+        rec["entry_us"] = {k: round(1e3 * sorted(v)[len(v) // 2], 1) for k, v in fsg._lib.stop_timing().items()}
+        emit_line(rec)
+
+    # clean-up: three marching-cubes meshes of about 50 000 faces each (a big sphere and some small blobs per field)
+    res = 128
+    zz, yy, xx = np.meshgrid(*(np.arange(res, dtype=np.float32),) * 3, indexing="ij")
+    fields = []
+    for s in range(3):
+        rng = np.random.default_rng(40 + s)
+        f = np.sqrt((zz - 64) ** 2 + (yy - 64) ** 2 + (xx - 60 - 4 * s) ** 2) - 44
+        for _ in range(6):
+            c = rng.uniform(8, 120, 3)
+            c[rng.integers(3)] = rng.choice([6.0, 121.0])          # near a wall of the volume: away from the sphere
+            f = np.minimum(f, np.sqrt((zz - c[0]) ** 2 + (yy - c[1]) ** 2 + (xx - c[2]) ** 2) - rng.uniform(2, 4.5))
+        fields.append(f)
+    field = torch.from_numpy(np.stack(fields)).to(dev)
+    verts, faces, vnormals, nv, nf = F.marching_cubes(field, 0.0, return_local_coords=False)
+    cut = lambda t, n: list(torch.split(t, n))                      # noqa: E731
+    meshes = Meshes(cut(verts, nv), cut(faces, nf), cut(vnormals, nv))
+    clusters, counts = F.mesh_face_components(meshes)
+    rec = dict(kernel="surffit mesh clean-up", meshes=3, faces=nf, verts=nv, clusters=counts.tolist())
+    for name, fn in (("face_components", lambda: F.mesh_face_components(meshes)),
+                     ("component_stats", lambda: F.mesh_component_stats(meshes, clusters)),
+                     ("remove_all_but_biggest_component", lambda: gu.remove_all_but_biggest_component(meshes, right=True, center_x=64.0))):
+        rec[name + "_hip_us"] = round(timeit(fn, iters=10, warm=2)[0], 1)
+    host = [(v.cpu().numpy(), f.cpu().numpy()) for v, f in zip(meshes.verts_list(), meshes.faces_list())]
+    t0 = time.perf_counter()
+    hc = [so.face_clusters(f) for _, f in host]
+    t1 = time.perf_counter()
+    hstats = [so.cluster_stats(v, f, c[0]) for (v, f), c in zip(host, hc)]
+    t2 = time.perf_counter()
+    hbig = []
+    for v, f in host:
+        k, cl, _ = so.biggest_component(v, f, True, 64.0)
+        hbig.append(so.compact(v, f, np.ones(len(v), bool), cl == k, True))
+    t3 = time.perf_counter()
+    rec.update(face_components_host_scipy_us=round((t1 - t0) * 1e6, 1), component_stats_host_numpy_us=round((t2 - t1) * 1e6, 1),
+               remove_all_but_biggest_component_host_us=round((t3 - t2) * 1e6, 1))
+    got = gu.remove_all_but_biggest_component(meshes, right=True, center_x=64.0)
+    rec["clusters_equal_host"] = bool(np.array_equal(clusters.cpu().numpy(), np.concatenate([c[0] for c in hc])))
+    rec["biggest_equal_host"] = all(np.array_equal(g.cpu().numpy(), h[1]) for g, h in zip(got.faces_list(), hbig))
+    area = F.mesh_component_stats(meshes, clusters)[0].cpu().numpy()
+    rec["area_max_rel_diff_host_fp64"] = float(np.max(np.abs(area - np.concatenate([h[0] for h in hstats])) / np.concatenate([h[0] for h in hstats])))
+    emit_line(rec)
+
+    # the whole fit: three labels of 20 000 points each
+    pts = np.concatenate([so.ellipsoid(20000, 50 + s)[0] * np.float32(40 + 5 * s) + np.float32(100 + 30 * s) for s in range(3)])
+    labels = np.repeat(np.arange(1, 4), 20000)
+    p, lab = torch.from_numpy(pts).to(dev), torch.from_numpy(labels).to(dev)
+    for depth in (6, 7):
+        sf.fit_label_surfaces(p, lab, 3, depth=depth, crop_to_bbox=True)
+        us, out = wall(lambda: sf.fit_label_surfaces(p, lab, 3, depth=depth, crop_to_bbox=True))
+        us_clean, _ = wall(lambda: gu.remove_all_but_biggest_component(out))
+        emit_line(dict(kernel="surffit fit_label_surfaces (3 labels x 20000 points, crop)", depth=depth, hip_wall_us=us,
+                       remove_all_but_biggest_component_wall_us=us_clean, verts=out._nv, faces=out._nf,
+                       note="no host pipeline to race (open3d absent); the host figures of its graph steps are on the lines above"))
+    out_path = os.environ.get("FSG_SURFFIT_BENCH_OUT", os.path.join(ROOT, "profiles", "surface_fit_bench.jsonl"))
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
