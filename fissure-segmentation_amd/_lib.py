@@ -123,6 +123,11 @@ SIGNATURES = {
     "fsg_pw_scatter_rows_workspace_bytes": ([_I, _I], ctypes.c_size_t),
     "fsg_pw_scatter_rows_f32": ([_P, _P, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P], _I),
     "fsg_pw_gf_dw_f32": ([_P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P], _I),
+    "fsg_pw_logits_bwd_bias_f32": ([_P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P], _I),
+    "fsg_pw_gf_prep_sort_f32": ([_P, _P, _L, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _L, _I, _F, _P, _P, _P, _P, _P, _P, _L, _I, _P,
+                                 _L, _P, _I, _P, _P, _P], _I),
+    "fsg_pw_tn_reduce_image_f32": ([_P, _I, _I, _I, _I, _F, _I, _I, _P, _P, _L, _P], _I),
+    "fsg_pw_rowgemm_scatter_f32": ([_P, _P, _P, _P, _P, _L, _I, _P], _I),
     "fsg_foerstner_dist_f32": ([_P, _I, _I, _I, _I, _P, _I, _P, _P], _I),
     "fsg_nms_keypoints": ([_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P], _I),
     "fsg_mind_stats_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),

@@ -5,6 +5,8 @@
 // block per 4 columns walking 16 K strided rows); one 1024-thread workgroup reading the matrix as a flat coalesced stream
 // does it in ~5 us: with C a power of two <= 32 a thread always meets the same column (1024 % C == 0), so it sums its
 // stride-1024 elements in order and the columns are then folded through LDS in a fixed tree -- reproducible.
+// pw_logits_bwd_bias_kernel (csrc/pointwise.hip) forms the same sums in the same order inside the logits-backward launch (four of
+// these threads to a thread); tests/test_pw_tail_gpu.py holds the two bit-equal: a change of the order here is a change there.
 #include "fsg_common.h"
 
 namespace {

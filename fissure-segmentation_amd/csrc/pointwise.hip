@@ -121,11 +121,24 @@ struct RowGemmArgs {
     const float *ealpha, *edelta, *emu, *er;   // its tables (edelta, emu = mean - cloud shift: per cloud with stride etstride)
     int etstride;
     float *rec2;          // (M / BM, 2, N): sums of h = c f'(u) and h * yhat over the block's rows
+    // SCAT (fsg_pw_rowgemm_scatter_f32): the rows the per-cloud max selected get sum_c coef[b, c] W[c, :] added on the way out
+    const unsigned *sc_keys;   // (B, 1024) keys (row << 12 | channel), sorted per cloud (pw_sort_sel_1024_block)
+    const int *sc_first;       // (B, rows_per_cloud / 64 + 1): first key of every 64-row tile of the cloud
+    const float *sc_coef;      // (B, sc_C)
+    const float *sc_W;         // (sc_C, N), row stride sc_ldw
+    long sc_ldw;
+    int sc_C;
 };
 
-template <int WM, int WN, int PRO, int EPI, int PIPE, int NP = 3>
+// SCAT = 1 (64 x 192 tile, N <= 192: the workgroup owns 64 complete rows): pw_scatter_rows_kernel's work in the epilogue.  The
+// entries of the tile's rows are a run [first[t], first[t + 1]) of the cloud's sorted keys; thread = column walks the run in
+// key order with ONE fma chain per row (acc = 0, acc = fma(coef, W[c, col], acc) in ascending channel order, sixteen entries'
+// loads in flight), parks a finished row's sums in LDS -- S[64][192] + 64 row flags in the dead operand images -- and the
+// store adds them: (acc_mfma + bias) + S, the `base + acc` of the separate launch bit for bit; unflagged rows get no add.
+template <int WM, int WN, int PRO, int EPI, int PIPE, int NP = 3, int SCAT = 0>
 __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
     static_assert(NP == 3 || (NP == 1 && PIPE == 1 && PRO == PRO_NONE), "one-piece (bf16 operand) mode: pipelined plain products only");
+    static_assert(!SCAT || (WM == 1 && WN == 3 && PIPE == 1 && EPI == (PW_STORE | PW_BIAS)), "scatter epilogue: whole-width tile 5 only");
     constexpr int BM = 64 * WM, BN = 64 * WN;
     constexpr int AI = BM / 64;                       // A rows per thread and iteration
     constexpr int BU = BN * 4 * NP / 256;             // 16-byte units of the B image per thread and iteration
@@ -145,6 +158,30 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
     const int row0 = tm * BM, col0 = tn * BN;
     const int K = p.K1 + p.K2, KT = K / 32, KS = K / 16;
     const int cloud = p.rows_per_cloud > 0 ? row0 / p.rows_per_cloud : 0;
+    int sc_e0 = 0, sc_e1 = 0;                             // SCAT: this tile's run of keys, requested now, used behind the loop
+    if constexpr (SCAT != 0) {
+        const int T = p.rows_per_cloud / 64 + 1, tl = (row0 - cloud * p.rows_per_cloud) / 64;
+        sc_e0 = max(__builtin_amdgcn_readfirstlane(p.sc_first[(long)cloud * T + tl]), 0);
+        sc_e1 = min(__builtin_amdgcn_readfirstlane(p.sc_first[(long)cloud * T + tl + 1]), p.sc_C);   // (a table that is not one: no stray reads)
+    }
+    // SCAT: the run's first SC_PRE entries (a tile of the flagship shape has 32 on average) are loaded behind the first A
+    // fetches and wait in registers through the main loop; only longer runs pay memory round trips behind the loop
+    constexpr int SC_PRE = SCAT ? 32 : 1;
+    unsigned sc_key[SC_PRE];
+    float sc_wv[SC_PRE], sc_cv[SC_PRE];
+    const int scol = min(tid, p.N - 1);               // SCAT: thread = column; threads behind N walk along (clamped): scalar control flow
+    auto sc_prefetch = [&]() {
+        const unsigned *keys = p.sc_keys + (long)cloud * 1024;
+        const float *cf = p.sc_coef + (long)cloud * p.sc_C;
+#pragma unroll
+        for (int i = 0; i < SC_PRE; ++i) sc_key[i] = __builtin_amdgcn_readfirstlane(keys[max(min(sc_e0 + i, sc_e1 - 1), 0)]);
+#pragma unroll
+        for (int i = 0; i < SC_PRE; ++i) {            // every load unconditional (entries behind the run repeat its last one, unused)
+            const unsigned c = min(sc_key[i] & 4095u, (unsigned)p.sc_C - 1u);
+            sc_wv[i] = p.sc_W[(long)c * p.sc_ldw + scol];
+            sc_cv[i] = cf[c];
+        }
+    };
 
     if (PRO != PRO_NONE) {
         for (int e = tid; e < p.K1; e += 256) {
@@ -283,6 +320,8 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
         fetchA(P0{}, 0);
         dmaB(0, 0);
         if (KT > 1) fetchA(P1{}, 1);
+        if constexpr (SCAT != 0) sc_prefetch();
+        (void)sc_prefetch;
         __syncthreads();                                  // the prologue tables are in LDS
         transformA(P0{}, 0, 0);
         __syncthreads();                                  // A and B images of block 0 are in LDS (the barrier drains the DMA)
@@ -414,6 +453,65 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
     // ---------------------------------------------------------------- epilogue: lane holds column (lane & 31) of each of its
     // tiles and rows (e & 3) + 8 (e >> 2) + 4 (lane >> 5), e = 0..15
     const int half = lane >> 5, lc = lane & 31;
+    float *scS = reinterpret_cast<float *>(smem);                     // SCAT: [64][192] sums of the selected rows
+    int *scF = reinterpret_cast<int *>(scS + 64 * 192);               //       [64] row flags
+    if constexpr (SCAT != 0) {
+        __syncthreads();                              // the operand images are dead
+        if (tid < 64) scF[tid] = 0;
+        __syncthreads();
+        const unsigned *keys = p.sc_keys + (long)cloud * 1024;
+        const float *cf = p.sc_coef + (long)cloud * p.sc_C;
+        const bool act = tid < p.N;
+        const unsigned rbase = (unsigned)(row0 - cloud * p.rows_per_cloud);
+        float sacc = 0.f;
+        int cur = -1;                                 // row (inside the tile) whose chain is open
+        auto feed = [&](unsigned key, float w, float c) {     // one entry, in key order: a new row closes the open chain
+            const int r = (int)min((key >> 12) - rbase, 63u);
+            if (r != cur) {
+                if (cur >= 0) {
+                    if (act) scS[cur * 192 + tid] = sacc;
+                    if (tid == 0) scF[cur] = 1;
+                }
+                cur = r;
+                sacc = 0.f;
+            }
+            sacc = __builtin_fmaf(c, w, sacc);
+        };
+#pragma unroll
+        for (int i = 0; i < SC_PRE; ++i)
+            if (sc_e0 + i < sc_e1) feed(sc_key[i], sc_wv[i], sc_cv[i]);
+        for (int e = sc_e0 + SC_PRE; e < sc_e1; e += 16) {
+            unsigned key[16];
+            float wv[16], cv[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) key[i] = __builtin_amdgcn_readfirstlane(keys[min(e + i, sc_e1 - 1)]);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {            // every load unconditional (entries behind the run repeat its last one, unused)
+                const unsigned c = min(key[i] & 4095u, (unsigned)p.sc_C - 1u);
+                wv[i] = p.sc_W[(long)c * p.sc_ldw + scol];
+                cv[i] = cf[c];
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (e + i < sc_e1) feed(key[i], wv[i], cv[i]);
+        }
+        if (cur >= 0) {
+            if (act) scS[cur * 192 + tid] = sacc;
+            if (tid == 0) scF[cur] = 1;
+        }
+        __syncthreads();
+    }
+    auto outv = [&](int i, int j, int e, float v) {   // SCAT: add the selected row's sums (flagged rows only: no add of zero)
+        if constexpr (SCAT != 0) {
+            // both LDS reads unconditional (an unflagged row's slot holds stale bits: the select drops that sum): no branch per
+            // element, the reads of a tile's sixteen stores go out together
+            const int rl = (wm * WM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+            const float sv = scS[rl * 192 + min((wn * WN + j) * 32 + lc, 191)];
+            const float vs = v + sv;
+            v = scF[rl] != 0 ? vs : v;
+        }
+        return v;
+    };
     if ((EPI & PW_STORE) && col0 + BN > p.store_n0) {     // (store_n0 may fall inside a column tile: the general path masks per column)
 #pragma unroll
         for (int i = 0; i < WM; ++i)
@@ -426,13 +524,14 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int row = row0 + (wm * WM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                        p.C[(long)row * p.ldc + (col - p.store_n0)] = acc[i][j][e] + bv;
+                        p.C[(long)row * p.ldc + (col - p.store_n0)] = outv(i, j, e, acc[i][j][e] + bv);
                     }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int row = row0 + (wm * WM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                        if (row < p.M && col < p.N && col >= p.store_n0) p.C[(long)row * p.ldc + (col - p.store_n0)] = acc[i][j][e] + bv;
+                        if (row < p.M && col < p.N && col >= p.store_n0)
+                            p.C[(long)row * p.ldc + (col - p.store_n0)] = outv(i, j, e, acc[i][j][e] + bv);
                     }
                 }
             }
@@ -543,7 +642,7 @@ __global__ __launch_bounds__(256) void pw_rowgemm_kernel(const RowGemmArgs p) {
     }
 }
 
-template <int WM, int WN, int PRO, int EPI, int PIPE = 1, int NP = 3>
+template <int WM, int WN, int PRO, int EPI, int PIPE = 1, int NP = 3, int SCAT = 0>
 int launch_rowgemm(const RowGemmArgs &a, hipStream_t st, const char *name) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
     const int MT = (a.M + BM - 1) / BM, NT = (a.N + BN - 1) / BN;
@@ -551,8 +650,8 @@ int launch_rowgemm(const RowGemmArgs &a, hipStream_t st, const char *name) {
     size_t lds = (PIPE ? 2 : 1) * ((size_t)(BM / 32) * 2 * NP + (size_t)(BN / 32) * 2 * NP) * 1024 + sizeof(float) * 4 * (size_t)a.K1;
     const size_t scratch = sizeof(float) * 2 * 2 * WN * 32;
     if (lds < scratch) lds = scratch;
-    FSG_GRANT_LDS(name, (pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP>), lds);   // (per template instantiation; the grant itself is per device)
-    hipLaunchKernelGGL((pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP>), dim3(grid), dim3(256), lds, st, a);
+    FSG_GRANT_LDS(name, (pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP, SCAT>), lds);   // (per template instantiation; the grant itself is per device)
+    hipLaunchKernelGGL((pw_rowgemm_kernel<WM, WN, PRO, EPI, PIPE, NP, SCAT>), dim3(grid), dim3(256), lds, st, a);
     FSG_CHECK_LAUNCH(name);
     return FSG_OK;
 }
@@ -776,6 +875,152 @@ __global__ __launch_bounds__(256) void pw_tn_reduce_kernel(const float *__restri
         if (r < N1a) C1[(long)r * ldc1 + c] = v;
         else C2[(long)(r - N1a) * ldc2 + c] = v;
     }
+}
+
+// pw_tn_reduce_kernel + pw_weight_image_kernel in one launch: the slices are folded in pw_tn_reduce_kernel's association and the
+// rows < NI go straight into the B operand image of the (NI, N2) matrix they form (k-steps ks0 .. of KS, times `scale`): the
+// thread grid of pw_weight_image_kernel, a thread folds the 8 consecutive k of its row n.  Rows [NI, N1) are stored as fp32 in C2
+// by the threads behind the image's.
+__device__ __forceinline__ float pw_tn_fold(const float *__restrict__ part, int S, long total, long t) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int q = 0;
+    for (; q + 16 <= S; q += 16) {         // sixteen loads in flight, the adds in the order of the four-slice rounds
+        float sl[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) sl[u] = part[(long)(q + u) * total + t];
+#pragma unroll
+        for (int u = 0; u < 16; u += 4) {
+            a0 += sl[u];
+            a1 += sl[u + 1];
+            a2 += sl[u + 2];
+            a3 += sl[u + 3];
+        }
+    }
+    for (; q + 4 <= S; q += 4) {
+        a0 += part[(long)q * total + t];
+        a1 += part[(long)(q + 1) * total + t];
+        a2 += part[(long)(q + 2) * total + t];
+        a3 += part[(long)(q + 3) * total + t];
+    }
+    for (; q < S; ++q) a0 += part[(long)q * total + t];
+    return (a0 + a1) + (a2 + a3);
+}
+
+__global__ __launch_bounds__(256) void pw_tn_reduce_image_kernel(const float *__restrict__ part, int S, int N1, int N2, int NI,
+                                                                 float scale, int ks0, int KS, u32x4 *__restrict__ img,
+                                                                 float *__restrict__ C2, long ldc2) {
+    const long total = (long)N1 * N2;
+    const int ksteps = (N2 + 15) / 16;
+    const long img_threads = (long)((NI + 31) / 32) * ksteps * 64;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if ((N2 & 63) == 0 && (long)blockIdx.x * 256 < img_threads) {
+        // N2 % 64 == 0: the workgroup's four image blocks are 32 rows x 64 consecutive k of ONE row block -- folded with
+        // coalesced 256-byte row segments (thread = 4 k of rows r and r + 16) into LDS, then split from there
+        __shared__ float tile[32][68];
+        const int tid = threadIdx.x;
+        const long blk0 = (long)blockIdx.x * 4;
+        const int nb = (int)(blk0 / ksteps), ksq = (int)(blk0 % ksteps);
+        const int r = tid >> 4, c4 = tid & 15;
+        auto add = [](float4 &d, const float4 v) { d.x += v.x; d.y += v.y; d.z += v.z; d.w += v.w; };
+        float4 a[2][4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) a[h][u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        // (rows behind NI are re-read from row NI - 1 and zeroed below)
+        const float *src0 = part + (long)min(nb * 32 + r, NI - 1) * N2 + ksq * 16 + 4 * c4;
+        const float *src1 = part + (long)min(nb * 32 + r + 16, NI - 1) * N2 + ksq * 16 + 4 * c4;
+        int q = 0;
+        for (; q + 4 <= S; q += 4) {        // (rounds of eight slices measured slower: 10.3 against 8.3 us at 16 slices of 193 x 192)
+            float4 v[2][4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[0][u] = *reinterpret_cast<const float4 *>(src0 + (long)(q + u) * total);
+                v[1][u] = *reinterpret_cast<const float4 *>(src1 + (long)(q + u) * total);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { add(a[0][u], v[0][u]); add(a[1][u], v[1][u]); }
+        }
+        for (; q < S; ++q) {
+            add(a[0][0], *reinterpret_cast<const float4 *>(src0 + (long)q * total));
+            add(a[1][0], *reinterpret_cast<const float4 *>(src1 + (long)q * total));
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float *d = &tile[r + 16 * h][4 * c4];
+            d[0] = (a[h][0].x + a[h][1].x) + (a[h][2].x + a[h][3].x);
+            d[1] = (a[h][0].y + a[h][1].y) + (a[h][2].y + a[h][3].y);
+            d[2] = (a[h][0].z + a[h][1].z) + (a[h][2].z + a[h][3].z);
+            d[3] = (a[h][0].w + a[h][1].w) + (a[h][2].w + a[h][3].w);
+        }
+        __syncthreads();
+        const int lane = tid & 63, sub = tid >> 6, nl = lane & 31, kl = sub * 16 + 8 * (lane >> 5);
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = nb * 32 + nl < NI ? tile[nl][kl + j] * scale : 0.f;
+        u32x4 h, m, l;
+        split8(x, h, m, l);
+        u32x4 *o = img + (((long)nb * KS + ks0 + ksq + sub) * 3) * 64 + lane;
+        o[0] = h;
+        o[64] = m;
+        o[128] = l;
+        return;
+    }
+    if (t >= img_threads) {                 // the fp32 rows behind the image's
+        const long e = t - img_threads;
+        if (e < (long)(N1 - NI) * N2) {
+            const int r = (int)(e / N2), c = (int)(e - (long)r * N2);
+            C2[(long)r * ldc2 + c] = pw_tn_fold(part, S, total, (long)NI * N2 + e);
+        }
+        return;
+    }
+    const int lane = (int)(t & 63);
+    const long blk = t >> 6;
+    const int ks = (int)(blk % ksteps), nb = (int)(blk / ksteps);
+    const int n = nb * 32 + (lane & 31), k0 = ks * 16 + 8 * (lane >> 5);
+    float x[8];
+    if (n < NI && k0 + 8 <= N2 && (N2 & 3) == 0) {
+        // 8 consecutive elements of every slice as two 16-byte loads (N2 % 4 == 0: every slice and row starts 16-byte aligned)
+        float4 a[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u][0] = a[u][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float *src = part + (long)n * N2 + k0;
+        auto add = [](float4 &d, const float4 v) { d.x += v.x; d.y += v.y; d.z += v.z; d.w += v.w; };
+        int q = 0;
+        for (; q + 4 <= S; q += 4) {
+            float4 v[4][2];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float4 *s4 = reinterpret_cast<const float4 *>(src + (long)(q + u) * total);
+                v[u][0] = s4[0];
+                v[u][1] = s4[1];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { add(a[u][0], v[u][0]); add(a[u][1], v[u][1]); }
+        }
+        for (; q < S; ++q) {
+            const float4 *s4 = reinterpret_cast<const float4 *>(src + (long)q * total);
+            add(a[0][0], s4[0]);
+            add(a[0][1], s4[1]);
+        }
+        x[0] = ((a[0][0].x + a[1][0].x) + (a[2][0].x + a[3][0].x)) * scale;
+        x[1] = ((a[0][0].y + a[1][0].y) + (a[2][0].y + a[3][0].y)) * scale;
+        x[2] = ((a[0][0].z + a[1][0].z) + (a[2][0].z + a[3][0].z)) * scale;
+        x[3] = ((a[0][0].w + a[1][0].w) + (a[2][0].w + a[3][0].w)) * scale;
+        x[4] = ((a[0][1].x + a[1][1].x) + (a[2][1].x + a[3][1].x)) * scale;
+        x[5] = ((a[0][1].y + a[1][1].y) + (a[2][1].y + a[3][1].y)) * scale;
+        x[6] = ((a[0][1].z + a[1][1].z) + (a[2][1].z + a[3][1].z)) * scale;
+        x[7] = ((a[0][1].w + a[1][1].w) + (a[2][1].w + a[3][1].w)) * scale;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (n < NI && k0 + j < N2) ? pw_tn_fold(part, S, total, (long)n * N2 + k0 + j) * scale : 0.f;
+    }
+    u32x4 h, m, l;
+    split8(x, h, m, l);
+    u32x4 *o = img + (((long)nb * KS + ks0 + ks) * 3) * 64 + lane;
+    o[0] = h;
+    o[64] = m;
+    o[128] = l;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1094,14 +1339,13 @@ __global__ __launch_bounds__(256) void pw_bnbwd_finalize_kernel(const float *__r
 //   h = da f'(alpha y + delta), records (sum h, sum h yhat) per 32-row block.  lane = channel, 4 waves x 8 rows, all loads of a
 //   wave's rows in flight together.
 constexpr int LB_ROWS = 32;
-__global__ __launch_bounds__(256) void pw_logits_bwd_kernel(const float *__restrict__ g, int cls, const float *__restrict__ W3,
-                                                            const float *__restrict__ y, const float *__restrict__ alpha,
-                                                            const float *__restrict__ delta, const float *__restrict__ mean,
-                                                            const float *__restrict__ invstd, long M, int C, float slope,
-                                                            float *__restrict__ da, float *__restrict__ rec2) {
-    __shared__ float red[2][4][64];
+__device__ __forceinline__ void pw_logits_bwd_block(float (*red)[4][64], const int blk, const float *__restrict__ g, int cls,
+                                                    const float *__restrict__ W3, const float *__restrict__ y,
+                                                    const float *__restrict__ alpha, const float *__restrict__ delta,
+                                                    const float *__restrict__ mean, const float *__restrict__ invstd, long M, int C,
+                                                    float slope, float *__restrict__ da, float *__restrict__ rec2) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long r0 = (long)blockIdx.x * LB_ROWS + wave * 8;
+    const long r0 = (long)blk * LB_ROWS + wave * 8;
     float gv[8][8];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -1131,12 +1375,85 @@ __global__ __launch_bounds__(256) void pw_logits_bwd_kernel(const float *__restr
         red[1][wave][lane] = sg;
         __syncthreads();
         if (wave == 0) {
-            float *pr = rec2 + (long)blockIdx.x * 2 * C;
+            float *pr = rec2 + (long)blk * 2 * C;
             pr[c] = (red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane]);
             pr[C + c] = (red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane]);
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(256) void pw_logits_bwd_kernel(const float *__restrict__ g, int cls, const float *__restrict__ W3,
+                                                            const float *__restrict__ y, const float *__restrict__ alpha,
+                                                            const float *__restrict__ delta, const float *__restrict__ mean,
+                                                            const float *__restrict__ invstd, long M, int C, float slope,
+                                                            float *__restrict__ da, float *__restrict__ rec2) {
+    __shared__ float red[2][4][64];
+    pw_logits_bwd_block(red, blockIdx.x, g, cls, W3, y, alpha, delta, mean, invstd, M, C, slope, da, rec2);
+}
+
+// the same grid plus ONE block in front (block 0) that forms the bias gradient db[j] = sum_m g[m, j] in the exact order of
+// colsum_narrow_kernel (csrc/colsum.hip): that kernel's 1024 threads are carried four to a thread here (virtual thread
+// v = tid + 256 u: sixteen chains), each with its four interleaved chains over the stride-1024 elements and the tail loop into
+// chain 0, then the same LDS tree over the 1024 partial sums.  cls: a power of two (a thread always meets one column).
+__global__ __launch_bounds__(256) void pw_logits_bwd_bias_kernel(const float *__restrict__ g, int cls, const float *__restrict__ W3,
+                                                                 const float *__restrict__ y, const float *__restrict__ alpha,
+                                                                 const float *__restrict__ delta, const float *__restrict__ mean,
+                                                                 const float *__restrict__ invstd, long M, int C, float slope,
+                                                                 float *__restrict__ da, float *__restrict__ rec2,
+                                                                 float *__restrict__ db) {
+    __shared__ float sm[1024];
+    if (blockIdx.x > 0) {
+        pw_logits_bwd_block(reinterpret_cast<float (*)[4][64]>(sm), blockIdx.x - 1, g, cls, W3, y, alpha, delta, mean, invstd, M, C,
+                            slope, da, rec2);
+        return;
+    }
+    const int tid = threadIdx.x;
+    const long total = M * cls;
+    float a[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[u][q] = 0.f;
+    // virtual thread v walks e = v, v + 4096, ... while e + 3 * 1024 < total: total / 4096 rounds for every v (unconditional
+    // loads: 32 in flight over two rounds), at most one more for the low v
+    const long rounds = total / 4096;
+#pragma unroll 2
+    for (long i = 0; i < rounds; ++i) {
+        float x[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x[u][q] = g[i * 4096 + q * 1024 + u * 256 + tid];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[u][q] += x[u][q];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        long e = rounds * 4096 + u * 256 + tid;
+        if (e + 3 * 1024 < total) {
+            a[u][0] += g[e];
+            a[u][1] += g[e + 1024];
+            a[u][2] += g[e + 2 * 1024];
+            a[u][3] += g[e + 3 * 1024];
+            e += 4 * 1024;
+        }
+        for (; e < total; e += 1024) a[u][0] += g[e];
+        sm[u * 256 + tid] = (a[u][0] + a[u][1]) + (a[u][2] + a[u][3]);
+    }
+    __syncthreads();
+    if (512 >= cls) {                 // s = 512: virtual threads 0..511
+        sm[tid] += sm[tid + 512];
+        sm[tid + 256] += sm[tid + 768];
+        __syncthreads();
+    }
+    for (int s = 256; s >= cls; s >>= 1) {
+        if (tid < s) sm[tid] += sm[tid + s];
+        __syncthreads();
+    }
+    if (tid < cls) db[tid] = sm[tid];
 }
 
 // global-feature backward, per channel j (the Gram form of DESIGN.md).  First the two tiny products around the per-cloud
@@ -1237,15 +1554,16 @@ __global__ __launch_bounds__(64 * GP_WAVES) void pw_gf_prep_kernel(const float *
 }
 
 // dW0g[k, j] = sum_b dc[b, k] g[b, j]  (C0 x CG outputs, B terms each): thread = column j, eight rows k per workgroup row
+// (the body of workgroup (bx, by) of a gx x gy grid: pw_outer_kernel, and the leading blocks of pw_outer_sort_kernel)
 template <int GP_MAXB>
-__global__ __launch_bounds__(256) void pw_outer_kernel(const float *__restrict__ dc, const float *__restrict__ g, int B, int C0,
-                                                       int CG, float *__restrict__ out, long ldo, const float *__restrict__ Q,
-                                                       const float *__restrict__ P, const float *__restrict__ Wgl, long ldwgl,
-                                                       int KL, float *__restrict__ Wq, long ldwq) {
+__device__ __forceinline__ void pw_outer_block(const int bx, const int by, const int gx, const int gy, const float *__restrict__ dc,
+                                               const float *__restrict__ g, int B, int C0, int CG, float *__restrict__ out, long ldo,
+                                               const float *__restrict__ Q, const float *__restrict__ P,
+                                               const float *__restrict__ Wgl, long ldwgl, int KL, float *__restrict__ Wq, long ldwq) {
     if (Wq) {
         // rows [Q[c] W[c, :] | -P[c]] of the CG channels: the left operand of [M1 ; npvec] = [Q o W | -P]^T W, spread over the
         // whole grid (thread = column, workgroup = a run of channel rows)
-        const int nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;
+        const int nwg = gx * gy, wg = by * gx + bx;
         const int per = (CG + nwg - 1) / nwg;
         for (int c = wg * per; c < min(CG, (wg + 1) * per); ++c) {
             const float q = Q[c], pp = P[c];
@@ -1253,7 +1571,7 @@ __global__ __launch_bounds__(256) void pw_outer_kernel(const float *__restrict__
                 Wq[(long)c * ldwq + jj] = jj < KL ? q * Wgl[(long)c * ldwgl + jj] : -pp;
         }
     }
-    const int j = blockIdx.x * 256 + threadIdx.x, k0 = blockIdx.y * 8;
+    const int j = bx * 256 + threadIdx.x, k0 = by * 8;
     if (j >= CG) return;
     float gv[GP_MAXB];
 #pragma unroll
@@ -1269,6 +1587,14 @@ __global__ __launch_bounds__(256) void pw_outer_kernel(const float *__restrict__
     }
 }
 
+template <int GP_MAXB>
+__global__ __launch_bounds__(256) void pw_outer_kernel(const float *__restrict__ dc, const float *__restrict__ g, int B, int C0,
+                                                       int CG, float *__restrict__ out, long ldo, const float *__restrict__ Q,
+                                                       const float *__restrict__ P, const float *__restrict__ Wgl, long ldwgl,
+                                                       int KL, float *__restrict__ Wq, long ldwq) {
+    pw_outer_block<GP_MAXB>(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, dc, g, B, C0, CG, out, ldo, Q, P, Wgl, ldwgl, KL, Wq, ldwq);
+}
+
 // dX rows of the selected points: for every cloud, dX[b N + arg[b,c], :] += coef[b,c] W[c, :], summed per destination row in
 // channel order (no atomics, reproducible).  pw_sort_sel_kernel sorts the cloud's keys (arg << 12 | c) once (bitonic in LDS,
 // one key per thread); pw_scatter_rows_kernel gives every workgroup a chunk of the sorted list: it owns the row segments whose
@@ -1278,10 +1604,11 @@ constexpr int SC_CHUNK = 16;
 // 1024 keys, one workgroup of 256 threads per cloud, four keys per thread in registers: compare-exchanges with a partner inside
 // the thread are register swaps (19 of the 55 stages), partners inside the wave come through __shfl_xor (33 stages), only the
 // three stages whose partner sits in another wave go through LDS and a barrier
-__global__ __launch_bounds__(256) void pw_sort_sel_1024_kernel(const int *__restrict__ arg, int C, unsigned *__restrict__ sorted) {
+// (cloud b's sort by one 256-thread workgroup, xch: 1024 words of LDS; the sorted keys are left in xch as well, no barrier behind)
+__device__ __forceinline__ void pw_sort_sel_1024_block(unsigned *xch, const int b, const int *__restrict__ arg, int C,
+                                                       unsigned *__restrict__ sorted) {
     constexpr int KPL = 4, NK = 1024;
-    __shared__ unsigned xch[NK];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     unsigned v[KPL];
 #pragma unroll
     for (int r = 0; r < KPL; ++r) {
@@ -1330,6 +1657,46 @@ __global__ __launch_bounds__(256) void pw_sort_sel_1024_kernel(const int *__rest
     uint4 o;
     o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
     reinterpret_cast<uint4 *>(sorted + (long)b * NK)[tid] = o;
+    __syncthreads();                       // (the last exchange stage's readers are done with xch)
+    reinterpret_cast<uint4 *>(xch)[tid] = o;
+}
+
+__global__ __launch_bounds__(256) void pw_sort_sel_1024_kernel(const int *__restrict__ arg, int C, unsigned *__restrict__ sorted) {
+    __shared__ unsigned xch[1024];
+    pw_sort_sel_1024_block(xch, blockIdx.x, arg, C, sorted);
+}
+
+// pw_outer_kernel's grid (gx x gy workgroups) followed by rows of gx workgroups that hold the B sort workgroups: the sort reads
+// only `arg`, a forward result, so it rides in the launch that waits for pw_gf_prep_kernel anyway.  Behind its sort a workgroup
+// writes the cloud's tile table first[b][t] = index of the first key with arg >= 64 t, t = 0 .. Npts / 64 (lower bound among the
+// C live keys: first[b][Npts / 64] = C) -- the row-GEMM's scatter epilogue finds the entries of its 64 rows there.
+template <int GP_MAXB>
+__global__ __launch_bounds__(256) void pw_outer_sort_kernel(const int gy, const float *__restrict__ dc, const float *__restrict__ g,
+                                                            int B, int C0, int CG, float *__restrict__ out, long ldo,
+                                                            const float *__restrict__ Q, const float *__restrict__ P,
+                                                            const float *__restrict__ Wgl, long ldwgl, int KL,
+                                                            float *__restrict__ Wq, long ldwq, const int *__restrict__ arg,
+                                                            int Npts, unsigned *__restrict__ sorted, int *__restrict__ first) {
+    __shared__ unsigned xch[1024];
+    if ((int)blockIdx.y < gy) {
+        pw_outer_block<GP_MAXB>(blockIdx.x, blockIdx.y, gridDim.x, gy, dc, g, B, C0, CG, out, ldo, Q, P, Wgl, ldwgl, KL, Wq, ldwq);
+        return;
+    }
+    const int b = ((int)blockIdx.y - gy) * gridDim.x + blockIdx.x;
+    if (b >= B) return;
+    pw_sort_sel_1024_block(xch, b, arg, CG, sorted);
+    __syncthreads();
+    const int T = Npts / 64 + 1;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const unsigned want = 64u * (unsigned)t;
+        int lo = 0, hi = CG;               // first index in [0, CG] whose key's row is >= want
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((xch[mid] >> 12) < want) lo = mid + 1;
+            else hi = mid;
+        }
+        first[(long)b * T + t] = lo;
+    }
 }
 
 // larger channel counts: bitonic sort in LDS
@@ -1415,7 +1782,10 @@ __global__ __launch_bounds__(256) void pw_gf_dw_kernel(const float *__restrict__
                                                        const float *__restrict__ W, long ldw, const float *__restrict__ G,
                                                        const float *__restrict__ P, const float *__restrict__ Q, int B, int C,
                                                        int K, int Npts, float *__restrict__ dW, long lddw) {
-    extern __shared__ float wr[];      // [4][K] rows of W, then [4 waves][4 channels][64] partial products
+    // Three 64-column blocks of W G run together (twelve accumulators, one LDS fold per 192 columns): six rows of G = eighteen
+    // loads are issued before their fmas, so a wave's share of the rows is 8 dependent round trips at K = 192 instead of 18.
+    // Every output's chain over the wave's rows i stays ascending and the fold over the waves (r0 + r1) + (r2 + r3).
+    extern __shared__ float wr[];      // [4][K] rows of W, then [4 waves][4 channels][3 column blocks][64] partial products
     float *red = wr + 4 * K;
     const int c0 = blockIdx.x * 4, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int e = tid; e < 4 * K; e += 256) {
@@ -1424,38 +1794,75 @@ __global__ __launch_bounds__(256) void pw_gf_dw_kernel(const float *__restrict__
     }
     __syncthreads();
     const int per = (K + 3) / 4, i0 = wave * per, i1 = min(K, i0 + per);
-    for (int k0 = 0; k0 < K; k0 += 64) {
-        const int k = min(k0 + lane, K - 1);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll 8
-        for (int i = i0; i < i1; ++i) {
-            const float g = G[(long)i * K + k];
-            a0 = __builtin_fmaf(wr[i], g, a0);
-            a1 = __builtin_fmaf(wr[K + i], g, a1);
-            a2 = __builtin_fmaf(wr[2 * K + i], g, a2);
-            a3 = __builtin_fmaf(wr[3 * K + i], g, a3);
+    for (int k0 = 0; k0 < K; k0 += 192) {
+        int kk[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) kk[u] = min(k0 + 64 * u + lane, K - 1);
+        float a[3][4];
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[u][q] = 0.f;
+        int i = i0;
+        for (; i + 6 <= i1; i += 6) {
+            float gv[6][3];
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int u = 0; u < 3; ++u) gv[r][u] = G[(long)(i + r) * K + kk[u]];
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int u = 0; u < 3; ++u)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) a[u][q] = __builtin_fmaf(wr[q * K + i + r], gv[r][u], a[u][q]);
         }
-        red[(wave * 4 + 0) * 64 + lane] = a0;
-        red[(wave * 4 + 1) * 64 + lane] = a1;
-        red[(wave * 4 + 2) * 64 + lane] = a2;
-        red[(wave * 4 + 3) * 64 + lane] = a3;
+        for (; i < i1; ++i)
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const float g = G[(long)i * K + kk[u]];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) a[u][q] = __builtin_fmaf(wr[q * K + i], g, a[u][q]);
+            }
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[((wave * 4 + q) * 3 + u) * 64 + lane] = a[u][q];
         __syncthreads();
         // wave q finishes channel c0 + q
         const int c = c0 + wave;
-        if (c < C && k0 + lane < K) {
-            const float wg = (red[(0 * 4 + wave) * 64 + lane] + red[(1 * 4 + wave) * 64 + lane]) +
-                             (red[(2 * 4 + wave) * 64 + lane] + red[(3 * 4 + wave) * 64 + lane]);
-            float a = -__builtin_fmaf(Q[c], wg, P[c] * s[k]);
-            float xv[8];
+        if (c < C) {
+            float acc[3];
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const float wg = (red[((0 * 4 + wave) * 3 + u) * 64 + lane] + red[((1 * 4 + wave) * 3 + u) * 64 + lane]) +
+                                 (red[((2 * 4 + wave) * 3 + u) * 64 + lane] + red[((3 * 4 + wave) * 3 + u) * 64 + lane]);
+                acc[u] = -__builtin_fmaf(Q[c], wg, P[c] * s[kk[u]]);
+            }
             int bb = 0;
             for (; bb + 8 <= B; bb += 8) {
+                float xv[8][3], cf[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) xv[q] = X[((long)(bb + q) * Npts + arg[(long)(bb + q) * C + c]) * ldx + k];
+                for (int q = 0; q < 8; ++q) {
+                    const long row = (long)(bb + q) * Npts + arg[(long)(bb + q) * C + c];
+                    cf[q] = coef[(long)(bb + q) * C + c];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) a = __builtin_fmaf(coef[(long)(bb + q) * C + c], xv[q], a);
+                    for (int u = 0; u < 3; ++u) xv[q][u] = X[row * ldx + kk[u]];
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) acc[u] = __builtin_fmaf(cf[q], xv[q][u], acc[u]);
             }
-            for (; bb < B; ++bb) a = __builtin_fmaf(coef[(long)bb * C + c], X[((long)bb * Npts + arg[(long)bb * C + c]) * ldx + k], a);
-            dW[(long)c * lddw + k] = a;
+            for (; bb < B; ++bb) {
+                const long row = (long)bb * Npts + arg[(long)bb * C + c];
+                const float cf = coef[(long)bb * C + c];
+#pragma unroll
+                for (int u = 0; u < 3; ++u) acc[u] = __builtin_fmaf(cf, X[row * ldx + kk[u]], acc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+                if (k0 + 64 * u + lane < K) dW[(long)c * lddw + kk[u]] = acc[u];
         }
         __syncthreads();
     }
@@ -1482,6 +1889,18 @@ __global__ __launch_bounds__(256) void pw_tn_reduce_many_kernel(const TnReduceJo
     const float *part = jobs.part[j];
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     int q = 0;
+    for (; q + 16 <= S; q += 16) {         // sixteen slice loads issued before the first add; the adds in the order of the loop below
+        float sl[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) sl[u] = part[(long)(q + u) * total + t];
+#pragma unroll
+        for (int u = 0; u < 16; u += 4) {
+            a0 += sl[u];
+            a1 += sl[u + 1];
+            a2 += sl[u + 2];
+            a3 += sl[u + 3];
+        }
+    }
     for (; q + 4 <= S; q += 4) {
         a0 += part[(long)q * total + t];
         a1 += part[(long)(q + 1) * total + t];
@@ -1702,6 +2121,26 @@ extern "C" int fsg_pw_rowgemm_f32(const fsg_pw_rowgemm_args *a, int pro, int epi
     return FSG_ERR_UNSUPPORTED;
 }
 
+// the (PRO_BNBWD, PW_STORE | PW_BIAS, tile 5) member with fsg_pw_scatter_rows_f32 in its epilogue (see pw_rowgemm_kernel, SCAT)
+extern "C" int fsg_pw_rowgemm_scatter_f32(const fsg_pw_rowgemm_args *a, const void *sorted, const int32_t *first, const float *coef,
+                                          const float *W, int64_t ldw, int C, fsg_stream_t stream) {
+    const int rc = check_rowgemm(a, PRO_BNBWD, PW_STORE | PW_BIAS, 64);
+    if (rc != FSG_OK) return rc;
+    FSG_REQUIRE(sorted && first && coef && W, "fsg_pw_rowgemm_scatter_f32: NULL pointer");
+    FSG_REQUIRE(a->N <= 192 && a->store_n0 == 0 && a->rows_per_cloud > 0 && a->rows_per_cloud % 64 == 0 &&
+                    a->M % a->rows_per_cloud == 0 && a->rows_per_cloud <= (1 << 20) && C > 512 && C <= 1024 && ldw >= a->N,
+                "fsg_pw_rowgemm_scatter_f32: bad shape N=%d rows_per_cloud=%d M=%d C=%d (N <= 192, whole 64-row tiles per cloud, "
+                "512 < C <= 1024)", a->N, a->rows_per_cloud, a->M, C);
+    RowGemmArgs k = to_kernel_args(a);
+    k.sc_keys = reinterpret_cast<const unsigned *>(sorted);
+    k.sc_first = first;
+    k.sc_coef = coef;
+    k.sc_W = W;
+    k.sc_ldw = ldw;
+    k.sc_C = C;
+    return launch_rowgemm<1, 3, PRO_BNBWD, PW_STORE | PW_BIAS, 1, 3, 1>(k, (hipStream_t)stream, "fsg_pw_rowgemm_scatter_f32");
+}
+
 extern "C" size_t fsg_pw_tn_workspace_bytes(int N1, int N2, int M, int rows_per_slice) {
     if (rows_per_slice <= 0) return 0;
     return sizeof(float) * (size_t)((M + rows_per_slice - 1) / rows_per_slice) * N1 * N2;
@@ -1789,6 +2228,22 @@ extern "C" int fsg_pw_tn_reduce_f32(const fsg_pw_tn_reduce_jobs *jobs, fsg_strea
     return FSG_OK;
 }
 
+// fold of ONE deferred product whose rows < NI are wanted only as a B operand image (fsg_pw_weight_image_f32 of the (NI, N2)
+// matrix, stride N2, times scale, into k-steps ks0 .. of KS): the image is written straight from the sums, the matrix is not
+// stored.  Rows [NI, N1) -> C2 (fp32, row stride ldc2).  Sums in fsg_pw_tn_f32's own fold order.
+extern "C" int fsg_pw_tn_reduce_image_f32(const void *workspace, int S, int N1, int N2, int NI, float scale, int ks0, int KS,
+                                          void *image, float *C2, int64_t ldc2, fsg_stream_t stream) {
+    FSG_REQUIRE(workspace && image && ((uintptr_t)workspace & 15) == 0, "fsg_pw_tn_reduce_image_f32: NULL or unaligned pointer");
+    FSG_REQUIRE(S > 0 && N2 > 0 && NI > 0 && NI <= N1 && (NI == N1 || C2) && ks0 >= 0 && ks0 + (N2 + 15) / 16 <= KS,
+                "fsg_pw_tn_reduce_image_f32: bad shape S=%d N1=%d N2=%d NI=%d ks0=%d KS=%d", S, N1, N2, NI, ks0, KS);
+    const long threads = (long)((NI + 31) / 32) * ((N2 + 15) / 16) * 64 + (long)(N1 - NI) * N2;
+    hipLaunchKernelGGL(pw_tn_reduce_image_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float *>(workspace), S, N1, N2, NI, scale, ks0, KS, reinterpret_cast<u32x4 *>(image), C2,
+                       (long)ldc2);
+    FSG_CHECK_LAUNCH("fsg_pw_tn_reduce_image_f32");
+    return FSG_OK;
+}
+
 extern "C" int fsg_pw_bn_finalize_f32(const float *rec, int R, int ldn, int c0, int C, const float *shift, int B, int training,
                                       const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
                                       float *running_var, float *mean, float *invstd, float *alpha, float *delta, float *emu,
@@ -1868,6 +2323,20 @@ extern "C" int fsg_pw_logits_bwd_f32(const float *g, int classes, const float *W
     return FSG_OK;
 }
 
+// fsg_pw_logits_bwd_f32 + the bias gradient db (classes) = column sums of g in fsg_colsum_narrow_f32's summation order, by one
+// more workgroup of the same launch; classes: a power of two
+extern "C" int fsg_pw_logits_bwd_bias_f32(const float *g, int classes, const float *W3, const float *y, const float *alpha,
+                                          const float *delta, const float *mean, const float *invstd, int64_t M, int C, float slope,
+                                          float *da, float *rec2, float *db, fsg_stream_t stream) {
+    FSG_REQUIRE(g && W3 && y && alpha && delta && mean && invstd && da && rec2 && db && M > 0 && C > 0 && C % 64 == 0 && classes >= 1 &&
+                    classes <= 8 && (classes & (classes - 1)) == 0,
+                "fsg_pw_logits_bwd_bias_f32: bad arguments (C %% 64 == 0, classes in {1, 2, 4, 8})");
+    hipLaunchKernelGGL(pw_logits_bwd_bias_kernel, dim3((unsigned)((M + LB_ROWS - 1) / LB_ROWS) + 1), dim3(256), 0, (hipStream_t)stream, g,
+                       classes, W3, y, alpha, delta, mean, invstd, (long)M, C, slope, da, rec2, db);
+    FSG_CHECK_LAUNCH("fsg_pw_logits_bwd_bias_f32");
+    return FSG_OK;
+}
+
 extern "C" int fsg_pw_gf_prep_f32(const float *dc, const float *W0g, int64_t ldw0, int C0, const float *gfeat, float *dW0g,
                                   int64_t lddw0, const float *dg, const float *ysel, const float *alpha, const float *delta,
                                   const float *mean, const float *invstd, int B, int C, int64_t M, int training, float slope,
@@ -1894,6 +2363,40 @@ extern "C" int fsg_pw_gf_prep_f32(const float *dc, const float *W0g, int64_t ldw
     if (B <= 8) FSG_GF_PREP(8, 16);
     else FSG_GF_PREP(32, 4);
 #undef FSG_GF_PREP
+    return FSG_OK;
+}
+
+// fsg_pw_gf_prep_f32 (dc form) whose second launch also sorts the selection keys of fsg_pw_scatter_rows_f32 (512 < C <= 1024:
+// `sorted` (B, 1024) as that entry's workspace) and writes the tile table first (B, Npts / 64 + 1) of fsg_pw_rowgemm_scatter_f32
+extern "C" int fsg_pw_gf_prep_sort_f32(const float *dc, const float *W0g, int64_t ldw0, int C0, const float *gfeat, float *dW0g,
+                                       int64_t lddw0, const float *ysel, const float *alpha, const float *delta, const float *mean,
+                                       const float *invstd, int B, int C, int64_t M, int training, float slope, float *dbeta,
+                                       float *dgamma, float *P, float *Q, float *coef, const float *W, int64_t ldw, int K, float *Wq,
+                                       int64_t ldwq, const int32_t *arg, int Npts, void *sorted, int32_t *first, fsg_stream_t stream) {
+    FSG_REQUIRE(!Wq || (W && K > 0 && ldwq >= K + 1), "fsg_pw_gf_prep_sort_f32: Wq needs W, K, ldwq >= K + 1");
+    FSG_REQUIRE(ysel && alpha && delta && mean && invstd && dbeta && dgamma && P && Q && coef && B > 0 && B <= 32 && C > 0 && M > 0,
+                "fsg_pw_gf_prep_sort_f32: bad arguments (B <= 32)");
+    FSG_REQUIRE(dc && W0g && gfeat && dW0g && C0 > 0 && (size_t)(B <= 8 ? 8 : 32) * C0 * 4 <= 32 * 1024,
+                "fsg_pw_gf_prep_sort_f32: dc, W0g, gfeat, dW0g (C0 <= 1024 up to 8 clouds, <= 256 up to 32)");
+    FSG_REQUIRE(arg && sorted && first && C > 512 && C <= 1024 && Npts > 0 && Npts % 64 == 0 && Npts <= (1 << 20) &&
+                    ((uintptr_t)sorted & 15) == 0,
+                "fsg_pw_gf_prep_sort_f32: the sort needs arg, sorted, first, 512 < C <= 1024, Npts %% 64 == 0, Npts <= 2^20");
+#define FSG_GF_PREP_SORT(MAXB, WAVES)                                                                                                \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL((pw_gf_prep_kernel<MAXB, WAVES>), dim3((C + 63) / 64), dim3(64 * WAVES),                                \
+                           sizeof(float) * (MAXB * C0 + WAVES * MAXB * 64), (hipStream_t)stream, dc, W0g, (long)ldw0, C0, gfeat,    \
+                           dW0g, (long)lddw0, (const float *)nullptr, ysel, alpha, delta, mean, invstd, B, C, (long)M, training,   \
+                           slope, dbeta, dgamma, P, Q, coef, W, (long)ldw, K, Wq, (long)ldwq);                                     \
+        FSG_CHECK_LAUNCH("fsg_pw_gf_prep_sort_f32");                                                                               \
+        const int gx = (C + 255) / 256, gy = (C0 + 7) / 8;                                                                         \
+        hipLaunchKernelGGL((pw_outer_sort_kernel<MAXB>), dim3(gx, gy + (B + gx - 1) / gx), dim3(256), 0, (hipStream_t)stream, gy,  \
+                           dc, gfeat, B, C0, C, dW0g, (long)lddw0, Q, P, W, (long)ldw, K, Wq, (long)ldwq, arg, Npts,               \
+                           reinterpret_cast<unsigned *>(sorted), first);                                                          \
+        FSG_CHECK_LAUNCH("fsg_pw_gf_prep_sort_f32/outer");                                                                         \
+    } while (0)
+    if (B <= 8) FSG_GF_PREP_SORT(8, 16);
+    else FSG_GF_PREP_SORT(32, 4);
+#undef FSG_GF_PREP_SORT
     return FSG_OK;
 }
 
@@ -1925,7 +2428,7 @@ extern "C" int fsg_pw_gf_dw_f32(const float *coef, const int32_t *arg, const flo
                                 int Npts, float *dW, int64_t lddw, fsg_stream_t stream) {
     FSG_REQUIRE(coef && arg && X && s && W && G && P && Q && dW && B > 0 && C > 0 && K > 0 && Npts > 0, "fsg_pw_gf_dw_f32: bad arguments");
     FSG_REQUIRE(K <= 4096, "fsg_pw_gf_dw_f32: K = %d > 4096", K);
-    hipLaunchKernelGGL(pw_gf_dw_kernel, dim3((C + 3) / 4), dim3(256), sizeof(float) * (4 * K + 16 * 64), (hipStream_t)stream, coef, arg, X,
+    hipLaunchKernelGGL(pw_gf_dw_kernel, dim3((C + 3) / 4), dim3(256), sizeof(float) * (4 * K + 48 * 64), (hipStream_t)stream, coef, arg, X,
                        (long)ldx, s, W, (long)ldw, G, P, Q, B, C, K, Npts, dW, (long)lddw);
     FSG_CHECK_LAUNCH("fsg_pw_gf_dw_f32");
     return FSG_OK;

@@ -1176,6 +1176,21 @@ def pw_rowgemm(pro, epi, tile, **kw):
         _lib.call("fsg_pw_rowgemm_f32", ctypes.byref(a), pro, epi, tile, _stream())
 
 
+def pw_rowgemm_scatter(sorted_keys, first, coef, W, **kw):
+    """include/fsg_hip.h: fsg_pw_rowgemm_scatter_f32 -- the (PRO_BNBWD, PW_STORE | PW_BIAS, tile 5) product with
+    fsg_pw_scatter_rows_f32 in its epilogue; sorted_keys / first: from fsg_pw_gf_prep_sort_f32; keyword arguments as pw_rowgemm"""
+    a = _lib.PWRowGemmArgs()
+    keep = []
+    for k, v in kw.items():
+        if torch.is_tensor(v):
+            keep.append(v)
+            v = v.data_ptr()
+        setattr(a, k, v)
+    with torch.cuda.device(coef.device):
+        _lib.call("fsg_pw_rowgemm_scatter_f32", ctypes.byref(a), _p(sorted_keys), _p(first), _p(coef), _p(W), W.stride(0),
+                  coef.shape[1], _stream())
+
+
 def pw_tn(tile, C1, ldc1, C2=None, ldc2=0, defer=None, **kw):
     """include/fsg_hip.h: fsg_pw_tn_f32.  `defer`: a list -- the slices stay in their workspace and the job is appended to the
     list, to be folded by `pw_tn_reduce(list)` together with the other products' (one launch instead of one per product)"""
@@ -1341,7 +1356,12 @@ class _SegHead(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _lib.call(name, *a, _stream())
         # ---- logits layer
-        db3 = _bias_grad(gout)
+        # folded tail (set_fused_head_tail): db3 by one more workgroup of the logits launch, where _bias_grad would take
+        # fsg_colsum_narrow_f32 (the same sums in the same order); the key sort + tile table in the launch behind gf_prep and the
+        # scatter in the epilogue of the dlv product, where the head takes the 64 x 192 tile and the 1024-key sort
+        tail_bias = _fused_head_tail and (CLS & (CLS - 1)) == 0 and 4096 <= M * CLS <= 131072
+        tail_scatter = _fused_head_tail and KL == 192 and 512 < CG <= 1024
+        db3 = torch.empty(CLS, **f32) if tail_bias else _bias_grad(gout)
         dW3 = torch.empty(CLS, C2, **f32)
         folds = []                      # the four weight-gradient products leave their row slices; one launch folds them at the end
         pw_tn(3, dW3, C2, defer=folds, L1=gout, ldl1=CLS, N1a=CLS, N1b=0, lpro=PRO_NONE, R=y2, ldr=C2, N2=C2, rpro=PRO_BNACT, ralpha=al_2,
@@ -1349,8 +1369,12 @@ class _SegHead(torch.autograd.Function):
         da2 = torch.empty(M, C2, **f32)
         Rb = (M + 31) // 32
         r2b = torch.empty(Rb, 2, C2, **f32)
-        call("fsg_pw_logits_bwd_f32", _p(gout), CLS, _p(W3), _p(y2), _p(al_2), _p(de_2), _p(mean_2), _p(inv_2), M, C2, slope,
-             _p(da2), _p(r2b))
+        if tail_bias:
+            call("fsg_pw_logits_bwd_bias_f32", _p(gout), CLS, _p(W3), _p(y2), _p(al_2), _p(de_2), _p(mean_2), _p(inv_2), M, C2, slope,
+                 _p(da2), _p(r2b), _p(db3))
+        else:
+            call("fsg_pw_logits_bwd_f32", _p(gout), CLS, _p(W3), _p(y2), _p(al_2), _p(de_2), _p(mean_2), _p(inv_2), M, C2, slope,
+                 _p(da2), _p(r2b))
 
         def bwd_fin(rec, R, C, training, alpha, inv, emu, per_cloud, cm=None, want_dc=False):
             nb = B if per_cloud else 1
@@ -1391,16 +1415,31 @@ class _SegHead(torch.autograd.Function):
         W0G, dW0G = W0[:, KL:], dW0[:, KL:]
         ldq = (KL + 4) & ~3
         Wq = torch.empty(CG, ldq, **f32)                                   # rows [Q o Wg | -P]
-        call("fsg_pw_gf_prep_f32", _p(dc), _p(W0G), W0.stride(0), C0, _p(g), _p(dW0G), dW0.stride(0), None, _p(ysel), _p(al_g),
-             _p(de_g), _p(mean_g), _p(inv_g), B, CG, M, int(tr_g), slope, _p(dbg), _p(dgg), _p(Pg), _p(Qg), _p(coef), _p(Wg),
-             Wg.stride(0), KL, _p(Wq), ldq)
+        if tail_scatter:
+            skeys = torch.empty(B, 1024, dtype=torch.int32, device=dev)         # sorted (arg << 12 | channel) per cloud
+            sfirst = torch.empty(B, Npts // 64 + 1, dtype=torch.int32, device=dev)
+            call("fsg_pw_gf_prep_sort_f32", _p(dc), _p(W0G), W0.stride(0), C0, _p(g), _p(dW0G), dW0.stride(0), _p(ysel), _p(al_g),
+                 _p(de_g), _p(mean_g), _p(inv_g), B, CG, M, int(tr_g), slope, _p(dbg), _p(dgg), _p(Pg), _p(Qg), _p(coef), _p(Wg),
+                 Wg.stride(0), KL, _p(Wq), ldq, _p(arg), Npts, _p(skeys), _p(sfirst))
+        else:
+            call("fsg_pw_gf_prep_f32", _p(dc), _p(W0G), W0.stride(0), C0, _p(g), _p(dW0G), dW0.stride(0), None, _p(ysel), _p(al_g),
+                 _p(de_g), _p(mean_g), _p(inv_g), B, CG, M, int(tr_g), slope, _p(dbg), _p(dgg), _p(Pg), _p(Qg), _p(coef), _p(Wg),
+                 Wg.stride(0), KL, _p(Wq), ldq)
         # [M1 ; npvec] = [Q o Wg | -P]^T Wg with M1 = Wg^T diag(Q) Wg: one row contraction over the CG channel rows
-        m1n = torch.empty(KL + 1, KL, **f32)
-        pw_tn(3, m1n, KL, L1=Wq, ldl1=ldq, N1a=KL + 1, N1b=0, lpro=PRO_NONE, R=Wg, ldr=Wg.stride(0), N2=KL, rpro=PRO_NONE, slope=slope,
-              M=CG, rows_per_cloud=0, rows_per_slice=64)
-        M1, npvec = m1n[:KL], m1n[KL]
         ks_a, ks_b = C0 // 16, KL // 16
-        pw_weight_image(M1, scale=-1.0, out=img_lv, ks0=ks_a, KS=ks_a + ks_b)
+        tn_m1 = dict(L1=Wq, ldl1=ldq, N1a=KL + 1, N1b=0, lpro=PRO_NONE, R=Wg, ldr=Wg.stride(0), N2=KL, rpro=PRO_NONE, slope=slope,
+                     M=CG, rows_per_cloud=0, rows_per_slice=64)
+        if _fused_head_tail:       # the fold writes -M1 straight into the B image; M1 itself is not stored
+            npvec = torch.empty(KL, **f32)
+            part = []
+            pw_tn(3, npvec, KL, defer=part, **tn_m1)
+            call("fsg_pw_tn_reduce_image_f32", _p(part[0][0]), part[0][5], KL + 1, KL, KL, -1.0, ks_a, ks_a + ks_b, _p(img_lv),
+                 _p(npvec), KL)
+        else:
+            m1n = torch.empty(KL + 1, KL, **f32)
+            pw_tn(3, m1n, KL, **tn_m1)
+            M1, npvec = m1n[:KL], m1n[KL]
+            pw_weight_image(M1, scale=-1.0, out=img_lv, ks0=ks_a, KS=ks_a + ks_b)
         Gs = torch.empty(KL + 1, KL, **f32)          # [X^T X ; column sums of X] (the all-ones column behind the left operand)
         G, s = Gs[:KL], Gs[KL]
         pw_tn(5, dW0, KL + CG, Gs, KL, defer=folds, ones=1, L1=da0, LY1=y0, L2=levels, ldl1=C0, ldl2=levels.stride(0), N1a=C0, N1b=KL, lpro=PRO_BNBWD,
@@ -1411,11 +1450,15 @@ class _SegHead(torch.autograd.Function):
         # the 64 x 192 tile (5) for the (B N, 448) x (448, 192) input-gradient product of the first head layer: its BatchNorm-backward
         # prologue + split is then done once per row instead of once per column tile (38.8 -> 33.1 us).  The 64 x 256 tile for the
         # 256-wide products was measured SLOWER (24.9 vs 20.7 us, 25.5 vs 21.3 us: 120 KB of LDS = one workgroup per CU)
-        pw_rowgemm(PRO_BNBWD, PW_STORE | PW_BIAS, 5 if KL == 192 else 4, A1=da0, Y1=y0, A2=levels, lda1=C0, lda2=levels.stride(0), K1=C0, K2=KL,
-                   Bimg=img_lv, M=M, N=KL, rows_per_cloud=Npts, alpha=al_0, delta=de_0, P=P0, Q=Q0, tstride=C0, slope=slope,
-                   C=dlv, ldc=KL, store_n0=0, bias=npvec)
-        sws = _lib.workspace("fsg_pw_scatter_rows", B, CG, device=dev)
-        call("fsg_pw_scatter_rows_f32", _p(coef), _p(arg), _p(Wg), Wg.stride(0), B, CG, KL, Npts, _p(dlv), KL, _p(sws))
+        gemm_lv = dict(A1=da0, Y1=y0, A2=levels, lda1=C0, lda2=levels.stride(0), K1=C0, K2=KL, Bimg=img_lv, M=M, N=KL,
+                       rows_per_cloud=Npts, alpha=al_0, delta=de_0, P=P0, Q=Q0, tstride=C0, slope=slope, C=dlv, ldc=KL, store_n0=0,
+                       bias=npvec)
+        if tail_scatter:           # the scatter of the selected rows rides in the product's epilogue
+            pw_rowgemm_scatter(skeys, sfirst, coef, Wg, **gemm_lv)
+        else:
+            pw_rowgemm(PRO_BNBWD, PW_STORE | PW_BIAS, 5 if KL == 192 else 4, **gemm_lv)
+            sws = _lib.workspace("fsg_pw_scatter_rows", B, CG, device=dev)
+            call("fsg_pw_scatter_rows_f32", _p(coef), _p(arg), _p(Wg), Wg.stride(0), B, CG, KL, Npts, _p(dlv), KL, _p(sws))
         dWg = torch.empty(CG, KL, **f32)
         call("fsg_pw_gf_dw_f32", _p(coef), _p(arg), _p(levels), levels.stride(0), _p(s), _p(Wg), Wg.stride(0), _p(G), _p(Pg), _p(Qg),
              B, CG, KL, Npts, _p(dWg), KL)
@@ -1437,6 +1480,18 @@ def set_fused_head(flag):
     (the round-2 path, kept for shapes outside the fused kernels' envelope and as their cross-check); returns the old value"""
     global _fused_head
     old, _fused_head = _fused_head, bool(flag)
+    return old
+
+
+_fused_head_tail = True
+
+
+def set_fused_head_tail(flag):
+    """the folded tail of the fused head's backward (bias gradient in the logits launch, key sort behind gf_prep, -M1 image
+    from the fold, scatter in the dlv product's epilogue: include/fsg_hip.h) on / off; off = the separate launches, which
+    also serve the widths outside the folded kernels' envelope.  Both give the same bits.  Returns the old value"""
+    global _fused_head_tail
+    old, _fused_head_tail = _fused_head_tail, bool(flag)
     return old
 
 

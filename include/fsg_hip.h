@@ -827,6 +827,34 @@ int fsg_pw_gf_dw_f32(const float *coef, const int32_t *arg, const float *X, int6
                      int64_t lddw, fsg_stream_t stream);
 
 /*
+ * The tail of the head's backward with four launches folded into their neighbours.  Every entry computes what the sequence it
+ * replaces computes, BIT FOR BIT (same operations, same order; tests/test_pw_tail_gpu.py compares with torch.equal):
+ * fsg_pw_logits_bwd_bias_f32 = fsg_pw_logits_bwd_f32 + fsg_colsum_narrow_f32(g, M, classes) -> db, one more workgroup of the
+ *   same launch (classes a power of two).
+ * fsg_pw_gf_prep_sort_f32 = fsg_pw_gf_prep_f32 (dc form) + the key sort of fsg_pw_scatter_rows_f32 in the second launch
+ *   (512 < C <= 1024): sorted (B, 1024) keys (arg << 12 | channel) ascending, padded with 0xFFFFFFFF -- what that entry leaves
+ *   in its workspace -- and first (B, Npts / 64 + 1): first[b][t] = number of channels of cloud b with arg < 64 t.
+ * fsg_pw_tn_reduce_image_f32 = the fold of fsg_pw_tn_f32 (called with C1 == NULL: slices left in `workspace`, S of them, N1 x N2
+ *   each) + fsg_pw_weight_image_f32(rows < NI as an (NI, N2) matrix, scale, ks0, KS) -> image; rows [NI, N1) -> C2 (fp32).
+ * fsg_pw_rowgemm_scatter_f32 = fsg_pw_rowgemm_f32(PRO_BNBWD, PW_STORE | PW_BIAS, tile 5) + fsg_pw_scatter_rows_f32 on its output
+ *   (K = N <= 192, Npts = rows_per_cloud, a multiple of 64 that divides M; sorted / first from fsg_pw_gf_prep_sort_f32): the
+ *   workgroup that owns 64 rows adds their selected sums before it stores them.  A tile walks its own entries alone: up to C
+ *   of them when every channel of a cloud selects rows of one tile.
+ */
+int fsg_pw_logits_bwd_bias_f32(const float *g, int classes, const float *W3, const float *y, const float *alpha,
+                               const float *delta, const float *mean, const float *invstd, int64_t M, int C, float slope,
+                               float *da, float *rec2, float *db, fsg_stream_t stream);
+int fsg_pw_gf_prep_sort_f32(const float *dc, const float *W0g, int64_t ldw0, int C0, const float *gfeat, float *dW0g, int64_t lddw0,
+                            const float *ysel, const float *alpha, const float *delta, const float *mean, const float *invstd,
+                            int B, int C, int64_t M, int training, float slope, float *dbeta, float *dgamma, float *P, float *Q,
+                            float *coef, const float *W, int64_t ldw, int K, float *Wq, int64_t ldwq, const int32_t *arg, int Npts,
+                            void *sorted, int32_t *first, fsg_stream_t stream);
+int fsg_pw_tn_reduce_image_f32(const void *workspace, int S, int N1, int N2, int NI, float scale, int ks0, int KS, void *image,
+                               float *C2, int64_t ldc2, fsg_stream_t stream);
+int fsg_pw_rowgemm_scatter_f32(const fsg_pw_rowgemm_args *args, const void *sorted, const int32_t *first, const float *coef,
+                               const float *W, int64_t ldw, int C, fsg_stream_t stream);
+
+/*
  * Image front end on single-channel fp32 volumes (B, D, H, W), contiguous: Foerstner keypoints
  * (data_processing/foerstner.py:62-108) and MIND descriptors (data_processing/point_features.py:86-150).  Everything here is
  * an evaluation primitive, not differentiable.  `weights` (HOST, N odd <= 9 floats) are the taps of utils/image_utils.py:
