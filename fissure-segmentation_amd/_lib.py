@@ -38,6 +38,7 @@ SIGNATURES = {
     "fsg_edge_weights_fwd_f32": ([_P, _I, _I, _P, _P], _I),
     "fsg_edge_weights_bwd_f32": ([_P, _I, _I, _P, _P], _I),
     "fsg_edge_weights_many_f32": ([_P, _I, _P], _I),
+    "fsg_edge_weights_bwd_folded_f32": ([_P, _P], _I),
     "fsg_edgeconv1_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
     "fsg_edgeconv1_fwd_f32": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
                               _I),
@@ -73,6 +74,7 @@ SIGNATURES = {
     "fsg_colsum_narrow_f32": ([_P, _L, _I, _P, _P], _I),
     "fsg_fold_layer1_f32": ([_P, _I, _P, _L, _P, _I, _I, _I, _I, _P, _P], _I),
     "fsg_adam_flat_f32": ([_P, _P, _P, _P, _P, _L, _F, _P, _F, _F, _F, _F, _P], _I),
+    "fsg_adam_flat_segments_f32": ([_P, _P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P], _I),
     "fsg_nnu_loss_workspace_bytes": ([_I], ctypes.c_size_t),
     "fsg_nnu_loss_f32": ([_P, _L, _L, _L, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _L, _P, _P], _I),
     "fsg_bn_rows_workspace_bytes": ([ctypes.c_long, _I], ctypes.c_size_t),
@@ -83,6 +85,7 @@ SIGNATURES = {
     "fsg_gemm_small_rowsum_f32": ([_P, _L, _L, _P, _L, _L, _P, _P, _L, _I, _I, _I, _P, _P, _P], _I),
     "fsg_gemm_small_deferred_f32": ([_P, _L, _L, _P, _L, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P], _I),
     "fsg_gemm_small_reduce_many_f32": ([_P, _P], _I),
+    "fsg_gemm_small_many_deferred_f32": ([_P, _P], _I),
     "fsg_gemm_small_bf16": ([_P, _L, _L, _P, _L, _L, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P], _I),
     "fsg_pt_attn_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
     "fsg_pt_attn_fwd_f32": ([_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
@@ -224,9 +227,30 @@ class GemmReduceJobs(ctypes.Structure):
                 ("J", _I * GEMM_REDUCE_MAX_JOBS), ("blocks", _I * GEMM_REDUCE_MAX_JOBS), ("n", _I)]
 
 
+ADAM_MAX_SEGMENTS = 128
+
+
+class AdamSegments(ctypes.Structure):
+    """include/fsg_hip.h: fsg_adam_segments"""
+    _fields_ = [("grad", _P * ADAM_MAX_SEGMENTS), ("offset", _L * ADAM_MAX_SEGMENTS), ("count", _L * ADAM_MAX_SEGMENTS),
+                ("n", _I)]
+
+
+class GemmSmallJobs(ctypes.Structure):
+    """include/fsg_hip.h: fsg_gemm_small_jobs"""
+    _fields_ = [("A", _P * 8), ("sa_i", _L * 8), ("sa_k", _L * 8), ("B", _P * 8), ("sb_k", _L * 8), ("sb_j", _L * 8),
+                ("C", _P * 8), ("ldc", _L * 8), ("I", _I * 8), ("J", _I * 8), ("K", _I * 8), ("workspace", _P * 8),
+                ("splits", _I * 8), ("n", _I)]
+
+
 class EdgeWeightJobs(ctypes.Structure):
     """include/fsg_hip.h: fsg_edge_weight_jobs"""
     _fields_ = [("src", _P * 8), ("dst", _P * 8), ("Co", _I * 8), ("C", _I * 8), ("n", _I)]
+
+
+class EdgeWeightFoldJobs(ctypes.Structure):
+    """include/fsg_hip.h: fsg_edge_weight_fold_jobs"""
+    _fields_ = [("src", _P * 8), ("dst", _P * 8), ("Co", _I * 8), ("C", _I * 8), ("S", _I * 8), ("n", _I)]
 
 
 class PWRowGemmArgs(ctypes.Structure):

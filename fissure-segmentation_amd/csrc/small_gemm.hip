@@ -19,15 +19,16 @@ namespace {
 constexpr int TI = 64, TJ = 64, TK = 32, LDT = 65;  // k-major LDS tiles [TK][64 + 1]
 constexpr int LPT = TI * TK / 256;                  // tile elements per thread and operand
 
-__global__ __launch_bounds__(256) void gemm_small_kernel(const float *__restrict__ A, long sai, long sak,
-                                                         const float *__restrict__ B, long sbk, long sbj,
-                                                         const float *__restrict__ bias, float *__restrict__ C, long ldc,
-                                                         int I, int J, int K, int kchunk, float *__restrict__ part,
-                                                         float *__restrict__ rowsum) {
-    __shared__ float As[TK * LDT], Bs[TK * LDT];
+// one workgroup's share of a product: output tile (bx, by), reduction split bz of nz.  The body of gemm_small_kernel (grid = tiles
+// x splits of ONE product) and of gemm_small_many_kernel (the workgroups of several products behind each other in one grid):
+// whichever launch runs a tile, it runs the same instructions in the same order.
+__device__ __forceinline__ void gemm_small_tile(const float *__restrict__ A, long sai, long sak, const float *__restrict__ B,
+                                                long sbk, long sbj, const float *__restrict__ bias, float *__restrict__ C, long ldc,
+                                                int I, int J, int K, int kchunk, float *__restrict__ part,
+                                                float *__restrict__ rowsum, int bx, int by, int bz, int nz, float *As, float *Bs) {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, ql = lane & 31, half = lane >> 5;
-    const int i0 = blockIdx.x * TI, j0 = blockIdx.y * TJ;
-    const int kbeg = blockIdx.z * kchunk, kend = min(K, kbeg + kchunk);
+    const int i0 = bx * TI, j0 = by * TJ;
+    const int kbeg = bz * kchunk, kend = min(K, kbeg + kchunk);
     const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;  // this wave's 32 x 32 quadrant
     // loader mapping: consecutive threads along whichever tile dimension is contiguous in memory
     const bool a_kfast = sak == 1, b_kfast = sbk == 1;
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(const float *__restrict
     // optional by-product: rowsum[i] = sum_k A(i, k) -- with A = dY^T this is the bias gradient of the Linear whose weight
     // gradient the product is (one ATen column reduction less per Linear).  The first column of workgroups sums its A tiles as
     // they pass through LDS: thread i < 64 walks the tile's 32 k-rows of row i; k order is fixed, so it is reproducible.
-    const bool do_rs = rowsum != nullptr && blockIdx.y == 0 && tid < TI;
+    const bool do_rs = rowsum != nullptr && by == 0 && tid < TI;
     float rs = 0.f;
     if (kbeg < kend) fetch(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += TK) {
@@ -74,14 +75,14 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(const float *__restrict
                                                        acc, 0, 0, 0);
     }
     if (do_rs && i0 + tid < I) {
-        // partial sums of the splits behind the partial products: [S][I] at part + S * I * J (gridDim.z = S)
-        if (part) part[(long)gridDim.z * I * J + (long)blockIdx.z * I + i0 + tid] = rs;
+        // partial sums of the splits behind the partial products: [S][I] at part + S * I * J (nz = S)
+        if (part) part[(long)nz * I * J + (long)bz * I + i0 + tid] = rs;
         else rowsum[i0 + tid] = rs;
     }
     const int col = j0 + wj + ql;
     if (col >= J) return;
     if (part) {
-        float *dst = part + (long)blockIdx.z * I * J;
+        float *dst = part + (long)bz * I * J;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int row = i0 + wi + (e & 3) + 8 * (e >> 2) + 4 * half;
@@ -95,6 +96,42 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(const float *__restrict
             if (row < I) C[(long)row * ldc + col] = acc[e] + bb;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void gemm_small_kernel(const float *__restrict__ A, long sai, long sak,
+                                                         const float *__restrict__ B, long sbk, long sbj,
+                                                         const float *__restrict__ bias, float *__restrict__ C, long ldc,
+                                                         int I, int J, int K, int kchunk, float *__restrict__ part,
+                                                         float *__restrict__ rowsum) {
+    __shared__ float As[TK * LDT], Bs[TK * LDT];
+    gemm_small_tile(A, sai, sak, B, sbk, sbj, bias, C, ldc, I, J, K, kchunk, part, rowsum, blockIdx.x, blockIdx.y, blockIdx.z,
+                    gridDim.z, As, Bs);
+}
+
+// fsg_gemm_small_many_deferred_f32: the workgroups of up to FSG_GEMM_SMALL_MAX_JOBS products in ONE grid, job after job.  The weight
+// gradients of the EdgeConv [P | Q] Linears are 256 workgroups each, one per CU, bounded by their own chain of loads: launched
+// together they share the chip instead of queueing behind each other.  Tiles, splits and arithmetic per product are those of
+// gemm_small_launch, so every partial product has the bits it has when the product runs alone.
+struct SmallGemmJobs {
+    const float *A[FSG_GEMM_SMALL_MAX_JOBS], *B[FSG_GEMM_SMALL_MAX_JOBS];
+    float *C[FSG_GEMM_SMALL_MAX_JOBS], *part[FSG_GEMM_SMALL_MAX_JOBS];
+    long sai[FSG_GEMM_SMALL_MAX_JOBS], sak[FSG_GEMM_SMALL_MAX_JOBS], sbk[FSG_GEMM_SMALL_MAX_JOBS], sbj[FSG_GEMM_SMALL_MAX_JOBS];
+    long ldc[FSG_GEMM_SMALL_MAX_JOBS];
+    int I[FSG_GEMM_SMALL_MAX_JOBS], J[FSG_GEMM_SMALL_MAX_JOBS], K[FSG_GEMM_SMALL_MAX_JOBS], kchunk[FSG_GEMM_SMALL_MAX_JOBS];
+    int ti[FSG_GEMM_SMALL_MAX_JOBS], tj[FSG_GEMM_SMALL_MAX_JOBS], S[FSG_GEMM_SMALL_MAX_JOBS];
+    int first[FSG_GEMM_SMALL_MAX_JOBS];      // first workgroup of the job
+    int n;
+};
+__global__ __launch_bounds__(256) void gemm_small_many_kernel(SmallGemmJobs jobs) {
+    __shared__ float As[TK * LDT], Bs[TK * LDT];
+    int j = 0;
+    while (j + 1 < jobs.n && (int)blockIdx.x >= jobs.first[j + 1]) ++j;
+    int b = blockIdx.x - jobs.first[j];
+    const int bx = b % jobs.ti[j];
+    b /= jobs.ti[j];
+    const int by = b % jobs.tj[j], bz = b / jobs.tj[j];
+    gemm_small_tile(jobs.A[j], jobs.sai[j], jobs.sak[j], jobs.B[j], jobs.sbk[j], jobs.sbj[j], nullptr, jobs.C[j], jobs.ldc[j],
+                    jobs.I[j], jobs.J[j], jobs.K[j], jobs.kchunk[j], jobs.part[j], nullptr, bx, by, bz, jobs.S[j], As, Bs);
 }
 
 // bf16 operand mode (BASELINE config 3 names bf16): the same tiling, split and epilogue, but both operands are rounded to bf16
@@ -237,6 +274,73 @@ __global__ __launch_bounds__(256) void gemm_small_reduce_kernel(const float *__r
     }
 }
 
+// from this many splits on the split sum runs sliced (gemm_small_reduce_kernel), below it flat (gemm_small_reduce_flat_kernel)
+constexpr int SLICED_MIN_S = 16;
+
+// fsg_edge_weights_bwd_folded_f32: the split sum of the [P | Q] weight gradient grad_Wt (2Co, C) inside the element-wise transform
+// that consumes it -- grad_W[r][c] = gP - gQ, grad_W[r][C + c] = gQ with gP = grad_Wt[r][c], gQ = grad_Wt[Co + r][c] -- so the
+// sums take no launch of their own and grad_Wt is never written.  One pair (r, c) per 16 threads; the adds are the two reduce
+// kernels' above, in their order (S >= SLICED_MIN_S: sixteen slices s = sl, sl + 16, ..., then the slice sums in slice order;
+// below: s = 0, 1, ...), hence the same bits.  Split loads go out eight per operand at a time, not one dependent load after another.
+constexpr int FOLD_BATCH = 8;
+__device__ __forceinline__ void fold_sum2(const float *__restrict__ part, long IJ, long ip, long iq, int s_begin, int s_step, int S,
+                                          float &ap, float &aq) {
+    for (int s0 = s_begin; s0 < S; s0 += s_step * FOLD_BATCH) {
+        float vp[FOLD_BATCH], vq[FOLD_BATCH];
+#pragma unroll
+        for (int u = 0; u < FOLD_BATCH; ++u) {
+            const int s = s0 + s_step * u;
+            vp[u] = s < S ? part[(long)s * IJ + ip] : 0.f;
+            vq[u] = s < S ? part[(long)s * IJ + iq] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < FOLD_BATCH; ++u)
+            if (s0 + s_step * u < S) {
+                ap += vp[u];
+                aq += vq[u];
+            }
+    }
+}
+__global__ __launch_bounds__(256) void edge_weights_bwd_folded_kernel(fsg_edge_weight_fold_jobs jobs) {
+    __shared__ float red[2][16][17];
+    const int j = blockIdx.y;
+    const int Co = jobs.Co[j], C = jobs.C[j], S = jobs.S[j];
+    const int o = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int t = blockIdx.x * 16 + o;
+    const bool live = t < Co * C;
+    const float *__restrict__ src = jobs.src[j];
+    const long IJ = 2L * Co * C;
+    const int r = t / C, c = t - r * C;
+    const long ip = (long)r * C + c, iq = (long)(Co + r) * C + c;
+    float gp = 0.f, gq = 0.f;
+    if (S >= SLICED_MIN_S) {     // (S is the job's: the whole workgroup takes this branch or none of it)
+        float ap = 0.f, aq = 0.f;
+        if (live) fold_sum2(src, IJ, ip, iq, sl, 16, S, ap, aq);
+        red[0][sl][o] = ap;
+        red[1][sl][o] = aq;
+        __syncthreads();
+        if (sl == 0) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                gp += red[0][i][o];
+                gq += red[1][i][o];
+            }
+        }
+    } else if (sl == 0 && live) {
+        if (S > 1) {
+            fold_sum2(src, IJ, ip, iq, 0, 1, S, gp, gq);
+        } else {
+            gp = src[ip];
+            gq = src[iq];
+        }
+    }
+    if (sl == 0 && live) {
+        float *dst = jobs.dst[j] + (long)r * 2 * C;
+        dst[c] = gp - gq;
+        dst[C + c] = gq;
+    }
+}
+
 // the reductions of up to FSG_GEMM_REDUCE_MAX_JOBS deferred products in ONE launch (fsg_gemm_small_reduce_many_f32): the weight
 // gradients of a backward pass are read by nobody until the optimizer runs, so their split sums need not sit between the
 // products on the stream.  One thread per output, splits summed in split order (fixed: reproducible).
@@ -340,6 +444,51 @@ extern "C" int fsg_gemm_small_reduce_many_f32(const fsg_gemm_reduce_jobs *jobs, 
     return FSG_OK;
 }
 
+extern "C" int fsg_gemm_small_many_deferred_f32(fsg_gemm_small_jobs *jobs, fsg_stream_t stream) {
+    FSG_REQUIRE(jobs && jobs->n >= 1 && jobs->n <= FSG_GEMM_SMALL_MAX_JOBS, "fsg_gemm_small_many_deferred_f32: 1..%d jobs",
+                FSG_GEMM_SMALL_MAX_JOBS);
+    SmallGemmJobs t = {};
+    t.n = jobs->n;
+    long total = 0;
+    for (int j = 0; j < jobs->n; ++j) {
+        const int I = jobs->I[j], J = jobs->J[j], K = jobs->K[j];
+        FSG_REQUIRE(jobs->A[j] && jobs->B[j] && jobs->C[j], "fsg_gemm_small_many_deferred_f32: NULL pointer in job %d", j);
+        FSG_REQUIRE(I > 0 && J > 0 && K > 0 && jobs->ldc[j] >= J, "fsg_gemm_small_many_deferred_f32: bad shape I=%d J=%d K=%d in job %d",
+                    I, J, K, j);
+        // (the split rule of gemm_small_launch)
+        const int S = splits_for(I, J, K);
+        FSG_REQUIRE(S == 1 || jobs->workspace[j], "fsg_gemm_small_many_deferred_f32: job %d needs the workspace", j);
+        const int kchunk = fsg_cdiv(fsg_cdiv(K, S), TK) * TK, S_eff = fsg_cdiv(K, kchunk);
+        t.A[j] = jobs->A[j], t.B[j] = jobs->B[j], t.C[j] = jobs->C[j];
+        t.part[j] = S_eff > 1 ? (float *)jobs->workspace[j] : nullptr;
+        t.sai[j] = jobs->sa_i[j], t.sak[j] = jobs->sa_k[j], t.sbk[j] = jobs->sb_k[j], t.sbj[j] = jobs->sb_j[j], t.ldc[j] = jobs->ldc[j];
+        t.I[j] = I, t.J[j] = J, t.K[j] = K, t.kchunk[j] = kchunk, t.ti[j] = fsg_cdiv(I, TI), t.tj[j] = fsg_cdiv(J, TJ), t.S[j] = S_eff;
+        t.first[j] = (int)total;
+        total += (long)t.ti[j] * t.tj[j] * S_eff;
+        FSG_REQUIRE(total < (1L << 31), "fsg_gemm_small_many_deferred_f32: too many workgroups");
+        jobs->splits[j] = S_eff > 1 ? S_eff : 0;
+    }
+    hipLaunchKernelGGL(gemm_small_many_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, t);
+    FSG_CHECK_LAUNCH("fsg_gemm_small_many_deferred_f32");
+    return FSG_OK;
+}
+
+extern "C" int fsg_edge_weights_bwd_folded_f32(const fsg_edge_weight_fold_jobs *jobs, fsg_stream_t stream) {
+    FSG_REQUIRE(jobs && jobs->n >= 1 && jobs->n <= FSG_EDGE_WEIGHT_MAX_JOBS, "fsg_edge_weights_bwd_folded_f32: 1..%d jobs",
+                FSG_EDGE_WEIGHT_MAX_JOBS);
+    long most = 0;
+    for (int j = 0; j < jobs->n; ++j) {
+        FSG_REQUIRE(jobs->src[j] && jobs->dst[j] && jobs->Co[j] > 0 && jobs->C[j] > 0 && jobs->S[j] >= 0 &&
+                        2L * jobs->Co[j] * jobs->C[j] < (1L << 31),
+                    "fsg_edge_weights_bwd_folded_f32: bad job %d", j);
+        const long e = (long)jobs->Co[j] * jobs->C[j];
+        most = e > most ? e : most;
+    }
+    hipLaunchKernelGGL(edge_weights_bwd_folded_kernel, dim3(fsg_cdiv(most, 16), jobs->n), dim3(256), 0, (hipStream_t)stream, *jobs);
+    FSG_CHECK_LAUNCH("fsg_edge_weights_bwd_folded_f32");
+    return FSG_OK;
+}
+
 namespace {
 int gemm_small_launch(const float *A, int64_t sa_i, int64_t sa_k, const float *B, int64_t sb_k, int64_t sb_j, const float *bias,
                       float *C, int64_t ldc, int I, int J, int K, float *rowsum, void *workspace, int *deferred_splits,
@@ -366,7 +515,7 @@ int gemm_small_launch(const float *A, int64_t sa_i, int64_t sa_k, const float *B
     }
     if (part) {
         const long IJ = (long)I * J, outs = IJ + (rowsum ? I : 0);
-        if (S_eff >= 16)
+        if (S_eff >= SLICED_MIN_S)
             hipLaunchKernelGGL(gemm_small_reduce_kernel, dim3(fsg_cdiv(IJ, 16) + (rowsum ? fsg_cdiv(I, 16) : 0)), dim3(256), 0, st, part,
                                S_eff, IJ, J, bias, C, (long)ldc, I, rowsum);
         else

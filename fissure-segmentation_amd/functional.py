@@ -335,6 +335,7 @@ class _LinearPM(torch.autograd.Function):
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.pw16 = False
+        ctx.fold = _fold_slot(w)
         tw, tb = _grad_targets(w), (_grad_targets(b) if b is not None else ())
         ctx.defer_targets = tw + tb if (tw is not None and tb is not None) else None
         x2 = x.reshape(-1, x.shape[-1])
@@ -364,6 +365,8 @@ class _LinearPM(torch.autograd.Function):
         gx = gw = gb = None
         if not g2.is_contiguous():
             g2 = g2.contiguous()
+        if ctx.fold is not None:
+            ctx.fold.pending = None
         if ctx.gs16:     # dX = bf16(dY) bf16(W), dW = bf16(dY)^T bf16(X) (+ the bias gradient: row sums of the rounded dY^T)
             N, K = w.shape
             M = g2.shape[0]
@@ -389,7 +392,9 @@ class _LinearPM(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             gx = _linear_dx(g2, w).view_as(x)
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and not want_gb and x2.is_contiguous():
+            gw = _dw_unreduced(ctx.fold, w, g2, x2)     # (the first EdgeConv's [P | Q] product: K = 3 input channels)
+        if ctx.needs_input_grad[1] and gw is None:
             gw = _linear_dw(g2, x2, with_bias_grad=want_gb, defer=_may_defer(ctx.defer_targets))
             if isinstance(gw, tuple):      # the small-GEMM path hands the bias gradient (row sums of dY^T) over with the product
                 gw, gb = gw
@@ -421,6 +426,60 @@ def _linear_dw(g2, x2, with_bias_grad=False, defer=False):
     return g2.t() @ x2
 
 
+_fused_pq_tail = True
+
+
+def set_fused_pq_tail(flag):
+    """Tail of the EdgeConv [P | Q] Linears' backward (default on): their weight gradients dW = dY^T X are left to the backward of
+    `edge_weights_many`, which runs all of them in ONE launch (fsg_gemm_small_many_deferred_f32: each product with the tiles and
+    splits it has alone) and sums the split partials, in the reduction's own order, inside the launch that transforms them
+    (fsg_edge_weights_bwd_folded_f32): the same bits from 2 launches instead of 2 per product + 1.  Off: every product runs and
+    reduces at once (the earlier launch sequence; also what every case outside `_dw_unreduced`'s conditions takes).  Returns the
+    old value."""
+    global _fused_pq_tail
+    old, _fused_pq_tail = _fused_pq_tail, bool(flag)
+    return old
+
+
+class _FoldSlot:
+    """One weight handed out by `edge_weights_many`, shared between the products that consume it and the Function that made it:
+    `uses` counts the products of this forward pass that took the weight; `pending` is (dW tensor, dY, X) of the running backward
+    pass while dW is still to be computed.  It holds the TENSORS, so no buffer can be recycled before `_EdgeWeightsMany.backward`
+    has consumed them, and it lives and dies with this forward pass's graph: a later pass has slots of its own, and every
+    product's backward clears the slot before it decides, so nothing stale is ever picked up."""
+    __slots__ = ("uses", "pending")
+
+    def __init__(self):
+        self.uses, self.pending = 0, None
+
+
+def _fold_slot(w):
+    """forward of a product with weight `w`: its slot (counted as one more use), or None for any other weight"""
+    slot = getattr(w, "_fsg_fold", None)
+    if slot is not None:
+        slot.uses += 1
+    return slot
+
+
+def _dw_unreduced(slot, w, g2, x2):
+    """the tensor that WILL hold dW = dY^T X once `_EdgeWeightsMany.backward` has run, or None when the caller has to compute it at
+    once as before: the weight `w` is not one of `edge_weights_many`'s, it feeds a second product (autograd would ADD the two
+    gradients -- bytes that are not there yet), it keeps its gradient or carries hooks (they would read it), create_graph
+    (gradient mode is on inside such a pass: the gradient may be differentiated, i.e. read), the switch is off, or the product is
+    not one fsg_gemm_small_f32 takes.  The tensor returned must reach that backward untouched; it checks."""
+    if slot is None:
+        return None
+    slot.pending = None
+    M, N = g2.shape
+    K = x2.shape[1]
+    if not _fused_pq_tail or slot.uses != 1 or torch.is_grad_enabled() or w.retains_grad or w._backward_hooks or \
+            not _small(N, K, M, g2, x2):
+        return None
+    out = torch.empty(N, K, dtype=torch.float32, device=g2.device)
+    slot.pending = (out, g2, x2)
+    return out
+
+
 def _bias_grad(g2):
     """column sums of dY (M,N).  Narrow outputs (the class logits: N = 4) go to fsg_colsum_narrow_f32 -- ATen's dim-0
     reduction of a (16384, 4) tensor takes 17 us; otherwise `sum(0)` (a one-row product with ones is 3-15x slower:
@@ -444,6 +503,7 @@ class _LinearPMGiven(torch.autograd.Function):
     @_amp_fwd
     def forward(ctx, x, w, value):
         ctx.save_for_backward(x, w)
+        ctx.fold = _fold_slot(w)
         return value.view_as(value)
 
     @staticmethod
@@ -455,7 +515,12 @@ class _LinearPMGiven(torch.autograd.Function):
             g2 = g2.contiguous()
         x2 = x.reshape(-1, x.shape[-1])
         gx = _linear_dx(g2, w).view_as(x) if ctx.needs_input_grad[0] else None
-        gw = _linear_dw(g2, x2 if x2.is_contiguous() else x2.contiguous()) if ctx.needs_input_grad[1] else None
+        gw = None
+        if ctx.needs_input_grad[1]:
+            x2 = x2 if x2.is_contiguous() else x2.contiguous()
+            gw = _dw_unreduced(ctx.fold, w, g2, x2)
+            if gw is None:
+                gw = _linear_dw(g2, x2)
         return gx, gw, None
 
 
@@ -682,9 +747,10 @@ class _EdgeWeightsMany(torch.autograd.Function):
 
     @staticmethod
     @_amp_fwd
-    def forward(ctx, *Ws):
+    def forward(ctx, slots, *Ws):
         Wc = [W if (W.dtype == torch.float32 and W.is_contiguous()) else W.float().contiguous() for W in Ws]
         ctx.shapes = [(W.shape[0], W.shape[1] // 2) for W in Wc]
+        ctx.slots = slots
         return tuple(_EdgeWeightsMany._run(Wc, ctx.shapes, False))
 
     @staticmethod
@@ -694,7 +760,43 @@ class _EdgeWeightsMany(torch.autograd.Function):
         gc = [torch.zeros(2 * Co, C, dtype=torch.float32, device=dev) if g is None else
               (g if (g.dtype == torch.float32 and g.is_contiguous()) else g.float().contiguous())
               for g, (Co, C) in zip(gs, ctx.shapes)]
-        return tuple(_EdgeWeightsMany._run(gc, ctx.shapes, True))
+        pending = [None] * len(gc)
+        for j, slot in enumerate(ctx.slots or ()):
+            pending[j], slot.pending = slot.pending, None
+        if not any(pending):
+            return (None,) + tuple(_EdgeWeightsMany._run(gc, ctx.shapes, True))
+        # weight gradients left to this node (_dw_unreduced): all their products in one launch, then one launch that sums the split
+        # partials before it transforms
+        prods = _lib.GemmSmallJobs()
+        spaces = []
+        for j, pend in enumerate(pending):
+            if pend is None:
+                continue
+            dw, g2, x2 = pend
+            if gs[j] is None or gs[j].data_ptr() != dw.data_ptr():
+                raise RuntimeError("edge_weights_many: the gradient of weight %d is not the product that was registered for it "
+                                   "(a weight of edge_weights_many may feed one product only)" % j)
+            (M, N), K, i = g2.shape, x2.shape[1], len(spaces)
+            ws = _lib.workspace("fsg_gemm_small", N, K, M, device=dev)
+            prods.A[i], prods.sa_i[i], prods.sa_k[i], prods.B[i], prods.sb_k[i], prods.sb_j[i] = g2.data_ptr(), 1, N, x2.data_ptr(), K, 1
+            prods.C[i], prods.ldc[i], prods.I[i], prods.J[i], prods.K[i] = dw.data_ptr(), K, N, K, M
+            prods.workspace[i] = ws.data_ptr() if ws is not None else None
+            spaces.append((j, ws))
+        prods.n = len(spaces)
+        jobs = _lib.EdgeWeightFoldJobs()
+        jobs.n = len(gc)
+        outs = []
+        with torch.cuda.device(dev):
+            _lib.call("fsg_gemm_small_many_deferred_f32", ctypes.byref(prods), _stream())
+            partials = {j: (ws, prods.splits[i]) for i, (j, ws) in enumerate(spaces)}
+            for j, (g, (Co, C)) in enumerate(zip(gc, ctx.shapes)):
+                ws, S = partials.get(j, (None, 0))
+                out = torch.empty(Co, 2 * C, dtype=torch.float32, device=dev)
+                jobs.src[j], jobs.dst[j] = (ws if S > 1 else g).data_ptr(), out.data_ptr()
+                jobs.Co[j], jobs.C[j], jobs.S[j] = Co, C, S
+                outs.append(out)
+            _lib.call("fsg_edge_weights_bwd_folded_f32", ctypes.byref(jobs), _stream())
+        return (None,) + tuple(outs)
 
 
 def edge_weights_many(conv_weights):
@@ -702,7 +804,11 @@ def edge_weights_many(conv_weights):
     Ws = [w.reshape(w.shape[0], w.shape[1]) for w in conv_weights]
     if not 1 <= len(Ws) <= 8:
         raise ValueError("edge_weights_many: 1..8 layers")
-    return list(_EdgeWeightsMany.apply(*Ws))
+    slots = [_FoldSlot() for _ in Ws]
+    outs = list(_EdgeWeightsMany.apply(slots, *Ws))
+    for w, slot in zip(outs, slots):     # marks the weight for the products that take it (_fold_slot)
+        w._fsg_fold = slot
+    return outs
 
 
 # ------------------------------------------------------------------ BatchNorm call counters

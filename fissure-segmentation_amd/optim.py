@@ -3,10 +3,12 @@
 `torch.optim.Adam(model.parameters())` (the reference's optimizer, model_trainer.py:57) walks ~450 small tensors of the
 PointTransformer in 16 chunked multi-tensor launches (470 us per step on MI355X for 7.8 M parameters, launch-bound); the
 same arithmetic over one contiguous buffer is a single streaming kernel.  `FlatAdam` re-points every parameter at a view of
-one flat fp32 buffer (the modules, their `state_dict` and autograd are unaffected), gathers the gradients with one
-`torch.cat` per step and updates the flat buffer with one launch of `fsg_adam_flat_f32` (csrc/adam.hip: float4 streaming,
-one workgroup per 1024 elements, step count on the device -- torch's fused kernel, also one launch here, runs 64 Ki
-elements per workgroup = 28 workgroups for DGCNN-seg).  Same update rule as torch/optim/adam.py; always capturable into
+one flat fp32 buffer (the modules, their `state_dict` and autograd are unaffected) and updates the flat buffer with one launch
+per step: `fsg_adam_flat_segments_f32` reads every gradient where autograd left it and stores it into the flat gradient buffer
+on its way; when a gradient is missing, not contiguous fp32, or a parameter's size is no multiple of 4, and for data-parallel
+callers (`gather_grads()`, all-reduce, `step_flat()`), the gradients are gathered with one `torch.cat` and `fsg_adam_flat_f32`
+updates from the flat gradient (csrc/adam.hip: float4 streaming, step count on the device -- torch's fused kernel, also one launch
+here, runs 64 Ki elements per workgroup = 28 workgroups for DGCNN-seg).  Same update rule as torch/optim/adam.py; always capturable into
 a hipGraph.  On a CPU model (host-logic tests) the flat buffer is handed to torch.optim.Adam instead.
 
 Drop-in contract with `torch.optim.Adam(model.parameters())` as `model_trainer.py:57,189-195` uses it:
@@ -82,6 +84,10 @@ class FlatAdam:
         if self.inner is not None:
             self.inner.step()
             return
+        self._launch("fsg_adam_flat_f32", None)
+
+    def _launch(self, entry, segments):
+        """fsg_adam_flat_f32 (segments None: the gradient is the flat buffer) or fsg_adam_flat_segments_f32"""
         from . import _lib
         g = self._groups[0]
         lr = g["lr"]
@@ -91,11 +97,41 @@ class FlatAdam:
                 raise ValueError("a tensor learning rate must be one fp32 element on the parameters' device")
             lr_dev, lr = ctypes.c_void_p(lr.data_ptr()), 0.0
         P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.call("fsg_adam_flat_f32", P(self.flat.data), P(self.flat.grad), P(self.exp_avg), P(self.exp_avg_sq),
-                  P(self._state), self.flat.numel(), float(lr), lr_dev, float(g["betas"][0]), float(g["betas"][1]),
-                  float(g["eps"]), float(g["weight_decay"]), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        table = () if segments is None else (segments,)
+        with torch.cuda.device(self.flat.device):
+            _lib.call(entry, P(self.flat.data), P(self.flat.grad), P(self.exp_avg), P(self.exp_avg_sq),
+                      P(self._state), self.flat.numel(), *table, float(lr), lr_dev, float(g["betas"][0]), float(g["betas"][1]),
+                      float(g["eps"]), float(g["weight_decay"]), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+    def _grad_segments(self):
+        """the table of fsg_adam_flat_segments_f32 when the update can read every gradient in place, else None: every parameter
+        has a contiguous fp32 gradient on the buffer's device, 16-byte aligned, and every span starts and ends on a multiple of
+        4 floats (a parameter of 3 elements shifts all that follow), within the table's size"""
+        from . import _lib
+        if self.inner is not None or len(self.params) > _lib.ADAM_MAX_SEGMENTS:
+            return None
+        seg = _lib.AdamSegments()
+        for i, (p, (a, b)) in enumerate(zip(self.params, self._spans)):
+            g = p.grad
+            if g is None or g.dtype != torch.float32 or g.device != self.flat.device or not g.is_contiguous() or \
+                    g.numel() != b - a or (a | b) & 3 or g.data_ptr() & 15:
+                return None
+            seg.grad[i], seg.offset[i], seg.count[i] = g.data_ptr(), a, b - a
+        seg.n = len(self.params)
+        return seg
 
     def step(self):
+        """one process, one GPU: the update reads the gradients where autograd left them and stores them into the flat gradient
+        buffer on its way (one launch, no concatenation).  Data-parallel callers all-reduce the flat buffer between
+        `gather_grads()` and `step_flat()` instead."""
+        seg = None
+        if self.inner is None:
+            from . import functional as F_hip
+            F_hip.flush_deferred_reduces()     # (as gather_grads() does: the gradients must be complete)
+            seg = self._grad_segments()
+        if seg is not None:
+            self._launch("fsg_adam_flat_segments_f32", ctypes.byref(seg))
+            return
         missing = [i for i, p in enumerate(self.params) if p.grad is None]
         self.gather_grads()
         if not missing or self.inner is not None:

@@ -152,6 +152,19 @@ typedef struct fsg_edge_weight_jobs {
     int n;
 } fsg_edge_weight_jobs;
 int fsg_edge_weights_many_f32(const fsg_edge_weight_jobs *jobs, int backward, fsg_stream_t stream);
+/* The backward transform of fsg_edge_weights_many_f32 fed with UNREDUCED weight gradients: a job with S > 1 reads src as the
+ * [S][2Co * C] split partials that fsg_gemm_small_deferred_f32 left in its workspace for the product grad_Wt (2Co, C), sums
+ * them in the order fsg_gemm_small_f32's own reduction uses for that S (bit-identical to reducing first), then transforms;
+ * a job with S <= 1 reads src as a finished grad_Wt.  One launch, no atomics. */
+typedef struct fsg_edge_weight_fold_jobs {
+    const float *src[FSG_EDGE_WEIGHT_MAX_JOBS];
+    float *dst[FSG_EDGE_WEIGHT_MAX_JOBS];
+    int Co[FSG_EDGE_WEIGHT_MAX_JOBS];
+    int C[FSG_EDGE_WEIGHT_MAX_JOBS];
+    int S[FSG_EDGE_WEIGHT_MAX_JOBS];
+    int n;
+} fsg_edge_weight_fold_jobs;
+int fsg_edge_weights_bwd_folded_f32(const fsg_edge_weight_fold_jobs *jobs, fsg_stream_t stream);
 
 /*
  * Last pass of the fused EdgeConv forward on its own: out (B,Co,N) [+ out_pm (B,N,Co)] = LeakyReLU(BatchNorm(ysel)) from the
@@ -496,6 +509,23 @@ int fsg_gemm_small_deferred_f32(const float *A, int64_t sa_i, int64_t sa_k, cons
                                 int64_t ldc, int I, int J, int K, float *rowsum, void *workspace, int *splits,
                                 fsg_stream_t stream);
 int fsg_gemm_small_reduce_many_f32(const fsg_gemm_reduce_jobs *jobs, fsg_stream_t stream);
+/* fsg_gemm_small_deferred_f32 for up to FSG_GEMM_SMALL_MAX_JOBS products in ONE launch (no row sums): every product keeps the
+ * tiles, splits and arithmetic it has alone, so C / the partials in workspace[j] carry the same bits.  splits[j] is filled by
+ * the callee as fsg_gemm_small_deferred_f32 fills *splits; `jobs` is read and written on the host during the call. */
+#define FSG_GEMM_SMALL_MAX_JOBS 8
+typedef struct fsg_gemm_small_jobs {
+    const float *A[FSG_GEMM_SMALL_MAX_JOBS];
+    int64_t sa_i[FSG_GEMM_SMALL_MAX_JOBS], sa_k[FSG_GEMM_SMALL_MAX_JOBS];
+    const float *B[FSG_GEMM_SMALL_MAX_JOBS];
+    int64_t sb_k[FSG_GEMM_SMALL_MAX_JOBS], sb_j[FSG_GEMM_SMALL_MAX_JOBS];
+    float *C[FSG_GEMM_SMALL_MAX_JOBS];
+    int64_t ldc[FSG_GEMM_SMALL_MAX_JOBS];
+    int32_t I[FSG_GEMM_SMALL_MAX_JOBS], J[FSG_GEMM_SMALL_MAX_JOBS], K[FSG_GEMM_SMALL_MAX_JOBS];
+    void *workspace[FSG_GEMM_SMALL_MAX_JOBS];
+    int32_t splits[FSG_GEMM_SMALL_MAX_JOBS];
+    int32_t n;
+} fsg_gemm_small_jobs;
+int fsg_gemm_small_many_deferred_f32(fsg_gemm_small_jobs *jobs, fsg_stream_t stream);
 /* bf16 operand mode of fsg_gemm_small_rowsum_f32 (splits == NULL) / fsg_gemm_small_deferred_f32 (splits != NULL, bias NULL): both
  * operands are rounded to bf16 (nearest even) on their way into LDS, products on v_mfma_f32_32x32x16_bf16, fp32 accumulation,
  * fp32 output.  The nn.Linear products of the PointTransformer in bf16 mode (reference: autocast, model_trainer.py:75-76,157). */
@@ -564,6 +594,20 @@ int fsg_pt_attn_bwd_f32(const float *p, const int32_t *idx, const float *q, cons
 int fsg_adam_flat_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, void *state, int64_t n,
                       float lr, const float *lr_dev, float beta1, float beta2, float eps, float weight_decay,
                       fsg_stream_t stream);
+/* The same update with the gradient read where autograd left it, one segment per parameter: `count` floats at grad[s] belong
+ * at flat offset[s].  The segments tile [0, n) in order; every grad[s] is 16-byte aligned and every count a multiple of 4.
+ * The gradients read are also stored into `flat_grad` (n), which afterwards holds their concatenation -- what the caller of
+ * fsg_adam_flat_f32 had to build with a copy of its own beforehand.  Same arithmetic per element, same `state`.
+ * `segments` is read on the host during the call. */
+#define FSG_ADAM_MAX_SEGMENTS 128
+typedef struct fsg_adam_segments {
+    const float *grad[FSG_ADAM_MAX_SEGMENTS];
+    int64_t offset[FSG_ADAM_MAX_SEGMENTS], count[FSG_ADAM_MAX_SEGMENTS];
+    int32_t n;
+} fsg_adam_segments;
+int fsg_adam_flat_segments_f32(float *param, float *flat_grad, float *exp_avg, float *exp_avg_sq, void *state, int64_t n,
+                               const fsg_adam_segments *segments, float lr, const float *lr_dev, float beta1, float beta2,
+                               float eps, float weight_decay, fsg_stream_t stream);
 
 /*
  * Accumulation step of the test-time ensembling `predict_full_pointcloud` (models/point_seg_net.py:21-48; the loop body
