@@ -1239,6 +1239,40 @@ int fsg_mesh_compact_f32(const float *verts, const float *normals, const int32_t
                          int B, const uint8_t *vert_flag, const int64_t *vert_new, const uint8_t *face_flag, const int64_t *face_new,
                          float *verts_out, float *normals_out, int64_t *faces_out, fsg_stream_t stream);
 
+/* Dense Adam image registration (csrc/dense_reg.hip).  Replace the body of the optimisation loop of
+ * shape_model/adam_registration.py:106-124: three avg_pool3d and their backward, a grid_sample of every feature channel with
+ * its sampled (C, S0, S1, S2) tensor, three slice-difference regularisers.  All pointers DEVICE.  An iteration is four launches
+ * of entry points and no host read: smooth3 of the parameter, objective, smooth3 of grad_disp, fsg_adam_flat_f32.
+ *
+ * fsg_reg_smooth3_f32: in (B, C, S0, S1, S2) fp32 -> out, the same shape = avg_pool3d(kernel 3, stride 1, padding 1,
+ *   count_include_pad=True) applied three times (:110-111, :129-130).  Per axis that is T^3, T the tridiagonal 1/3 operator with
+ *   zero neighbours outside the domain: the values outside are zero again after every pool, so within two cells of a border and
+ *   on an axis shorter than 7 it is NOT the truncated [1 3 6 7 6 3 1] / 27.  The axes commute and T is symmetric: the operator
+ *   is its own adjoint, the backward pass calls this entry with the gradient.  One launch (an LDS tile with a halo of 3).
+ *   Every axis >= 3 (avg_pool3d refuses smaller ones), in != out, B C <= 65535.
+ * fsg_reg_objective_f16: disp (B, 3, S0, S1, S2) fp32 = the smoothed field, channel c displaces along axis S_c in the
+ *   reference's units; feat_fix, feat_mov (B, S0, S1, S2, Cp) fp16, channels last, 16-byte aligned, Cp a multiple of 8,
+ *   C <= Cp <= 4096, channels C .. Cp - 1 are ignored.  Per node (:115-122): the identity coordinate of
+ *   affine_grid(align_corners=False) plus disp[c] / ((S_c - 1) / 2) with the channel flip (channel 0 -> last grid coordinate
+ *   <-> axis S0), grid_sample's align_corners=False unnormalisation -- together t_c = i_c + disp[c] S_c / (S_c - 1) --,
+ *   trilinear weights, zero padding: a corner outside the volume gives nothing to the value and nothing to the gradient.
+ *   cost = cost_scale / (C nodes) sum over nodes and channels of (sample - fix)^2, nodes = S0 S1 S2, per item.
+ *   reg (:112-114) = lambda * sum over the axes a of the mean of the squared forward differences of disp along a, each mean
+ *   over its own 3 (S_a - 1) S_b S_c elements; lambda == 0 skips it (reg = 0 whatever the field holds).
+ *   -> grad_disp (B, 3, S0, S1, S2) = d (cost + reg) / d disp (one-sided differences at the borders), loss (B, 2) fp32 =
+ *   { cost, reg } of every item.  Any disp is legal: a coordinate far outside, infinite or NaN reads 0, gets a zero data-term
+ *   gradient and never indexes outside the volumes (fsg_grid_sample_f32's contract); the regulariser of a non-finite field is
+ *   not finite.  Sums: fp32 per node, then fp64 per workgroup and per item in a fixed order (a finishing launch); no
+ *   floating-point atomics: the same input gives the same bits, an item gives the same bits alone and inside a batch.
+ *   workspace: the query below, 8-byte aligned.
+ * B <= 65535, S0 S1 S2 < 2^31 (offsets into the volumes are 64-bit).  Bad shapes, NULL pointers, misaligned volumes or a short
+ *   workspace are FSG_ERR_ARG before any launch. */
+int fsg_reg_smooth3_f32(const float *in, int B, int C, int S0, int S1, int S2, float *out, fsg_stream_t stream);
+size_t fsg_reg_objective_workspace_bytes(int B, int S0, int S1, int S2);
+int fsg_reg_objective_f16(const float *disp, const void *feat_fix, const void *feat_mov, int B, int C, int Cp, int S0, int S1, int S2,
+                          float lambda, float cost_scale, float *grad_disp, float *loss, void *workspace, size_t workspace_bytes,
+                          fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1032,3 +1032,67 @@ if "surffit" in which:
     out_path = os.environ.get("FSG_SURFFIT_BENCH_OUT", os.path.join(ROOT, "profiles", "surface_fit_bench.jsonl"))
     with open(out_path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+if "reg" in which:
+    # Dense Adam registration (csrc/dense_reg.hip, shape_model/adam_registration.py): one fused iteration (4 entry points) and a
+    # 50-iteration run captured into one graph, beside the torch composition of the same loop (tests/reg_oracle.adam_loop, fp32,
+    # on the device) in the same process, alternating; peak extra memory of both.  Writes profiles/reg_bench.jsonl.
+    import json
+    import reg_oracle as ro
+    from fissure_segmentation_amd.shape_model import adam_registration as ar
+    lines = []
+
+    def emit_line(rec):
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 1)
+
+    C, ITERS = 22, 50
+    for (S, B) in [((64, 64, 64), 1), ((64, 64, 64), 4), ((96, 96, 104), 1), ((96, 96, 104), 4)]:
+        g = torch.Generator(device=dev).manual_seed(7)
+        ff = ro.smooth3(torch.rand(B, C, *S, device=dev, generator=g))
+        ff = ((ff - ff.amin()) / (ff.amax() - ff.amin())).half().float()
+        fm = torch.roll(ff, (1, -1, 1), (2, 3, 4))
+        pf, pm = F.reg_pack_features(ff), F.reg_pack_features(fm)
+        run = ar.InstanceOptimisation(pf, pm, C, iters=ITERS)
+        run.iterate()                                              # loads the kernels; the parameter has left its start
+        fused_it = timeit(lambda: run.iterate(0, 1), iters=40, warm=5)
+        graph_run = ar.InstanceOptimisation(pf, pm, C, iters=ITERS)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            graph_run.iterate()
+        fused_50 = timeit(graph.replay, iters=10, warm=2)
+        fused_50_eager = timeit(run.iterate, iters=10, warm=2)
+        comp_it = timeit(lambda: ro.adam_loop(ff, fm, 1), iters=10, warm=2)      # (includes building Adam's state: one iteration)
+        comp_50 = timeit(lambda: ro.adam_loop(ff, fm, ITERS), iters=4, warm=1)
+        fused_50b = timeit(graph.replay, iters=10, warm=2)                       # again, after the composition: the spread
+        fsg._lib.start_timing()
+        for _ in range(10):
+            run.iterate(0, 1)
+        entry = {k: round(1e3 * sorted(v)[len(v) // 2], 1) for k, v in fsg._lib.stop_timing().items()}
+        mem_fused = peak_extra(lambda: ar.adam_instance_optimisation(pf, pm, iters=ITERS, channels=C))
+        mem_comp = peak_extra(lambda: ro.adam_loop(ff, fm, ITERS))
+        fresh = ar.adam_instance_optimisation(pf, pm, iters=ITERS, channels=C)[1]      # (the timed runs went on from where they were)
+        fused_first, fused_final = float(fresh[0].sum()), float(fresh[-1].sum())
+        comp_final = float(ro.adam_loop(ff, fm, ITERS)[1][-1].sum())
+        emit_line(dict(kernel="reg adam_instance_optimisation", grid=list(S), C=C, B=B, iters=ITERS,
+                       fused_iteration_us=round(fused_it[0], 1), fused_iteration_min_us=round(fused_it[1], 1), entry_us=entry,
+                       fused_50_graph_us=round(fused_50[0], 1), fused_50_graph_again_us=round(fused_50b[0], 1),
+                       fused_50_eager_us=round(fused_50_eager[0], 1),
+                       composition_1_iteration_us=round(comp_it[0], 1), composition_50_us=round(comp_50[0], 1),
+                       speedup_50=round(comp_50[0] / fused_50[0], 2),
+                       fused_peak_extra_MiB=mem_fused, composition_peak_extra_MiB=mem_comp,
+                       final_objective_fused=fused_final, final_objective_composition=comp_final,
+                       initial_objective=fused_first))
+        del run, graph_run, graph
+    out_path = os.environ.get("FSG_REG_BENCH_OUT", os.path.join(ROOT, "profiles", "reg_bench.jsonl"))
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
