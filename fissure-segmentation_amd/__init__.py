@@ -40,6 +40,7 @@ def install_reference_aliases():
         "data_processing.surface_fitting_optimization": ".data_processing.surface_fitting_optimization",
         "models.divroc": ".models.divroc", "models.dpsr_utils": ".models.dpsr_utils", "models.dpsr_net": ".models.dpsr_net",
         "models.seg_logits_to_mesh": ".models.seg_logits_to_mesh", "losses.dpsr_loss": ".losses.dpsr_loss",
+        "models.seg_cnn": ".models.seg_cnn", "models.mobilenet": ".models.mobilenet", "models.aspp_3d": ".models.aspp_3d",
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)

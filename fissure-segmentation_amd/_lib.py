@@ -180,6 +180,9 @@ SIGNATURES = {
     "fsg_reg_smooth3_f32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
     "fsg_reg_objective_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
     "fsg_reg_objective_f16": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_mbconv3d_fwd_f32": ([_P] * 10 + [_I] * 10 + [_P, _P], _I),
+    "fsg_patch_accumulate_f32": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
+    "fsg_patch_finalize_f32": ([_P, _P, _I, _I, _I, _I, _I, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

@@ -2,7 +2,7 @@
 data_processing/keypoint_extraction.py and point_features.py:163-203), tensors in, tensors out: no SimpleITK, no files."""
 import torch
 
-from ..utils.general_utils import ALIGN_CORNERS, kpts_to_grid
+from ..utils.general_utils import ALIGN_CORNERS, kpts_to_grid, sample_patches_at_kpts
 from .. import functional as F_hip
 from . import foerstner
 from .point_features import image_patch_features, mind_at_keypoints
@@ -89,6 +89,45 @@ def enhancement_point_cloud(img, mask, fissure_mu, fissure_sigma, spacing=(1, 1,
     else:
         feat = mind_at_keypoints(img, kp, dilation=1, sigma=0.8, ssc=feature_mode == 'mind_ssc')
     return torch.cat([points, feat], dim=0).contiguous()
+
+
+def cnn_keypoints_from_softmax(softmax_pred, mask, spacing=(1, 1, 1), feat_patch=5):
+    """keypoint_extraction.py:101-118: softmax_pred (1, K, D, H, W), mask (D, H, W) bool -> (kp (N, 3) int64, features
+    (feat_patch^3, N)): the voxels inside the mask whose largest score is not the background's, as (z, y, x) indices times the
+    spacing (truncated, as the reference stores them), and around each the feat_patch^3 patch of the summed foreground scores"""
+    fissure_points = (softmax_pred.argmax(1)[0] != 0) & mask
+    sp = torch.tensor(tuple(spacing), dtype=torch.float32, device=softmax_pred.device)
+    kp = torch.nonzero(fissure_points) * sp
+    if kp.shape[0] == 0:
+        return kp.long(), torch.zeros(feat_patch ** 3, 0, dtype=softmax_pred.dtype, device=softmax_pred.device)
+    extent = torch.tensor(tuple(fissure_points.shape), device=kp.device) * sp
+    kp_grid = kpts_to_grid(kp.flip(-1), extent, align_corners=ALIGN_CORNERS)
+    foreground = softmax_pred[:, 1:].sum(1, keepdim=True)
+    features = sample_patches_at_kpts(foreground, kp_grid, feat_patch).reshape(kp.shape[0], -1).transpose(0, 1)
+    return kp.long(), features
+
+
+def cnn_point_cloud(models, img, mask, spacing=(1, 1, 1), feat_patch=5):
+    """The reference's third keypoint mode, kp_mode='cnn' (`get_cnn_keypoints`, keypoint_extraction.py:87-131), tensors in,
+    tensors out: `models` one `MobileNetASPP` in eval mode or a list of them (the fold models), img (1, 1, D, H, W) on the GPU
+    at the networks' resolution, mask (1, 1, D, H, W) | (D, H, W) the lung mask, spacing (z, y, x).  Each model's
+    `predict_all_patches` gives softmax scores; -> `cnn_keypoints_from_softmax` of them: (kp, features) for one model, two
+    lists for several.  File reading, the cross-validation split lookup and the argument files are the caller's."""
+    single = isinstance(models, torch.nn.Module)
+    models = [models] if single else list(models)
+    if not models:
+        raise ValueError('cnn_point_cloud: no model given')
+    if img.dim() != 5 or img.shape[0] != 1:
+        raise ValueError(f'expected one volume (1, 1, D, H, W), got {tuple(img.shape)}')
+    mask = mask.reshape(img.shape[2:]).to(device=img.device, dtype=torch.bool)
+    kps, feats = [], []
+    for model in models:
+        with torch.no_grad():
+            softmax_pred = model.predict_all_patches(img)
+        kp, feat = cnn_keypoints_from_softmax(softmax_pred, mask, spacing, feat_patch)
+        kps.append(kp)
+        feats.append(feat)
+    return (kps, feats) if len(models) > 1 else (kps[0], feats[0])
 
 
 def keypoints_to_grid(kp, shape, spacing=(1, 1, 1)):

@@ -1273,6 +1273,35 @@ int fsg_reg_objective_f16(const float *disp, const void *feat_fix, const void *f
                           float lambda, float cost_scale, float *grad_disp, float *loss, void *workspace, size_t workspace_bytes,
                           fsg_stream_t stream);
 
+/* Voxel CNN inference (csrc/seg_cnn.hip): the eval-mode backbone block of models/mobilenet.py and the tail of the patch loop of
+ * models/seg_cnn.py:48-62.  All pointers DEVICE unless said otherwise; fp32.
+ *
+ * fsg_mbconv3d_fwd_f32: one inverted-residual block in one launch; the expanded tensor is never written to memory.
+ *   x (B, D, H, W, Cin) -- the logical (B, Cin, D, H, W) tensor in channels-last memory -- -> y (B, Do, Ho, Wo, Cout), the same.
+ *   expand: w1 (Cmid, Cin), the 1x1x1 product; with first != 0 the dense 3x3x3, stride-2, padding-1 convolution of ONE channel,
+ *     w1 (Cmid, 27) with the taps in (kd, kh, kw) order, whose output has (n - 1) / 2 + 1 cells per axis.
+ *   then v s1 + b1 (the folded BatchNorm, per channel), ReLU6; depthwise 3x3x3 wd (Cmid, 27), stride 1 | 2, padding 1 with zeros
+ *     around the ACTIVATED tensor, (n - 1) / stride + 1 cells per axis; v s2 + b2, ReLU6; project w3 (Cout, Cmid); v s3 + b3, no
+ *     activation; residual != 0 adds x (needs stride 1, Cin == Cout, first == 0).
+ *   Limits: 1 <= Cin, Cout <= 64, Cmid a multiple of 16 in 16..384, B D H W >= 1, D H W < 2^31, x != y.  Anything else, or a NULL
+ *   pointer, is FSG_ERR_ARG before the launch.  Products on the exact fp32 matrix instruction, sums in a fixed order, no atomics:
+ *   the same bits on every run, and an item gives the same bits alone and inside a batch.
+ *
+ * fsg_patch_accumulate_f32: logits (P, K, pd/2, ph/2, pw/2), the half-resolution output of the head for P patches of
+ *   pd x ph x pw voxels (even); starts: HOST (P, 4) int32 = { item, z, y, x }, the patch's corner in the volume.  Per patch:
+ *   x2 trilinear up-sampling (align_corners = False), softmax over K, times wmap (pd, ph, pw), or 1 where wmap is NULL, cropped
+ *   to the part of the patch inside the volume -- a patch that overhangs the volume was replicate-padded by
+ *   ceil(r / 2) cells in front and floor(r / 2) behind, r the overhang -- and added into sum (B, K, D, H, W); the weight into
+ *   wsum (B, 1, D, H, W).  One launch per patch in the order of `starts` on `stream`: overlapping patches add in that order.
+ * fsg_patch_finalize_f32: out (B, K, D, H, W) = softmax over K of sum / wsum (the reference applies its activation to every
+ *   patch AND to the normalised sum); out may be sum. */
+int fsg_mbconv3d_fwd_f32(const float *x, const float *w1, const float *s1, const float *b1, const float *wd, const float *s2,
+                         const float *b2, const float *w3, const float *s3, const float *b3, int B, int Cin, int Cmid, int Cout,
+                         int D, int H, int W, int stride, int first, int residual, float *y, fsg_stream_t stream);
+int fsg_patch_accumulate_f32(const float *logits, int P, int K, int pd, int ph, int pw, const int *starts, const float *wmap,
+                             float *sum, float *wsum, int B, int D, int H, int W, fsg_stream_t stream);
+int fsg_patch_finalize_f32(const float *sum, const float *wsum, int B, int K, int D, int H, int W, float *out, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
