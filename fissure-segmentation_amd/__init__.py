@@ -41,6 +41,7 @@ def install_reference_aliases():
         "models.divroc": ".models.divroc", "models.dpsr_utils": ".models.dpsr_utils", "models.dpsr_net": ".models.dpsr_net",
         "models.seg_logits_to_mesh": ".models.seg_logits_to_mesh", "losses.dpsr_loss": ".losses.dpsr_loss",
         "models.seg_cnn": ".models.seg_cnn", "models.mobilenet": ".models.mobilenet", "models.aspp_3d": ".models.aspp_3d",
+        "data_processing.process_lung_mask": ".data_processing.process_lung_mask",
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)

@@ -154,6 +154,10 @@ SIGNATURES = {
     "fsg_cc_label_bits": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_component_stats_i32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
     "fsg_relabel_lut_i32": ([_P, _I, _L, _P, _I, _P, _I, _P], _I),
+    "fsg_edt_workspace_bytes": ([_I, _I, _I, _I, _I], ctypes.c_size_t),
+    "fsg_edt_sq_i32": ([_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_edt_sq_f32": ([_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_edt_nearest_label": ([_P, _I, _I, _L, _P, _P, _P, _P], _I),
     "fsg_mesh_reg_workspace_bytes": ([_I, _I], ctypes.c_size_t),
     "fsg_mesh_reg_f32": ([_P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_mesh_sample_workspace_bytes": ([_I, _I], ctypes.c_size_t),

@@ -3298,6 +3298,161 @@ def relabel_by_size(labels, n):
     return out[0] if squeeze else out
 
 
+# ------------------------------------------------------------------ Euclidean distance transform (csrc/edt.hip)
+EDT_MAX_DIM = 16384          # csrc/edt.hip: MAX_DIM (3 * 16383^2 fits an int32)
+EDT_MAX_LABELS = 64          # csrc/edt.hip: MAX_PLANES
+EDT_INT_INF = 2 ** 31 - 1    # the int32 mode's +inf
+
+
+def _edt_shape(shape, what):
+    D, H, W = (int(v) for v in shape[-3:])
+    if max(D, H, W) > EDT_MAX_DIM or D * H * W >= 2 ** 31:
+        raise ValueError(f"{what}: volume {(D, H, W)}: a dimension above {EDT_MAX_DIM} or 2^31 voxels or more")
+
+
+def _edt_sampling(sampling, what):
+    """None -> None (unit spacing: the int32 mode); a number or three (s0, s1, s2) for (D, H, W) -> three floats rounded to
+    fp32, what the kernel computes with"""
+    if sampling is None:
+        return None
+    s = (sampling,) * 3 if isinstance(sampling, (int, float)) and not isinstance(sampling, bool) else tuple(sampling)
+    if len(s) != 3:
+        raise ValueError(f"{what}: sampling must be None, a number or three numbers for (D, H, W), got {sampling!r}")
+    s = tuple(float(torch.tensor(float(v), dtype=torch.float32)) for v in s)
+    if any(not (0.0 < v <= 1e6) for v in s):
+        raise ValueError(f"{what}: sampling {sampling!r} must be positive and at most 1e6")
+    return s
+
+
+def _edt_bits(bits, W, sampling, want_idx):
+    """bit plane (B, D, H, WW) -> (d2 (B, D, H, W) int32 for unit spacing / fp32, site index (B, D, H, W) int32 or None).  Three
+    launches on the current stream, no host read."""
+    B, D, H, _ = bits.shape
+    dev = bits.device
+    d2 = torch.empty(B, D, H, W, dtype=torch.int32 if sampling is None else torch.float32, device=dev)
+    idx = torch.empty(B, D, H, W, dtype=torch.int32, device=dev) if want_idx else None
+    ws = _lib.workspace("fsg_edt", B, D, H, W, int(want_idx), device=dev)
+    with torch.cuda.device(dev):
+        if sampling is None:
+            _lib.call("fsg_edt_sq_i32", _p(bits), B, D, H, W, _p(d2), _p(idx), _p(ws), ws.numel(), _stream())
+        else:
+            _lib.call("fsg_edt_sq_f32", _p(bits), B, D, H, W, sampling[0], sampling[1], sampling[2], _p(d2), _p(idx), _p(ws),
+                      ws.numel(), _stream())
+    return d2, idx
+
+
+def distance_transform_edt(vol, sampling=None, return_distances=True, return_indices=False, squared=False):
+    """scipy.ndimage.distance_transform_edt on the device (process_lung_mask.py:85): vol (D, H, W) or (B, D, H, W), bool or
+    integer, nonzero = set; every voxel gets the Euclidean distance to the nearest zero voxel (a SITE) of its item, under
+    `sampling` = None (unit), a number, or (s0, s1, s2) for (D, H, W).  Exact and separable (csrc/edt.hip).
+
+    Distances are float32 square roots of the squared values; `squared=True` returns the squared values themselves: int32,
+    exact, for sampling=None, else float32 (each term fl(fl(s * delta)^2), sums rounded once, no fused multiply-add; the
+    spacings are rounded to fp32 first).  Indices are (3, D, H, W) int32 -- (B, 3, D, H, W) for a batch -- the (z, y, x) of the
+    site that won.  Returns the distances, the indices, or (distances, indices), as scipy does.
+
+    Where this is NOT scipy: an item without a zero voxel gives +inf distances (2^31 - 1 as squared int32) and -1 indices
+    (scipy returns garbage there); among equidistant sites the winner is, per pass (W, then H, then D), the one with the
+    smaller offset and then the lower index, which is not scipy's choice."""
+    if not (return_distances or return_indices):
+        raise ValueError("distance_transform_edt: at least one of return_distances / return_indices must be set")
+    if vol.dim() in (3, 4):
+        _edt_shape(vol.shape, "distance_transform_edt")
+    s = _edt_sampling(sampling, "distance_transform_edt")
+    v4, squeeze = _binary_volume(vol, "distance_transform_edt")
+    B, D, H, W = v4.shape
+    with torch.no_grad():
+        d2, idx = _edt_bits(_pack_bits(v4), W, s, return_indices)
+        out = []
+        if return_distances:
+            if squared:
+                dist = d2
+            else:
+                dist = d2.to(torch.float32).sqrt_()
+                if s is None:
+                    dist.masked_fill_(d2 == EDT_INT_INF, float("inf"))
+            out.append(dist[0] if squeeze else dist)
+        if return_indices:
+            x = idx % W
+            y = torch.div(idx, W, rounding_mode="floor") % H
+            z = torch.div(idx, H * W, rounding_mode="floor")
+            zyx = torch.stack((z, y, x), 1)
+            zyx.masked_fill_((idx < 0)[:, None], -1)
+            out.append(zyx[0] if squeeze else zyx)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def nearest_label(labels, candidates, sampling=None, keep=None):
+    """For every voxel of `labels` (D, H, W), integer, the member of `candidates` whose nearest voxel is closest (Euclidean,
+    under `sampling` as in `distance_transform_edt`) -> int32 (D, H, W).  On an exact tie the lowest label wins, as np.argmin
+    over the distance maps in label order does (process_lung_mask.py:83-87; the feature transform has another tie rule and
+    cannot stand in).  One batched distance transform over len(candidates) bit planes and one compare launch; with unit
+    spacing the compare is exact in integers.  A candidate without voxels is infinitely far; if none has any, the lowest is
+    returned.  `keep` (D, H, W), bool or uint8: voxels where it is 0 get 0 (process_lung_mask.py:88).  No host read."""
+    cands = sorted({int(c) for c in candidates})
+    if not cands or len(cands) > EDT_MAX_LABELS or len(cands) != len(list(candidates)):
+        raise ValueError(f"nearest_label: candidates must be 1..{EDT_MAX_LABELS} distinct integers, got {candidates!r}")
+    if labels.dim() != 3 or labels.is_floating_point() or labels.is_complex() or labels.numel() == 0:
+        raise ValueError(f"nearest_label: expected an integer label map (D, H, W), got {tuple(labels.shape)} {labels.dtype}")
+    _edt_shape(labels.shape, "nearest_label")
+    s = _edt_sampling(sampling, "nearest_label")
+    _need_gpu(labels, keep)
+    if keep is not None and (keep.shape != labels.shape or keep.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError(f"nearest_label: keep must be bool or uint8 of shape {tuple(labels.shape)}")
+    D, H, W = labels.shape
+    dev = labels.device
+    with torch.no_grad():
+        cand_t = torch.tensor(cands, dtype=torch.int32, device=dev)
+        planes = labels[None] != cand_t[:, None, None, None]       # (K, D, H, W) bool; the comparison promotes, never wraps
+        d2, _ = _edt_bits(_pack_bits(planes), W, s, False)          # a candidate's voxels are the sites of its plane
+        out = torch.empty(D, H, W, dtype=torch.int32, device=dev)
+        k8 = None if keep is None else keep.contiguous().view(torch.uint8)
+        with torch.cuda.device(dev):
+            _lib.call("fsg_edt_nearest_label", _p(d2), int(s is not None), len(cands), D * H * W, _p(cand_t), _p(k8), _p(out),
+                      _stream())
+    return out
+
+
+def _quantile_linear(d, q):
+    """torch.quantile(d, q) (linear interpolation) of a 1-D tensor of any length: torch.quantile itself up to its limit of
+    metrics.QUANTILE_MAX_ELEMENTS, above it the same formula on a sort"""
+    from . import metrics
+    n = d.numel()
+    if n <= metrics.QUANTILE_MAX_ELEMENTS:
+        return torch.quantile(d, q)
+    srt = torch.sort(d).values
+    pos = q * (n - 1)
+    lo = int(pos)
+    hi = min(lo + 1, n - 1)
+    return srt[lo] + (srt[hi] - srt[lo]) * (pos - lo)
+
+
+def labelmap_distances(a, b, spacing=(1., 1., 1.)):
+    """The symmetric surface-distance statistics between the voxel clouds of two label maps -- what the reference's
+    `label_label_assd` (metrics.py:79-93) measures with open3d point-cloud distances -> (mean, std, hd, hd95), fp64 tensors on
+    the device, each the average of the two directions (`metrics._symmetric_point_distances`).  a, b (D, H, W), bool or integer,
+    nonzero = set; `spacing` in (x, y, z), as `mask_to_points` takes it.  The distance from a set voxel of `a` to the nearest
+    set voxel of `b` is the distance transform of b == 0 read at that voxel (squared distances in fp32 as in
+    `distance_transform_edt`, square roots and statistics in fp64).  An empty mask gives four NaNs (`metrics._nan4`).  Parity
+    with open3d is unpinned; scipy's transform is the checker."""
+    from . import metrics
+    if a.shape != b.shape or a.dim() != 3:
+        raise ValueError(f"labelmap_distances: expected two volumes (D, H, W) of one shape, got {tuple(a.shape)}, {tuple(b.shape)}")
+    _need_gpu(a, b)
+    sx, sy, sz = (float(v) for v in spacing)
+    with torch.no_grad():
+        am, bm = a != 0, b != 0
+        if not bool(am.any()) or not bool(bm.any()):
+            return metrics._nan4()
+        d2 = distance_transform_edt(torch.stack((~bm, ~am)), sampling=(sz, sy, sx), squared=True)
+        d_ab, d_ba = d2[0][am].double().sqrt_(), d2[1][bm].double().sqrt_()
+        if max(d_ab.numel(), d_ba.numel()) <= metrics.QUANTILE_MAX_ELEMENTS:
+            return metrics._symmetric_point_distances(d_ab, d_ba)
+        both = (d_ab, d_ba)
+        return (sum(d.mean() for d in both) / 2, sum(d.std() for d in both) / 2, sum(d.max() for d in both) / 2,
+                sum(_quantile_linear(d, 0.95) for d in both) / 2)
+
+
 # ------------------------------------------------------------------ point cloud <-> dense grid, spectral PSR (csrc/grid_points.hip)
 GRID_MODES = {"torch": _lib.GRID_TORCH, "sap": _lib.GRID_SAP}
 

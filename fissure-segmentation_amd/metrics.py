@@ -11,7 +11,8 @@ differentiable.
 `label_mesh_assd` (metrics.py:45-55) starts from `utils.general_utils.mask_to_points`; the way back from meshes to label
 maps, for `batch_dice`, is data_processing/surface_fitting.py and surface_fitting_optimization.py.
 
-Not included: `label_label_assd` (metrics.py:79-93), the distance between the point clouds of two label maps.
+Not included under its name: `label_label_assd` (metrics.py:79-93), the distance between the point clouds of two label maps;
+`functional.labelmap_distances` computes the same four numbers from a distance transform.
 """
 import numpy as np
 import torch

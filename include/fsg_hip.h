@@ -1056,6 +1056,33 @@ int fsg_component_stats_i32(const int32_t *labels, int B, int D, int H, int W, i
 int fsg_relabel_lut_i32(const int32_t *labels, int B, int64_t n_per_item, const int32_t *lut, int lut_len, void *out,
                         int out_is_i64, fsg_stream_t stream);
 
+/* Exact squared Euclidean distance transform of bit planes, optional feature transform, nearest of K planes (csrc/edt.hip).
+ * Stands where data_processing/process_lung_mask.py:80-91 of the reference calls scipy.ndimage.distance_transform_edt, and
+ * gives the nearest-neighbour distances between the voxel clouds of two label maps of metrics.py:79-93.  All pointers DEVICE.
+ *
+ * bits is a bit plane (B, D, H, WW) as above.  A SITE is a voxel whose bit is 0; out_d2 (B, D, H, W) is, at every voxel, the
+ *   smallest (s0 dz)^2 + (s1 dy)^2 + (s2 dx)^2 to a site of the same item.  An item without a site gives +inf everywhere in
+ *   the fp32 mode and INT32_MAX in the int32 mode (scipy returns garbage there; this rule is ours).
+ * Three separable passes (W from the words of the row, then H, then D; see the head of csrc/edt.hip), each exact.  The int32
+ *   mode (unit spacing) is exact in integers; every dimension is at most 16384 and D H W < 2^31.  The fp32 mode forms each
+ *   term as fl(fl(s * delta)^2) and each sum with one rounding, no fused multiply-add; spacings are positive, at most 1e6.
+ * out_idx (B, D, H, W) int32 or NULL: the linear index (z H + y) W + x, inside the item, of the site that won; -1 where
+ *   there is none.  Ties: per pass the smaller |delta| wins, then the lower index along that axis -- not scipy's rule.
+ * No atomics, no host read, everything on `stream`: the same input gives the same bits, an item does not depend on its batch.
+ * workspace: the query below (4 bytes per voxel, 8 with indices), 8-byte aligned.
+ * Nearest label: d2 is (K, V) int32 (is_f32 = 0) or fp32 distance planes, K <= 64; out[v] = cand[k] of the first plane k
+ *   with the smallest value (cand ascending: the lowest label wins a tie, as np.argmin does at process_lung_mask.py:87), or 0
+ *   where keep (V) uint8, if given, is 0 (process_lung_mask.py:88).
+ * Bad arguments (a dimension above 16384, 2^31 voxels or more, a spacing that is not positive, a NULL pointer, a short
+ *   workspace) are FSG_ERR_ARG. */
+size_t fsg_edt_workspace_bytes(int B, int D, int H, int W, int with_indices);
+int fsg_edt_sq_i32(const uint64_t *bits, int B, int D, int H, int W, int32_t *out_d2, int32_t *out_idx, void *workspace,
+                   size_t workspace_bytes, fsg_stream_t stream);
+int fsg_edt_sq_f32(const uint64_t *bits, int B, int D, int H, int W, float s0, float s1, float s2, float *out_d2,
+                   int32_t *out_idx, void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+int fsg_edt_nearest_label(const void *d2, int is_f32, int K, int64_t V, const int32_t *cand, const uint8_t *keep, int32_t *out,
+                          fsg_stream_t stream);
+
 /* Mesh regularisers and surface sampling for the PC-AE mesh loss (csrc/mesh.hip).  Replace pytorch3d's mesh_edge_loss,
  * mesh_normal_consistency, mesh_laplacian_smoothing(method="uniform") and sample_points_from_meshes as
  * losses/mesh_loss.py:28-57 and data_processing/surface_fitting_optimization.py call them.  All pointers DEVICE.

@@ -493,6 +493,102 @@ if "morph" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "edt" in which:
+    # Euclidean distance transform (csrc/edt.hip), nearest_label and the lung split on top of it, beside
+    # scipy.ndimage.distance_transform_edt on the host in the same run (there is no torch composition of an exact EDT).
+    # Masks: (a) the synthetic two-lung volume of the tests scaled to the shape (sites = everything outside the lungs),
+    # (b) the worst case of the outward walk, one site in a corner of a set volume.  FSG_EDT_HOST=0 leaves the host runs out.
+    import json, time
+    import numpy as np
+    from scipy import ndimage as ndi
+    import edt_oracle as eo
+    import morphology_oracle as mo
+    from fissure_segmentation_amd.data_processing import process_lung_mask as plm
+    shapes = [tuple(int(v) for v in a.split("x")) for a in os.environ.get("FSG_EDT_SHAPES", "128x128x128,256x256x320").split(",")]
+    with_host = os.environ.get("FSG_EDT_HOST", "1") != "0"
+    spacing = (2.5, 1.0, 0.75)
+
+    def peak(fn):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn(); torch.cuda.synchronize()
+        del out
+        return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    def host(fn):
+        t0 = time.perf_counter(); out = fn()
+        return round((time.perf_counter() - t0) * 1e6, 1), out
+
+    lines = []
+    for shape in shapes:
+        D, H, W = shape
+        V = D * H * W
+        lung = mo.lung_volume(shape)[0]
+        corner = np.ones(shape, bool)
+        corner[0, 0, 0] = False
+        bridged = lung.copy()
+        bridged[D // 2 - 1:D // 2 + 2, H // 2 - 1:H // 2 + 2, int(W * 0.26):int(W * 0.74)] = True     # a bar three voxels thick
+        rec = dict(kernel="Euclidean distance transform on bit planes", shape="x".join(map(str, shape)), voxels=V,
+                   compulsory_MB=round((V / 8 + 4 * V + 2 * 8 * V) / 1e6, 1), compulsory_with_indices_MB=round(
+                       (V / 8 + 4 * V + 12 * V + 2 * 16 * V) / 1e6, 1))
+        for mname, m in (("lungs", lung), ("corner", corner)):
+            t = torch.from_numpy(m).to(dev)
+            bits = F._pack_bits(t[None])
+            for vname, s, want_idx in (("unit", None, False), ("unit_idx", None, True), ("spacing", spacing, False),
+                                       ("spacing_idx", spacing, True)):
+                key = f"{mname}_{vname}"
+                med, mn = timeit(lambda: F._edt_bits(bits, W, s, want_idx), iters=10, warm=2)
+                rec[f"{key}_kernels_us"] = round(med, 1)
+                med, mn = timeit(lambda: F.distance_transform_edt(t, sampling=s, return_indices=want_idx), iters=10, warm=2)
+                rec[f"{key}_hip_us"] = round(med, 1)
+                rec[f"{key}_hip_peak_MiB"] = peak(lambda: F.distance_transform_edt(t, sampling=s, return_indices=want_idx))
+                print("edt: %s %s done" % (rec["shape"], key), file=sys.stderr, flush=True)
+            rec[f"{mname}_unit_kernels_GBps_of_compulsory"] = round(rec["compulsory_MB"] * 1e6 / (rec[f"{mname}_unit_kernels_us"] * 1e-6) / 1e9, 1)
+            if with_host:
+                hus, ref = host(lambda: ndi.distance_transform_edt(m))
+                rec[f"{mname}_unit_scipy_us"] = hus
+                rec[f"{mname}_unit_speedup_vs_scipy"] = round(hus / rec[f"{mname}_unit_hip_us"], 1)
+                got = F.distance_transform_edt(t, squared=True).cpu().numpy()
+                rec[f"{mname}_unit_equals_scipy"] = bool(np.array_equal(got, np.rint(ref ** 2).astype(np.int32)))
+                if mname == "lungs":
+                    hus, ref = host(lambda: ndi.distance_transform_edt(m, sampling=spacing, return_indices=True))
+                    rec["lungs_spacing_idx_scipy_us"] = hus
+                    rec["lungs_spacing_idx_speedup_vs_scipy"] = round(hus / rec["lungs_spacing_idx_hip_us"], 1)
+                    got = F.distance_transform_edt(t, sampling=spacing, squared=True).cpu().numpy().astype(np.float64)
+                    rec["lungs_spacing_max_rel_err"] = float(np.max(np.abs(got - ref[0] ** 2)[ref[0] > 0] / ref[0][ref[0] > 0] ** 2))
+                del ref, got
+        # nearest_label with two labels: the restoration step of the lung split (sites = the voxels of each lung)
+        lab = torch.from_numpy(mo.label(lung, 6)[0]).to(dev)
+        med, mn = timeit(lambda: F.nearest_label(lab, (1, 2)), iters=10, warm=2)
+        rec["nearest_label2_hip_us"] = round(med, 1)
+        rec["nearest_label2_hip_peak_MiB"] = peak(lambda: F.nearest_label(lab, (1, 2)))
+        tb = torch.from_numpy(bridged).to(dev)
+        import contextlib, io
+        def split():
+            with contextlib.redirect_stdout(io.StringIO()):
+                return plm.binary_lung_mask_to_left_right(tb)
+        out = split()
+        rec["lung_split_opened"] = bool(F.connected_components(tb)[1] == 1)
+        med, mn = timeit(split, iters=5, warm=1)
+        rec["lung_split_hip_us"] = round(med, 1)
+        rec["lung_split_hip_peak_MiB"] = peak(split)
+        if with_host:
+            lab_np = lab.cpu().numpy()
+            hus, ref = host(lambda: eo.nearest_label(lab_np, (1, 2)))
+            rec["nearest_label2_scipy_us"] = hus
+            rec["nearest_label2_speedup_vs_scipy"] = round(hus / rec["nearest_label2_hip_us"], 1)
+            rec["nearest_label2_equals_scipy"] = bool(np.array_equal(F.nearest_label(lab, (1, 2)).cpu().numpy(), ref))
+            hus, (ref, radii, _) = host(lambda: eo.lung_split(bridged))
+            rec["lung_split_scipy_us"] = hus
+            rec["lung_split_speedup_vs_scipy"] = round(hus / rec["lung_split_hip_us"], 1)
+            rec["lung_split_equals_scipy"] = bool(np.array_equal(out.cpu().numpy(), ref))
+            rec["lung_split_scipy_radii"] = radii
+        print("EDT " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    out_path = os.environ.get("FSG_EDT_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
 if "mesh" in which:
     # mesh regularisers, surface sampler and the whole default mesh loss (csrc/mesh.hip) beside the torch composition of the
     # same math on the same device (the oracle's fp32 code, tests/mesh_oracle.py, batched over the shared face list), value +
