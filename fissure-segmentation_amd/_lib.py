@@ -158,6 +158,9 @@ SIGNATURES = {
     "fsg_edt_sq_i32": ([_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_edt_sq_f32": ([_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_edt_nearest_label": ([_P, _I, _I, _L, _P, _P, _P, _P], _I),
+    "fsg_bspline_prefilter_axis_f32": ([_P, _L, _I, _L, _P, _P], _I),
+    "fsg_gauss_axis_f32": ([_P, _I, _L, _I, _L, _P, _P, _P, _P], _I),
+    "fsg_spatial_resample_f32": ([_P, _I, _I, _P, _I, _I, _I] + [_I] * 7 + [_P, _P, _P, _P, _F, _F, _P, _P, _P], _I),
     "fsg_mesh_reg_workspace_bytes": ([_I, _I], ctypes.c_size_t),
     "fsg_mesh_reg_f32": ([_P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_mesh_sample_workspace_bytes": ([_I, _I], ctypes.c_size_t),
@@ -194,6 +197,8 @@ for _name, (_args, _res) in SIGNATURES.items():
 
 GRID_TORCH, GRID_SAP = 0, 1   # include/fsg_hip.h: FSG_GRID_*
 MORPH_MAX_RADIUS = 8   # csrc/morphology.hip: MAXR
+BSPLINE_PAD = 12   # include/fsg_hip.h: FSG_BSPLINE_PAD
+LABEL_U8, LABEL_I32, LABEL_I64 = 0, 1, 2   # include/fsg_hip.h: FSG_LABEL_*
 PCL_NORMALS_MAX_K = 64   # include/fsg_hip.h: fsg_pcl_normals_f32 (what fsg_knn_segment_f32 can deliver)
 ORIENT_MAX_POINTS = 1 << 20   # include/fsg_hip.h: fsg_orient_normals_f32 (20 bits per endpoint in the edge key)
 RW_BINARY, RW_INTENSITY, RW_MAX_LABELS = 0, 1, 8   # include/fsg_hip.h: FSG_RW_*; csrc/random_walk.hip builds K = 1..8

@@ -167,3 +167,96 @@ def sample_and_augment(x, labels=None, sample_points=None, augment=True, binary=
         if binary:
             lbl = (lbl != 0).long()
     return out, lbl, transforms
+
+
+# ------------------------------------------------------------------ voxel patches (reference: augmentations.py:13-49)
+# The reference hands a (B, C, D, H, W) numpy batch to batchgenerators' SpatialTransform + MirrorTransform.  Batchgenerators is
+# not vendored and parity with it is unpinned; the rules below restate its published behaviour (`augment_spatial`,
+# `MirrorTransform`) and DESIGN.md lists them.  Everything runs on the device: the draws use a torch generator (numpy's global
+# stream is not reproduced), the elastic field and the resampling are csrc/spatial.hip.
+def spacing_resampling_matrix(input_size, input_spacing, target_spacing=1.):
+    """augmentations.py:13-18: the (1, 3, 4) affine_grid matrix that resamples to `target_spacing`, and the output size"""
+    from .utils.image_ops import get_resample_factors
+    rescale = get_resample_factors(input_spacing, target_spacing)
+    mat = torch.zeros(1, 3, 4)
+    mat[:, :3, :3] = torch.diag(torch.tensor(rescale))
+    output_size = [int(round(s * f)) for s, f in zip(input_size, rescale)]
+    return mat, output_size
+
+
+def _uniform(shape, lo, hi, generator, device):
+    return torch.rand(shape, generator=generator, device=device) * (hi - lo) + lo
+
+
+def random_spatial_parameters(B, img_shape, patch_size, generator=None, device=None, angle=(-0.3, 0.3), scale=(0.8, 1.2),
+                              alpha=(0., 1000.), sigma=(10., 13.), p_mirror=0.7, p_mirror_axis=0.5):
+    """The random draws of one `image_augmentation` call for B items, on the device, without a host read -> dict of
+    matrix (B, 3, 3), centre (B, 3), mirror (B, 3) bool, sigma (B,), alpha (B,).  Defaults as the reference calls
+    SpatialTransform / MirrorTransform (augmentations.py:34-43); axes are (D, H, W).
+      rotation   one angle per axis, U(angle); R = R0 @ R1 @ R2 (R0 turns the (H, W) plane, R1 the (D, W) plane, R2 the (D, H)
+                 plane, signs as batchgenerators' create_matrix_rotation_{x,y,z}_3d); coordinates are ROW vectors times R,
+                 so the matrix applied to a column vector is R^T
+      scale      with probability 0.5 (and scale[0] < 1) U(scale[0], 1), else U(max(scale[0], 1), scale[1]); one factor for
+                 all axes, multiplied onto the coordinates: matrix = s R^T
+      centre     U(patch // 2, n - patch // 2) per axis, continuous: at least half a patch from every border; an axis
+                 shorter than its patch gets (n - 1) / 2
+      mirror     an item is mirrored with probability p_mirror, then every axis independently with p_mirror_axis
+      elastic    alpha ~ U(alpha), sigma ~ U(sigma) per item
+    `device` defaults to the generator's device, else the current CUDA device."""
+    if device is None:
+        device = generator.device if generator is not None else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("fissure_segmentation_amd runs on the GPU only (got a CPU device for the random draws)")
+    shape, patch = tuple(int(v) for v in img_shape[-3:]), tuple(int(v) for v in patch_size)
+    if len(shape) != 3 or len(patch) != 3 or min(shape) < 1 or min(patch) < 1 or B < 1:
+        raise ValueError(f"random_spatial_parameters: B={B}, img_shape={img_shape!r}, patch_size={patch_size!r}")
+    ang = _uniform((B, 3), angle[0], angle[1], generator, device)
+    cos, sin = ang.cos(), ang.sin()
+    one, zero = torch.ones(B, device=device), torch.zeros(B, device=device)
+    r0 = torch.stack([one, zero, zero, zero, cos[:, 0], -sin[:, 0], zero, sin[:, 0], cos[:, 0]], 1).view(B, 3, 3)
+    r1 = torch.stack([cos[:, 1], zero, sin[:, 1], zero, one, zero, -sin[:, 1], zero, cos[:, 1]], 1).view(B, 3, 3)
+    r2 = torch.stack([cos[:, 2], -sin[:, 2], zero, sin[:, 2], cos[:, 2], zero, zero, zero, one], 1).view(B, 3, 3)
+    rot = r0 @ r1 @ r2
+    u = torch.rand(B, 3, generator=generator, device=device)
+    lo, hi = float(scale[0]), float(scale[1])
+    small = lo + u[:, 1] * (1.0 - lo)
+    large = max(lo, 1.0) + u[:, 2] * (hi - max(lo, 1.0))
+    sc = torch.where((u[:, 0] < 0.5) & (lo < 1.0), small, large)
+    matrix = (rot.transpose(1, 2) * sc[:, None, None]).contiguous()
+    r = torch.rand(B, 3, generator=generator, device=device)       # (host numbers below: nothing is copied to the device)
+    centre = torch.stack([r[:, i] * float(n - 2 * (p // 2)) + float(p // 2) if n - 2 * (p // 2) >= 0
+                          else torch.full((B,), (n - 1) / 2, device=device) for i, (n, p) in enumerate(zip(shape, patch))], 1)
+    m = torch.rand(B, 4, generator=generator, device=device)
+    mirror = (m[:, :1] < p_mirror) & (m[:, 1:] < p_mirror_axis)
+    return {"matrix": matrix, "centre": centre, "mirror": mirror,
+            "sigma": _uniform((B,), sigma[0], sigma[1], generator, device),
+            "alpha": _uniform((B,), alpha[0], alpha[1], generator, device)}
+
+
+def image_augmentation(img, seg, patch_size=(128, 128, 128), generator=None, return_params=False, prefiltered=False,
+                       order_data=3, order_seg=1, intensity=None):
+    """augmentations.py:29-49 for a batch on the device: one randomly rotated, scaled, elastically deformed and mirrored patch
+    per item out of img (B, C, D, H, W) and seg (B, Cs, D, H, W) -> (img_patch fp32, seg_patch int64), both (B, ., *patch_size).
+    GPU tensors in, GPU tensors out; no host read.  `generator`: a CUDA torch.Generator (the same seed gives the same patch).
+    order_data 3 / order_seg 1 are SpatialTransform's defaults, which the reference's call keeps.
+    prefiltered=True: `img` holds `functional.bspline_prefilter(image)`, kept by the data set across epochs.
+    intensity (a, b): `normalize_img` (data.py:365-366) folded into the store, a = 2 / (max - min), b = -2 min / (max - min) - 1.
+    return_params=True appends the keyword arguments that make `functional.spatial_transform(img, seg, patch_size, **params)`
+    reproduce the patch: matrix, centre, elastic, mirror (and order_data, order_seg, prefiltered, intensity)."""
+    from . import functional as F_hip
+    ref = img if img is not None else seg
+    if ref is None or ref.dim() != 5:
+        raise ValueError("image_augmentation: expected img and / or seg of shape (B, C, D, H, W)")
+    F_hip._need_gpu(img, seg)
+    patch = F_hip._patch3(patch_size, "image_augmentation")
+    B = ref.shape[0]
+    pad = 2 * F_hip.BSPLINE_PAD if prefiltered else 0
+    shape = tuple(int(s) - pad for s in ref.shape[2:]) if ref is img else tuple(ref.shape[2:])
+    p = random_spatial_parameters(B, shape, patch, generator=generator, device=ref.device)
+    noise = torch.rand((B, 3) + patch, generator=generator, device=ref.device) * 2 - 1
+    params = {"matrix": p["matrix"], "centre": p["centre"], "elastic": F_hip.elastic_field(noise, p["sigma"], p["alpha"]),
+              "mirror": p["mirror"], "order_data": order_data, "order_seg": order_seg, "prefiltered": prefiltered,
+              "intensity": intensity}
+    out = F_hip.spatial_transform(img, seg, patch, **params)
+    return (out[0], out[1], params) if return_params else out

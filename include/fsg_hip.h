@@ -1083,6 +1083,43 @@ int fsg_edt_sq_f32(const uint64_t *bits, int B, int D, int H, int W, float s0, f
 int fsg_edt_nearest_label(const void *d2, int is_f32, int K, int64_t V, const int32_t *cand, const uint8_t *keep, int32_t *out,
                           fsg_stream_t stream);
 
+/* Voxel patch augmentation and resampling (csrc/spatial.hip).  Stands where ImageDataset.__getitem__ of the reference
+ * (data.py:290-327) calls batchgenerators' SpatialTransform + MirrorTransform (augmentations.py:29-49), sitk.Resample
+ * (utils/image_ops.py:12-28) and normalize_img (data.py:365-366).  All pointers DEVICE, everything fp32, no atomics, no host
+ * read, everything on `stream`: the same input gives the same bits, an item does not depend on its batch.
+ *
+ * Prefilter, one axis: in is (outer, n, inner), out (outer, n + 2 FSG_BSPLINE_PAD, inner): every line of n samples extended
+ *   by FSG_BSPLINE_PAD edge-replicated samples on both sides and turned into cubic B-spline coefficients as
+ *   scipy.ndimage.spline_filter1d(order=3, mode='nearest') does (pole sqrt(3) - 2).  Three calls, one per axis, give the
+ *   coefficients that fsg_spatial_resample_f32 reads at order 3.  in != out.
+ * Gauss, one axis: in and out are (B, outer, n, inner), outer n inner < 2^31; out = gaussian_filter1d(in, sigma[b],
+ *   mode='constant', cval=0, truncate=4) along the n axis with scipy's taps (radius int(4 sigma + 0.5), which may exceed n),
+ *   times alpha[b] when alpha is not NULL.  sigma, alpha (B).  An item whose sigma is not in (0, 255] gives NaN.  in != out.
+ * Resample: for output voxel o = (oz, oy, ox) of item b the source coordinate is
+ *     x = M_b ((o - (patch - 1) / 2) + elastic_b(o)) + centre_b      voxel units, axes (D, H, W)
+ *   with matrix (B, 3, 3) row-major, centre (B, 3), elastic (B, 3, pd, ph, pw) or NULL.
+ *   src (B, C, D, H, W) is read at order_data 0 (nearest, floor(x + 0.5)) or 1 (trilinear), the coordinate clamped to
+ *   [0, n - 1]; at order_data 3 src is the prefiltered (B, C, D + 2 PAD, H + 2 PAD, W + 2 PAD) read at x + PAD with the 4 tap
+ *   indices per axis clamped to the padded array (scipy's map_coordinates(order=3, mode='nearest'): beyond the padding the
+ *   value runs into the edge coefficient).  out_img
+ *   (B, C, pd, ph, pw) = ia * value + ib.  src may be NULL.
+ *   seg (B, Cs, D, H, W) of seg_kind FSG_LABEL_* (values must fit an int32), or NULL: order_seg 0 is the nearest label,
+ *   order_seg 1 the largest label whose summed trilinear weight among the 8 corners is >= 0.5, else 0; for both a
+ *   coordinate outside [0, n - 1] on any axis gives 0 (scipy's mode='constant', cval=0).  out_seg (B, Cs, pd, ph, pw) int64.
+ *   mirror (B, 3) uint8 or NULL: a nonzero flag stores the item's output reversed along that axis.
+ * Volumes (padded) and patches hold fewer than 2^31 voxels, B <= 65535.  Bad arguments are FSG_ERR_ARG. */
+#define FSG_BSPLINE_PAD 12
+#define FSG_LABEL_U8 0
+#define FSG_LABEL_I32 1
+#define FSG_LABEL_I64 2
+int fsg_bspline_prefilter_axis_f32(const float *in, int64_t outer, int n, int64_t inner, float *out, fsg_stream_t stream);
+int fsg_gauss_axis_f32(const float *in, int B, int64_t outer, int n, int64_t inner, const float *sigma, const float *alpha,
+                       float *out, fsg_stream_t stream);
+int fsg_spatial_resample_f32(const float *src, int C, int order_data, const void *seg, int seg_kind, int Cs, int order_seg,
+                             int B, int D, int H, int W, int pd, int ph, int pw, const float *matrix, const float *centre,
+                             const float *elastic, const uint8_t *mirror, float ia, float ib, float *out_img,
+                             int64_t *out_seg, fsg_stream_t stream);
+
 /* Mesh regularisers and surface sampling for the PC-AE mesh loss (csrc/mesh.hip).  Replace pytorch3d's mesh_edge_loss,
  * mesh_normal_consistency, mesh_laplacian_smoothing(method="uniform") and sample_points_from_meshes as
  * losses/mesh_loss.py:28-57 and data_processing/surface_fitting_optimization.py call them.  All pointers DEVICE.

@@ -1192,3 +1192,125 @@ if "reg" in which:
     out_path = os.environ.get("FSG_REG_BENCH_OUT", os.path.join(ROOT, "profiles", "reg_bench.jsonl"))
     with open(out_path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+if "spatial" in which:
+    # Voxel patch augmentation (csrc/spatial.hip): the prefilter, the elastic field, the fused resample at orders 3 and 1 and the
+    # whole image_augmentation, volume 224 x 160 x 224, patch 128^3, B = 1 and 4.  The order-1 path (elastic field + resample of
+    # image and labels) races the torch composition of the same math on the device in the same run, alternating (separable
+    # conv3d smoothing + grid_sample; torch has no order-3 sampler); scipy on the host, the code batchgenerators calls, is the
+    # other column (B = 1 item; FSG_SPATIAL_HOST=0 leaves it out).  Writes profiles/spatial_bench.jsonl.
+    import json, time
+    import numpy as np
+    import spatial_oracle as so
+    from fissure_segmentation_amd import augmentations as aug
+    from torch.nn import functional as TF
+    lines = []
+    VOL, PATCH, SIGMA, ALPHA = (224, 160, 224), (128, 128, 128), 11.5, 500.0
+    with_host = os.environ.get("FSG_SPATIAL_HOST", "1") != "0"
+
+    def peak_extra(fn):
+        torch.cuda.synchronize(); torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn(); torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 1)
+
+    def composition(vol, seg, noise, matrix, centre, mirror, intensity):
+        """the order-1 path in torch ops: zero-padded separable Gaussian (scipy's taps), coordinates, grid_sample (bilinear +
+        border for the image, nearest + zeros for the labels), flips, intensity"""
+        B = vol.shape[0]
+        r = int(4 * SIGMA + 0.5)
+        x = torch.arange(-r, r + 1, device=dev, dtype=torch.float32)
+        w = torch.exp(-0.5 / SIGMA ** 2 * x * x)
+        w = w / w.sum()
+        e = noise.reshape(B * 3, 1, *PATCH)
+        e = TF.conv3d(e, w.view(1, 1, 1, 1, -1), padding=(0, 0, r))
+        e = TF.conv3d(e, w.view(1, 1, 1, -1, 1), padding=(0, r, 0))
+        e = TF.conv3d(e, w.view(1, 1, -1, 1, 1), padding=(r, 0, 0))
+        e = e.reshape(B, 3, *PATCH) * ALPHA
+        grid = torch.stack(torch.meshgrid(*(torch.arange(p, device=dev, dtype=torch.float32) - (p - 1) / 2 for p in PATCH),
+                                          indexing="ij"))
+        src = torch.einsum("bij,bjdhw->bidhw", matrix, grid[None] + e) + centre[:, :, None, None, None]
+        size = torch.tensor(VOL, device=dev, dtype=torch.float32).view(1, 3, 1, 1, 1)
+        g = (2 * src / (size - 1) - 1).permute(0, 2, 3, 4, 1).flip(-1)
+        img = TF.grid_sample(vol, g, mode="bilinear", padding_mode="border", align_corners=True)
+        lab = TF.grid_sample(seg.float(), g, mode="nearest", padding_mode="zeros", align_corners=True).long()
+        img = img * intensity[0] + intensity[1]
+        outs = []
+        for t in (img, lab):
+            for ax in range(3):
+                t = torch.where(mirror[:, ax].view(B, 1, 1, 1, 1), t.flip(2 + ax), t)
+            outs.append(t)
+        return outs
+
+    for B in (1, 4):
+        g = torch.Generator(device=dev).manual_seed(3)
+        vol = torch.randn(B, 1, *VOL, device=dev, generator=g)
+        seg = (torch.rand(B, 1, *VOL, device=dev, generator=g) * 5).long()
+        p = aug.random_spatial_parameters(B, VOL, PATCH, generator=g)
+        noise = torch.rand(B, 3, *PATCH, device=dev, generator=g) * 2 - 1
+        inten = (2.0 / 1624.0, 0.26)
+        coef = F.bspline_prefilter(vol)
+        el = F.elastic_field(noise, SIGMA, ALPHA)
+        kw = dict(matrix=p["matrix"], centre=p["centre"], elastic=el, mirror=p["mirror"], intensity=inten)
+        rec = dict(kernel="voxel patch augmentation", volume=list(VOL), patch=list(PATCH), B=B, sigma=SIGMA)
+        rec["prefilter_us"] = round(timeit(lambda: F.bspline_prefilter(vol), iters=10, warm=2)[0], 1)
+        rec["elastic_field_us"] = round(timeit(lambda: F.elastic_field(noise, SIGMA, ALPHA), iters=10, warm=2)[0], 1)
+        rec["resample_order3_us"] = round(timeit(lambda: F.spatial_transform(coef, seg, PATCH, order_data=3, prefiltered=True, **kw),
+                                                 iters=10, warm=2)[0], 1)
+        rec["resample_order1_us"] = round(timeit(lambda: F.spatial_transform(vol, seg, PATCH, order_data=1, **kw), iters=10, warm=2)[0], 1)
+        rec["resample_order1_labels1_us"] = round(timeit(lambda: F.spatial_transform(vol, seg, PATCH, order_data=1, order_seg=1, **kw),
+                                                         iters=10, warm=2)[0], 1)
+        rec["image_augmentation_cached_us"] = round(timeit(lambda: aug.image_augmentation(coef, seg, PATCH, generator=g, prefiltered=True,
+                                                                                          intensity=inten), iters=10, warm=2)[0], 1)
+        rec["image_augmentation_uncached_us"] = round(timeit(lambda: aug.image_augmentation(vol, seg, PATCH, generator=g, intensity=inten),
+                                                             iters=10, warm=2)[0], 1)
+
+        def fused1():
+            e = F.elastic_field(noise, SIGMA, ALPHA)
+            return F.spatial_transform(vol, seg, PATCH, p["matrix"], p["centre"], elastic=e, mirror=p["mirror"], order_data=1,
+                                       intensity=inten)
+
+        def comp1():
+            return composition(vol, seg, noise, p["matrix"], p["centre"], p["mirror"], inten)
+        a = timeit(fused1, iters=8, warm=2)[0]
+        c = timeit(comp1, iters=8, warm=2)[0]
+        a2 = timeit(fused1, iters=8, warm=2)[0]
+        rec["order1_path_fused_us"], rec["order1_path_fused_again_us"], rec["order1_path_torch_us"] = round(a, 1), round(a2, 1), round(c, 1)
+        rec["order1_path_speedup"] = round(c / max(a, a2), 2)
+        rec["order1_path_verdict"] = "fused wins" if max(a, a2) < c else "fused LOSES"
+        fi, fl = fused1()
+        ci, cl = comp1()
+        rec["order1_image_max_abs_diff_vs_torch"] = float((fi - ci).abs().max())
+        rec["order1_labels_differing_share_vs_torch"] = float((fl != cl).double().mean())
+        rec["prefilter_peak_extra_MiB"] = peak_extra(lambda: F.bspline_prefilter(vol))
+        rec["elastic_field_peak_extra_MiB"] = peak_extra(lambda: F.elastic_field(noise, SIGMA, ALPHA))
+        rec["image_augmentation_cached_peak_extra_MiB"] = peak_extra(
+            lambda: aug.image_augmentation(coef, seg, PATCH, generator=g, prefiltered=True, intensity=inten))
+        rec["order1_path_fused_peak_extra_MiB"], rec["order1_path_torch_peak_extra_MiB"] = peak_extra(fused1), peak_extra(comp1)
+        if with_host and B == 1:
+            from scipy import ndimage as ndi
+            v, s, n = vol[0, 0].cpu().numpy().astype(np.float64), seg[0, 0].cpu().numpy(), noise[0].cpu().numpy().astype(np.float64)
+            t0 = time.perf_counter(); sm = ndi.gaussian_filter(n[0], SIGMA, mode="constant", cval=0)
+            rec["scipy_gaussian_one_component_us"] = round((time.perf_counter() - t0) * 1e6)
+            coords = so.coordinates(p["matrix"][:1].cpu().numpy(), p["centre"][:1].cpu().numpy(), el[:1].cpu().numpy(), PATCH)[0]
+            t0 = time.perf_counter(); w3 = ndi.map_coordinates(v, coords, order=3, mode="nearest")
+            rec["scipy_map_coordinates_order3_us"] = round((time.perf_counter() - t0) * 1e6)
+            t0 = time.perf_counter(); w1 = ndi.map_coordinates(v, coords, order=1, mode="nearest")
+            rec["scipy_map_coordinates_order1_us"] = round((time.perf_counter() - t0) * 1e6)
+            t0 = time.perf_counter(); ndi.map_coordinates(s, coords, order=0, mode="constant", cval=0)
+            rec["scipy_map_coordinates_labels_us"] = round((time.perf_counter() - t0) * 1e6)
+            rec["scipy_whole_sample_order3_us"] = (3 * rec["scipy_gaussian_one_component_us"] + rec["scipy_map_coordinates_order3_us"]
+                                                   + rec["scipy_map_coordinates_labels_us"])
+            plain = dict(kw, mirror=None, intensity=None)
+            g3 = F.spatial_transform(coef[:1], None, PATCH, order_data=3, prefiltered=True, **{k: (t[:1] if torch.is_tensor(t) else t)
+                                                                                               for k, t in plain.items()})[0]
+            rec["order3_max_abs_err_vs_scipy"] = float(np.abs(g3[0, 0].cpu().numpy() - w3).max())
+            rec["speedup_vs_scipy_whole_sample"] = round(rec["scipy_whole_sample_order3_us"] / rec["image_augmentation_cached_us"], 1)
+            del sm, w1
+        lines.append(json.dumps(rec))
+        print("SPATIAL " + lines[-1], flush=True)
+        del vol, seg, coef, el, noise
+    out_path = os.environ.get("FSG_SPATIAL_BENCH_OUT", os.path.join(ROOT, "profiles", "spatial_bench.jsonl"))
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
