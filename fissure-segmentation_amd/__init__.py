@@ -35,7 +35,7 @@ def install_reference_aliases():
         "data_processing.fissure_enhancement": ".data_processing.fissure_enhancement",
         "data_processing.random_walk": ".data_processing.random_walk", "data_processing.find_lobes": ".data_processing.find_lobes",
         "utils.image_utils": ".utils.image_utils", "utils.general_utils": ".utils.general_utils",
-        "utils.image_ops": ".utils.image_ops",
+        "utils.image_ops": ".utils.image_ops", "utils.fissure_utils": ".utils.fissure_utils",
         "data_processing.surface_fitting": ".data_processing.surface_fitting",
         "data_processing.surface_fitting_optimization": ".data_processing.surface_fitting_optimization",
         "models.divroc": ".models.divroc", "models.dpsr_utils": ".models.dpsr_utils", "models.dpsr_net": ".models.dpsr_net",
@@ -45,11 +45,13 @@ def install_reference_aliases():
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)
-    # the reference keeps `pointcloud_surface_fitting` in data_processing/surface_fitting.py, this package in a module of its own:
-    # under the reference's name both are found (a module object that carries the names of the two)
+    # the reference keeps `pointcloud_surface_fitting` and `poisson_reconstruction` in data_processing/surface_fitting.py, this
+    # package in modules of their own: under the reference's name all are found (a module object that carries the names of the three)
     import types
     both = types.ModuleType("data_processing.surface_fitting", "fissure_segmentation_amd.data_processing.surface_fitting + "
-                            "fissure_segmentation_amd.data_processing.pointcloud_surface_fitting")
-    for ours in (".data_processing.pointcloud_surface_fitting", ".data_processing.surface_fitting"):
+                            "fissure_segmentation_amd.data_processing.pointcloud_surface_fitting + "
+                            "fissure_segmentation_amd.data_processing.poisson_reconstruction")
+    for ours in (".data_processing.poisson_reconstruction", ".data_processing.pointcloud_surface_fitting",
+                 ".data_processing.surface_fitting"):
         both.__dict__.update({k: v for k, v in vars(importlib.import_module(ours, __name__)).items() if not k.startswith("_")})
     sys.modules["data_processing.surface_fitting"] = both

@@ -158,6 +158,8 @@ SIGNATURES = {
     "fsg_edt_sq_i32": ([_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_edt_sq_f32": ([_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_edt_nearest_label": ([_P, _I, _I, _L, _P, _P, _P, _P], _I),
+    "fsg_thin_max_words": ([], _I),
+    "fsg_thin_bits": ([_P, _I, _I, _I, _I, _P, _P, _P], _I),
     "fsg_bspline_prefilter_axis_f32": ([_P, _L, _I, _L, _P, _P], _I),
     "fsg_gauss_axis_f32": ([_P, _I, _L, _I, _L, _P, _P, _P, _P], _I),
     "fsg_spatial_resample_f32": ([_P, _I, _I, _P, _I, _I, _I] + [_I] * 7 + [_P, _P, _P, _P, _F, _F, _P, _P, _P], _I),
@@ -197,6 +199,7 @@ for _name, (_args, _res) in SIGNATURES.items():
 
 GRID_TORCH, GRID_SAP = 0, 1   # include/fsg_hip.h: FSG_GRID_*
 MORPH_MAX_RADIUS = 8   # csrc/morphology.hip: MAXR
+THIN_MAX_WORDS = 8192   # csrc/thinning.hip: MAX_WORDS, the 64-bit words H * ceil(W / 64) of one slice that fit in LDS (twice)
 BSPLINE_PAD = 12   # include/fsg_hip.h: FSG_BSPLINE_PAD
 LABEL_U8, LABEL_I32, LABEL_I64 = 0, 1, 2   # include/fsg_hip.h: FSG_LABEL_*
 PCL_NORMALS_MAX_K = 64   # include/fsg_hip.h: fsg_pcl_normals_f32 (what fsg_knn_segment_f32 can deliver)

@@ -1,8 +1,9 @@
 """`pointcloud_surface_fitting` of the reference's data_processing/surface_fitting.py (:42-84) and `fit_label_surfaces`, the
 batched form of the per-label loop around it.  They live in a module of their own, not in this package's
 data_processing/surface_fitting.py: import them from `fissure_segmentation_amd.data_processing.pointcloud_surface_fitting`.
-Not in scope: `poisson_reconstruction` (it needs sitk.BinaryThinning, which has no counterpart here),
-`regularize_fissure_segmentations` and `fit_plane_to_fissure` of surface_fitting_optimization.py; those names are not defined.
+`poisson_reconstruction`, the caller of the per-label loop, is in data_processing/poisson_reconstruction.py (on
+`functional.binary_thinning`, csrc/thinning.hip), not here.  Not in scope: `regularize_fissure_segmentations` and
+`fit_plane_to_fissure` of surface_fitting_optimization.py; those names are not defined.
 
 The reference runs open3d on the CPU per label: PCA normals, orient_normals_consistent_tangent_plane(100),
 octree Poisson reconstruction, crop, lung mask.  Here: normals from csrc/pcl_normals.hip (K = 30, no local disambiguation),

@@ -1,8 +1,9 @@
 """`mesh2labelmap_sampling` and `o3d_mesh_to_labelmap` of the reference's data_processing/surface_fitting.py (:19-39,
 :144-169) on `functional.mesh_labelmap_cover`.  `pointcloud_surface_fitting` of that module is mirrored in
 data_processing/pointcloud_surface_fitting.py (with `fit_label_surfaces`, its batched form); it is not defined here.
-`poisson_reconstruction` (it needs sitk.BinaryThinning) and `regularize_fissure_segmentations` are not in scope: those names are
-not defined anywhere in this package.
+`poisson_reconstruction` is mirrored in data_processing/poisson_reconstruction.py (sitk.BinaryThinning is
+`functional.binary_thinning`, csrc/thinning.hip); it is not defined here either.  `regularize_fissure_segmentations`, the file
+I/O around it, is not in scope: that name is not defined anywhere in this package.
 
 The reference draws 10^7 random points on every mesh and writes the label into the cell `floor(point / spacing)` of each.
 That is a Monte Carlo estimate of "the cells the surface passes through", and it misses cells that the surface only clips

@@ -3203,6 +3203,44 @@ def binary_opening(vol, radius):
     return _morph_public(vol, radius, "binary_opening", _bits_opening)
 
 
+def _thin_slice_fits(H, W):
+    words = H * ((W + 63) // 64)
+    if words > _lib.THIN_MAX_WORDS:
+        raise ValueError(f"binary_thinning: a slice of {H} x {W} voxels is {words} words of 64 voxels, at most "
+                         f"{_lib.THIN_MAX_WORDS} (H * ceil(W / 64)) fit in LDS")
+
+
+def _bits_thin(bits, W, want_iterations=False):
+    """one launch on a bit plane (csrc/thinning.hip): every slice thinned in its (y, x) plane until a pair of steps clears
+    nothing -> (thinned plane, (B, D) int32 pair counts or None).  No host read."""
+    B, D, H, _ = bits.shape
+    _thin_slice_fits(H, W)
+    out = torch.empty_like(bits)
+    iters = torch.empty(B, D, dtype=torch.int32, device=bits.device) if want_iterations else None
+    with torch.cuda.device(bits.device):
+        _lib.call("fsg_thin_bits", _p(bits), B, D, H, W, _p(out), _p(iters), _stream())
+    return out, iters
+
+
+def binary_thinning(vol, return_iterations=False):
+    """sitk.BinaryThinning as poisson_reconstruction uses it (data_processing/surface_fitting.py:109): vol (D, H, W) or
+    (B, D, H, W), bool or integer (nonzero = set), any strides -> bool of the same shape; the input is not modified.  The
+    two-sub-iteration thinning of Gonzalez & Woods in the (y, x) plane of every slice, clamped borders: slices never
+    interact, so a sheet that crosses the slices becomes a one-voxel-wide sheet, not a curve.  The rule of csrc/thinning.hip
+    and tests/thinning_oracle.py is the authority, parity with SimpleITK is unpinned.  A slice may hold at most
+    `_lib.THIN_MAX_WORDS` words, H * ceil(W / 64) (ValueError beyond).  return_iterations: also the int32 (D) or (B, D)
+    numbers of step pairs that cleared something, on the device.  One launch between the pack and the unpack, no host read."""
+    v4, squeeze = _binary_volume(vol, "binary_thinning")
+    W = v4.shape[-1]
+    _thin_slice_fits(v4.shape[-2], W)        # before any work
+    with torch.no_grad():
+        bits, iters = _bits_thin(_pack_bits(v4), W, return_iterations)
+        out = _unpack_bits(bits, W)
+    if squeeze:
+        out, iters = out[0], (iters[0] if return_iterations else None)
+    return (out, iters) if return_iterations else out
+
+
 def _cc_bits(bits, W, connectivity):
     """bit plane -> (labels (B, D, H, W) int32, n (B) int32 on the device): no host read"""
     B, D, H, _ = bits.shape

@@ -1083,6 +1083,22 @@ int fsg_edt_sq_f32(const uint64_t *bits, int B, int D, int H, int W, float s0, f
 int fsg_edt_nearest_label(const void *d2, int is_f32, int K, int64_t V, const int32_t *cand, const uint8_t *keep, int32_t *out,
                           fsg_stream_t stream);
 
+/* In-plane binary thinning of a bit plane (csrc/thinning.hip).  Stands where sitk.BinaryThinning stands in the reference's
+ * poisson_reconstruction (data_processing/surface_fitting.py:109, called from train_segmentation_net.py:75-148 and
+ * regularize_fissure_segmentations): the two-sub-iteration thinning of Gonzalez & Woods that ITK's BinaryThinningImageFilter
+ * documents, applied in the (y, x) plane of every slice, neighbours outside a slice clamped to the nearest voxel inside it.  The
+ * rule and its numpy oracle (tests/thinning_oracle.py) are the authority: parity with SimpleITK is unpinned.
+ *
+ * in / out: bit planes (B, D, H, ceil(W / 64)) as above (bits past W are 0 on the way out whatever came in); out may be in.
+ * iterations (B, D) int32 or NULL: per slice, the number of odd + even step pairs that cleared a voxel.
+ * One launch, one workgroup per (item, slice), the slice twice in LDS, the loop to convergence inside the launch (capped at
+ *   H W + 1 pairs).  No atomics, no host read, everything on `stream`: the same input gives the same bits, a slice does not
+ *   depend on its neighbours or its batch.
+ * A slice holds at most fsg_thin_max_words() = 8192 words, H * ceil(W / 64) (512 x 1024 or 1024 x 512 voxels); a larger one, a
+ *   NULL plane or a non-positive dimension is FSG_ERR_ARG. */
+int fsg_thin_max_words(void);
+int fsg_thin_bits(const uint64_t *in, int B, int D, int H, int W, uint64_t *out, int32_t *iterations, fsg_stream_t stream);
+
 /* Voxel patch augmentation and resampling (csrc/spatial.hip).  Stands where ImageDataset.__getitem__ of the reference
  * (data.py:290-327) calls batchgenerators' SpatialTransform + MirrorTransform (augmentations.py:29-49), sitk.Resample
  * (utils/image_ops.py:12-28) and normalize_img (data.py:365-366).  All pointers DEVICE, everything fp32, no atomics, no host

@@ -589,6 +589,108 @@ if "edt" in which:
     if out_path:
         with open(out_path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
+if "thin" in which:
+    # In-plane binary thinning (csrc/thinning.hip): whole `binary_thinning` calls and the thinning launch alone, beside (a) the
+    # torch composition of the same rule on the device (replicate-padded shifted slices, one host read per pair) and (b) the numpy
+    # oracle on the host (tests/thinning_oracle.py; it stands in for ITK, which is not available), in the same run.  Inputs: a
+    # synthetic three-sheet fissure label map, 3-5 voxels thick, as three planes in one launch, and the synthetic two-lung mask
+    # as the deep case.  Then the stage split of a whole poisson_reconstruction.  FSG_THIN_HOST=0 leaves the host runs out.
+    import json, time
+    import numpy as np
+    import morphology_oracle as mo
+    import thinning_oracle as tho
+    from fissure_segmentation_amd.data_processing.poisson_reconstruction import poisson_reconstruction
+    shapes = [tuple(int(v) for v in a.split("x")) for a in os.environ.get("FSG_THIN_SHAPES", "128x128x128,256x256x320").split(",")]
+    with_host = os.environ.get("FSG_THIN_HOST", "1") != "0"
+    host_max = int(os.environ.get("FSG_THIN_HOST_MAX_VOXELS", 128 ** 3))   # numpy needs seconds per step on 2 10^7 voxels
+
+    def peak(fn):
+        torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = fn(); torch.cuda.synchronize()
+        del out
+        return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+    def three_sheets(shape):
+        D, H, W = shape
+        z, y, x = np.meshgrid(np.arange(D), np.arange(H), np.arange(W), indexing="ij", sparse=True)
+        lab = np.zeros(shape, np.int64)
+        lab[(np.abs(y - (0.35 * H + 0.2 * x + 0.1 * z + 2 * np.sin(x / 9.0))) <= 1.5) & (x < W // 2 - 4) & (x > 4)] = 1
+        lab[(np.abs(y - (0.30 * H + 0.25 * (x - W / 2) + 0.1 * z)) <= 2.0) & (x > W // 2 + 4) & (x < W - 4)] = 2
+        lab[(np.abs(y - (0.75 * H - 0.2 * (x - W / 2) - 0.05 * z)) <= 2.5) & (x > W // 2 + 4) & (x < W - 4)] = 3
+        return lab
+
+    def torch_thin(v):
+        """the rule composed from torch operations: v (S, H, W) bool -> (thinned, pairs per slice); one host read per pair"""
+        pad = torch.nn.functional.pad
+        img = v.to(torch.uint8)
+        pairs = torch.zeros(img.shape[0], dtype=torch.int32, device=img.device)
+        H, W = img.shape[-2:]
+        for _ in range(H * W + 1):
+            cleared = torch.zeros(img.shape[0], dtype=torch.bool, device=img.device)
+            for odd in (True, False):
+                p = pad(img[:, None].float(), (1, 1, 1, 1), mode="replicate")[:, 0].to(torch.uint8)
+                n8 = [p[:, 1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy, dx in tho.OFFSETS]
+                p2, p3, p4, p5, p6, p7, p8, p9 = n8
+                cnt = sum(q.to(torch.int32) for q in n8)
+                trans = sum(((n8[k] == 0) & (n8[(k + 1) % 8] == 1)).to(torch.int32) for k in range(8))
+                cd = ((p2 & p4 & p6) == 0) & ((p4 & p6 & p8) == 0) if odd else ((p2 & p4 & p8) == 0) & ((p2 & p6 & p8) == 0)
+                mark = (img == 1) & (cnt >= 2) & (cnt <= 6) & (trans == 1) & cd
+                cleared |= mark.flatten(1).any(1)
+                img = img & ~mark.to(torch.uint8)
+            if not bool(cleared.any()):                              # the host read
+                break
+            pairs += cleared
+        return img.bool(), pairs
+
+    lines = []
+    for shape in shapes:
+        D, H, W = shape
+        lab = three_sheets(shape)
+        lung = mo.lung_volume(shape)[0]
+        rec = dict(kernel="in-plane binary thinning on bit planes", shape="x".join(map(str, shape)), voxels=D * H * W)
+        cases = (("sheets3", torch.from_numpy(np.stack([lab == f for f in (1, 2, 3)])).to(dev)),
+                 ("lungs", torch.from_numpy(lung).to(dev)[None]))
+        for cname, t in cases:
+            bits = F._pack_bits(t)
+            out, it = F.binary_thinning(t, return_iterations=True)
+            rec[f"{cname}_pairs_max"], rec[f"{cname}_pairs_mean"] = int(it.max()), round(float(it.float().mean()), 2)
+            rec[f"{cname}_voxels_in"], rec[f"{cname}_voxels_out"] = int(t.sum()), int(out.sum())
+            rec[f"{cname}_compulsory_MB"] = round(2 * t.numel() / 1e6, 1)       # a byte in and a byte out around the 1-bit plane
+            med, mn = timeit(lambda: F._bits_thin(bits, W), iters=20, warm=3)
+            rec[f"{cname}_launch_us"] = round(med, 1)
+            med, mn = timeit(lambda: F.binary_thinning(t), iters=20, warm=3)
+            rec[f"{cname}_hip_us"] = round(med, 1)
+            rec[f"{cname}_hip_peak_MiB"] = peak(lambda: F.binary_thinning(t))
+            flat = t.reshape(-1, H, W)
+            ref, rp = torch_thin(flat)
+            rec[f"{cname}_equals_torch"] = bool(torch.equal(ref.reshape(t.shape), out) and torch.equal(rp.reshape(it.shape), it))
+            med, mn = timeit(lambda: torch_thin(flat), iters=3, warm=1)
+            rec[f"{cname}_torch_us"] = round(med, 1)
+            rec[f"{cname}_torch_peak_MiB"] = peak(lambda: torch_thin(flat))
+            rec[f"{cname}_speedup_vs_torch"] = round(rec[f"{cname}_torch_us"] / rec[f"{cname}_hip_us"], 1)
+            del ref, rp
+            print("thin: %s %s done" % (rec["shape"], cname), file=sys.stderr, flush=True)
+            if with_host and D * H * W <= host_max:
+                m = t.cpu().numpy()
+                t0 = time.perf_counter(); want, wp = tho.thin(m)
+                rec[f"{cname}_numpy_us"] = round((time.perf_counter() - t0) * 1e6, 1)
+                rec[f"{cname}_speedup_vs_numpy"] = round(rec[f"{cname}_numpy_us"] / rec[f"{cname}_hip_us"], 1)
+                rec[f"{cname}_equals_numpy"] = bool(np.array_equal(out.cpu().numpy(), want) and np.array_equal(it.cpu().numpy(), wp))
+                del want, wp
+        if shape == shapes[-1]:
+            labels = torch.from_numpy(lab).to(dev)
+            mask = torch.ones(shape, dtype=torch.bool, device=dev)
+            poisson_reconstruction(labels, mask, (1.0, 1.0, 1.0))                                    # warm-up
+            _, meshes, times = poisson_reconstruction(labels, mask, (1.0, 1.0, 1.0), return_times=True)
+            rec["poisson_reconstruction_stage_s"] = {k: round(v, 4) for k, v in times.items()}
+            rec["poisson_reconstruction_faces"] = meshes.num_faces_per_mesh().tolist()
+        print("THIN " + json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    out_path = os.environ.get("FSG_THIN_BENCH_OUT")
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
 if "mesh" in which:
     # mesh regularisers, surface sampler and the whole default mesh loss (csrc/mesh.hip) beside the torch composition of the
     # same math on the same device (the oracle's fp32 code, tests/mesh_oracle.py, batched over the shared face list), value +
