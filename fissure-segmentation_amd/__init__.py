@@ -30,6 +30,7 @@ def install_reference_aliases():
         "losses.dgssm_loss": ".losses.dgssm_loss", "models.dg_ssm": ".models.dg_ssm",
         "shape_model": ".shape_model", "shape_model.ssm": ".shape_model.ssm", "metrics": ".metrics",
         "shape_model.point_cloud_registration": ".shape_model.point_cloud_registration",
+        "shape_model.generate_corresponding_points": ".shape_model.generate_corresponding_points",
         "data_processing.foerstner": ".data_processing.foerstner", "data_processing.point_features": ".data_processing.point_features",
         "data_processing.keypoint_extraction": ".data_processing.keypoint_extraction",
         "data_processing.fissure_enhancement": ".data_processing.fissure_enhancement",

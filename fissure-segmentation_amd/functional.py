@@ -2112,6 +2112,143 @@ def cpd_estep(X, TY, sigma2, w=0.):
     return P1, Pt1, PX, Np
 
 
+# ------------------------------------------------------------------ k-means (shape_model/generate_corresponding_points.py:44-48)
+KMEANS_CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
+
+
+def _kmeans_args(points, centroids, who):
+    if points.dim() != 3 or points.shape[2] != 3 or centroids.dim() != 3 or centroids.shape[2] != 3 \
+            or centroids.shape[0] != points.shape[0]:
+        raise ValueError(f"{who}: expected points (B,n,3) and centroids (B,K,3), got {tuple(points.shape)} and "
+                         f"{tuple(centroids.shape)}")
+    B, n, _ = points.shape
+    K = centroids.shape[1]
+    if n < 1 or n > _lib.KMEANS_MAX_POINTS:
+        raise ValueError(f"{who}: n={n} points per item, the kernel serves 1 <= n <= {_lib.KMEANS_MAX_POINTS}")
+    if not 1 <= K <= min(n, _lib.KMEANS_MAX_K):
+        raise ValueError(f"{who}: K={K} clusters, the kernel serves 1 <= K <= min(n, {_lib.KMEANS_MAX_K}) (n={n})")
+    _need_gpu(points, centroids)
+    if points.device != centroids.device:
+        raise ValueError(f"{who}: points are on {points.device}, centroids on {centroids.device}")
+    return B, n, K
+
+
+class _KMeansRun:
+    """the device state of one run: workspace (accumulators, scales, threshold, active flags), labels and the per-item outputs"""
+
+    def __init__(self, points, centroids, tol, prev_labels=None):
+        B, n, K = self.dims = points.shape[0], points.shape[1], centroids.shape[1]
+        dev = self.dev = points.device
+        self.points, self.centroids = points, centroids
+        self.labels = torch.full((B, n), -1, dtype=torch.int32, device=dev) if prev_labels is None else prev_labels
+        self.counts = torch.empty(B, K, dtype=torch.int32, device=dev)
+        self.stats = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+        self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self.ws = _lib.workspace("fsg_kmeans", B, n, K, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("fsg_kmeans_prepare_f32", _p(points), _p(centroids), B, n, K, float(tol), _p(self.ws), self.ws.numel(),
+                      _stream())
+
+    def launch(self, entry):
+        B, n, K = self.dims
+        with torch.cuda.device(self.dev):
+            _lib.call(entry, _p(self.points), _p(self.centroids), _p(self.labels), B, n, K, _p(self.ws), self.ws.numel(),
+                      _p(self.counts), _p(self.stats), _p(self.info), _stream())
+
+
+def kmeans_step(points, centroids, prev_labels=None):
+    """One Lloyd iteration of B independent k-means problems (fsg_kmeans_step_f32): points (B,n,3), centroids (B,K,3),
+    prev_labels (B,n) integer or None -> (labels (B,n) int32, new_centroids (B,K,3) fp32, counts (B,K) int32, inertia (B,) fp64,
+    n_changed (B,) int32).
+
+    labels[i] = argmin_k ((dx dx + dy dy) + dz dz) in fp32, the lowest k on ties; inertia is the sum of those squared distances,
+    that is the inertia of `centroids`, not of new_centroids; n_changed counts labels that differ from prev_labels (all n
+    without them); a cluster without points keeps its centroid (counts tells which).  Sums are int64 fixed-point: the same
+    inputs give the same bits, whatever else is in the batch.  The inputs are not modified.  Not differentiable."""
+    B, n, K = _kmeans_args(points, centroids, "kmeans_step")
+    if B == 0:
+        raise ValueError("kmeans_step: empty batch")
+    if prev_labels is not None:
+        _need_gpu(prev_labels)
+        if tuple(prev_labels.shape) != (B, n) or prev_labels.is_floating_point():
+            raise ValueError(f"kmeans_step: prev_labels must be integers of shape {(B, n)}, got {tuple(prev_labels.shape)} "
+                             f"{prev_labels.dtype}")
+    with torch.no_grad():
+        prev = None if prev_labels is None else prev_labels.to(torch.int32, copy=True).contiguous()
+        run = _KMeansRun(_f32c(points), _f32c(centroids).clone(), 0., prev)
+        run.launch("fsg_kmeans_step_f32")
+    return run.labels, run.centroids, run.counts, run.stats[:, 0].clone(), run.info[:, 0].clone()
+
+
+def kmeans(points, n_clusters=None, init='fps', max_iter=300, tol=1e-4, start=0, return_info=False):
+    """Lloyd's k-means of B independent 3-D clouds on the GPU: points (n,3) or (B,n,3) -> (centroids (B,K,3) fp32, labels (B,n)
+    int64, inertia (B,) fp64, n_iter (B,) int32); a 2-D input comes back without the batch axis.
+
+    `init` is 'fps' -- farthest point sampling (fsg_fps_f32) of n_clusters points of every item, started at row `start`; the
+    selected rows are the first centres -- or a tensor (B,K,3) / (K,3) of explicit centres (then n_clusters may be omitted).
+    There is no random seeding and no n_init: the run is deterministic, bit for bit, and an item's result does not depend on
+    the batch it is in.  An item stops when no label changes or when the summed squared centre shift is at most
+    tol * mean(var(points, axis=0)) (sklearn's rule) or after max_iter iterations, and is frozen from then on; the host looks at
+    one "any item active" word every KMEANS_CHECK_EVERY iterations.  A cluster that loses all its points keeps its centre
+    (scipy.cluster.vq.kmeans2's behaviour; sklearn relocates it).  The returned labels and inertia are those OF the returned
+    centres (one last assign).  `return_info` appends a dict with `counts` (B,K) and `n_empty` (B,) of that assignment."""
+    if not torch.is_tensor(points):
+        raise TypeError(f"kmeans: points must be a torch tensor on the GPU, got {type(points).__name__}")
+    squeeze = points.dim() == 2
+    if squeeze:
+        points = points[None]
+    if points.dim() != 3 or points.shape[2] != 3 or not points.is_floating_point():
+        raise ValueError(f"kmeans: expected floating-point points (n,3) or (B,n,3), got {tuple(points.shape)} {points.dtype}")
+    B, n, _ = points.shape
+    if B == 0:
+        raise ValueError("kmeans: empty batch")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
+        raise ValueError(f"kmeans: max_iter must be a non-negative integer, got {max_iter!r}")
+    if not tol >= 0:
+        raise ValueError(f"kmeans: tol must not be negative, got {tol!r}")
+    if torch.is_tensor(init):
+        cen = init[None] if init.dim() == 2 else init
+        if n_clusters is not None and cen.dim() == 3 and cen.shape[1] != n_clusters:
+            raise ValueError(f"kmeans: init holds {cen.shape[1]} centres, n_clusters={n_clusters}")
+        _kmeans_args(points, cen, "kmeans")
+    elif isinstance(init, str) and init == 'fps':
+        if n_clusters is None:
+            raise ValueError("kmeans: init='fps' needs n_clusters")
+        K = int(n_clusters)
+        if not 1 <= K <= min(n, _lib.KMEANS_MAX_K):
+            raise ValueError(f"kmeans: n_clusters={n_clusters}, the kernel serves 1 <= K <= min(n, {_lib.KMEANS_MAX_K}) (n={n})")
+        if n > _lib.KMEANS_MAX_POINTS:
+            raise ValueError(f"kmeans: n={n} points per item, the kernel serves n <= {_lib.KMEANS_MAX_POINTS}")
+        if not 0 <= start < n:
+            raise ValueError(f"kmeans: start={start} is no row of a cloud of {n} points")
+        _need_gpu(points)
+    else:
+        raise ValueError(f"kmeans: init must be 'fps' or a tensor of centres, got {init!r}")
+    with torch.no_grad():
+        pc = _f32c(points)
+        if torch.is_tensor(init):
+            cen = _f32c(cen).clone()
+        else:
+            # the sampling kernel starts a segment at its first row: rotate every cloud so that row `start` is there
+            rolled = torch.roll(pc, -start, 1).reshape(B * n, 3) if start else pc.reshape(B * n, 3)
+            seg = torch.arange(1, B + 1, dtype=torch.int32, device=pc.device)
+            rows = fps(rolled, seg * n, seg * K, B * K).long().view(B, K)    # rows of the packed, rotated clouds
+            rows = (rows - (seg.long() - 1)[:, None] * n + start) % n
+            cen = torch.gather(pc, 1, rows[:, :, None].expand(B, K, 3)).contiguous()
+        run = _KMeansRun(pc, cen, tol)
+        for it in range(max_iter):
+            if it and it % KMEANS_CHECK_EVERY == 0 and not bool(run.info[:, 3].any()):   # the only synchronisation of the loop
+                break
+            run.launch("fsg_kmeans_step_f32")
+        run.launch("fsg_kmeans_assign_f32")
+        out = [run.centroids, run.labels.long(), run.stats[:, 0].clone(), run.info[:, 2].clone()]
+        extra = {"counts": run.counts, "n_empty": run.info[:, 1].clone()}
+    if squeeze:
+        out = [t[0] for t in out]
+        extra = {k: v[0] for k, v in extra.items()}
+    return (*out, extra) if return_info else tuple(out)
+
+
 # ------------------------------------------------------------------ segmentation loss (losses/nnu_loss.py:6-19)
 class _NNULoss(torch.autograd.Function):
     @staticmethod

@@ -978,6 +978,34 @@ int fsg_cpd_estep_f32(const float *X, int64_t x_batch_stride, const float *TY, c
                       float *P1, float *Pt1, float *PX, float *Np, void *workspace, size_t workspace_bytes,
                       fsg_stream_t stream);
 
+/* Lloyd's k-means on 3-D points, batched and bit-reproducible (csrc/kmeans.hip).  Serves the 'kmeans' mode of the reference's
+ * data_set_correspondences, shape_model/generate_corresponding_points.py:44-48, which pools the registered clouds of all
+ * instances of one object and calls sklearn.cluster.k_means on the CPU, one object at a time.  B independent items:
+ *   points (B, n, 3) fp32, centroids (B, K, 3) fp32, labels (B, n) int32, all DEVICE and contiguous; coordinates finite.
+ *   1 <= K <= min(n, 4096), n <= 2^24, B <= 65535.  workspace: fsg_kmeans_workspace_bytes(B, n, K) bytes, 8-byte aligned; it
+ *   carries a run (accumulators, scales, threshold, active flag, iteration count per item) from `prepare` through the steps.
+ * prepare  once per run: the fixed-point scales of every item from its largest |coordinate| over points and centroids, the
+ *   stopping threshold tol * (mean over the three axes of the variance of the item's points) (sklearn's rule), zeroed
+ *   accumulators, every item active with iteration count 0.
+ * step     one iteration, two launches, nothing read on the host.  Assign: label = argmin_k ((dx dx + dy dy) + dz dz) in fp32
+ *   in that order, the lowest k on ties; coordinates and squared distances are summed per cluster as int64 fixed-point numbers
+ *   (so the sums do not depend on any order, nor on the rest of the batch).  Finalize: centroid = sum / count in fp64 rounded
+ *   to fp32, written over `centroids`; an empty cluster keeps its centroid (scipy.cluster.vq.kmeans2's rule, not sklearn's
+ *   relocation); an item stops when no label differs from the `labels` it found (-1 everywhere before the first step) or when
+ *   the summed squared centroid shift is <= its threshold.  A stopped item is frozen: later steps leave its centroids, labels,
+ *   outputs and iteration count alone.
+ * assign   labels, counts and inertia OF the given centroids for every item, frozen or not; centroids are not written.
+ * Outputs of step and assign, each may be NULL: counts (B, K) int32; stats (B, 2) fp64 = inertia (the sum of the squared
+ *   distances of this assignment), squared centroid shift; info (B, 4) int32 = labels changed, empty clusters, iterations
+ *   run, active. */
+size_t fsg_kmeans_workspace_bytes(int B, int n, int K);
+int fsg_kmeans_prepare_f32(const float *points, const float *centroids, int B, int n, int K, double tol, void *workspace,
+                           size_t workspace_bytes, fsg_stream_t stream);
+int fsg_kmeans_step_f32(const float *points, float *centroids, int32_t *labels, int B, int n, int K, void *workspace,
+                        size_t workspace_bytes, int32_t *counts, double *stats, int32_t *info, fsg_stream_t stream);
+int fsg_kmeans_assign_f32(const float *points, const float *centroids, int32_t *labels, int B, int n, int K, void *workspace,
+                          size_t workspace_bytes, int32_t *counts, double *stats, int32_t *info, fsg_stream_t stream);
+
 /* Random-walker lobe filling and lobes-to-fissures (csrc/random_walk.hip).  Volumes are (B, D, H, W), DEVICE, contiguous.
  *
  * The graph of compute_laplace_matrix (data_processing/random_walk.py:15-77) is never a matrix: nodes are the voxels, edges

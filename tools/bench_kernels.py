@@ -1416,3 +1416,126 @@ if "spatial" in which:
     out_path = os.environ.get("FSG_SPATIAL_BENCH_OUT", os.path.join(ROOT, "profiles", "spatial_bench.jsonl"))
     with open(out_path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+if "kmeans" in which:
+    # Batched k-means (csrc/kmeans.hip) and data_set_correspondences.  One iteration and a whole run at the reference's sizes
+    # (pooled clouds of 100 / 1000 instances of 1024 points, K = 1024), beside, in the same run, the torch composition on the
+    # device (functional.knn_segment with k = 1 for the assignment, index_add_ for the sums) and, on the host for item 0 only,
+    # scipy.cluster.vq.kmeans2 and sklearn.cluster.k_means from the same centres (FSG_KMEANS_HOST=0 leaves the host out);
+    # peak extra memory; final inertia of every path; a whole data_set_correspondences in both modes against the per-pair
+    # loop of the same calls.  Writes profiles/kmeans_bench.jsonl.
+    import json
+    import time
+    import numpy as np
+    import kmeans_oracle as ko
+    from fissure_segmentation_amd.shape_model import generate_corresponding_points as gcp
+    lines = []
+    HOST = os.environ.get("FSG_KMEANS_HOST", "1") != "0"
+
+    def emit_line(rec):
+        lines.append(json.dumps(rec))
+        print("KMEANS " + lines[-1], flush=True)
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            keep = fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+            del keep
+        return round(statistics.median(ts), 1)
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 1)
+
+    def torch_step(pts, cen):
+        """one Lloyd iteration out of existing device pieces: the segment kNN with k = 1, then index_add_ (float atomics)"""
+        B, n, K = pts.shape[0], pts.shape[1], cen.shape[1]
+        seg = torch.arange(1, B + 1, dtype=torch.int32, device=pts.device)
+        idx, d2 = F.knn_segment(1, cen.reshape(B * K, 3), pts.reshape(B * n, 3), seg * K, seg * n)
+        flat = idx.reshape(-1).long()
+        sums = torch.zeros(B * K, 3, device=pts.device).index_add_(0, flat, pts.reshape(B * n, 3))
+        cnt = torch.zeros(B * K, device=pts.device).index_add_(0, flat, torch.ones(B * n, device=pts.device))
+        new = torch.where(cnt[:, None] > 0, sums / cnt[:, None].clamp_min(1), cen.reshape(B * K, 3)).view(B, K, 3)
+        return new, d2.view(B, n).double().sum(1)
+
+    def torch_run(pts, cen, iters):
+        for _ in range(iters):
+            cen, _ = torch_step(pts, cen)
+        return cen, torch_step(pts, cen)[1]
+
+    for (B, I, P) in [(3, 100, 1024), (5, 1000, 1024)]:
+        n, K = I * P, P
+        pts = torch.from_numpy(np.stack([ko.pooled(I, P, 40 + b) for b in range(B)])).to(dev)
+        t_fps = wall(lambda: F.kmeans(pts, K, max_iter=0), reps=1)
+        c0 = F.kmeans(pts, K, max_iter=0)[0]
+        print(f"KMEANS B={B} n={n} K={K}: farthest point sampling + one assign {t_fps} us", flush=True)
+        step_us = timeit(lambda: F.kmeans_step(pts, c0), iters=10, warm=2)
+        fsg._lib.start_timing()
+        for _ in range(5):
+            F.kmeans_step(pts, c0)
+        entry = {k: round(1e3 * sorted(v)[len(v) // 2], 1) for k, v in fsg._lib.stop_timing().items()}
+        comp_step_us = timeit(lambda: torch_step(pts, c0), iters=5, warm=1)
+        cen, lab, inertia, n_iter = F.kmeans(pts, init=c0)
+        iters = int(n_iter.max())
+        run_us = wall(lambda: F.kmeans(pts, init=c0), reps=3)
+        comp_run_us = wall(lambda: torch_run(pts, c0, iters), reps=1)
+        comp_inertia = torch_run(pts, c0, iters)[1]
+        rec = dict(kernel="kmeans", B=B, n=n, K=K, fps_init_plus_assign_us=t_fps, step_us=round(step_us[0], 1),
+                   step_min_us=round(step_us[1], 1), entry_us=entry, torch_composition_step_us=round(comp_step_us[0], 1),
+                   iterations=n_iter.tolist(), run_us=run_us, torch_composition_run_same_iterations_us=comp_run_us,
+                   peak_extra_MiB=peak_extra(lambda: F.kmeans(pts, init=c0)),
+                   torch_composition_peak_extra_MiB=peak_extra(lambda: torch_run(pts, c0, 1)),
+                   initial_inertia=F.kmeans_step(pts, c0)[3].tolist(), final_inertia=inertia.tolist(),
+                   torch_composition_final_inertia=comp_inertia.tolist())
+        if HOST:
+            from scipy.cluster.vq import kmeans2, vq
+            p0, h0 = pts[0].cpu().numpy().astype(np.float64), c0[0].cpu().numpy().astype(np.float64)
+            t0 = time.perf_counter()
+            kmeans2(p0, h0, iter=2, minit="matrix", missing="warn")
+            rec["scipy_kmeans2_iteration_us_item0"] = round((time.perf_counter() - t0) * 1e6 / 2, 1)
+            print("KMEANS scipy done", flush=True)
+            try:
+                from sklearn.cluster import k_means
+                t0 = time.perf_counter()
+                sc, sl, si, sn = k_means(p0, n_clusters=K, init=h0, n_init=1, max_iter=iters, tol=1e-4, return_n_iter=True)
+                rec.update(sklearn_run_us_item0=round((time.perf_counter() - t0) * 1e6, 1), sklearn_iterations_item0=int(sn),
+                           sklearn_final_inertia_item0=float(si))
+            except ImportError:
+                rec["sklearn"] = "not installed"
+        emit_line(rec)
+        del pts, c0, cen, lab
+
+    inp = ko.correspondence_inputs(seed=77, instances=100, objects=2, P=1024, grid=32)
+    t = lambda a: torch.from_numpy(a).to(dev)   # noqa: E731
+    args = lambda: (t(inp["fixed_pcs"]), inp["meshes"], t(inp["moving_pcs"]), [dict(d) for d in inp["transforms"]],   # noqa: E731
+                    t(inp["moved_pcs"]), t(inp["displacements"]), None, None)
+
+    def per_pair(mode):
+        """the reference's double loop over the same public calls: one object and one instance at a time"""
+        fixed, meshes, moving, tr, moved, disp = args()[:6]
+        s, R, tl = gcp._transforms(tr, len(tr), dev)
+        O, I = fixed.shape[0], moved.shape[0]
+        cen = fixed if mode == "simple" else torch.stack(
+            [F.kmeans(moved[:, o].reshape(-1, 3), n_clusters=fixed.shape[1])[0].double() for o in range(O)])
+        return [gcp.object_correspondences(cen[o], moved[i:i + 1, o], disp[i:i + 1, o], moving[i:i + 1, o], [meshes[i][o]],
+                                           s[i:i + 1], R[i:i + 1], tl[i:i + 1]) for o in range(O) for i in range(I)]
+
+    for mode in ("simple", "kmeans"):
+        gcp.data_set_correspondences(*args(), mode=mode, show=False)
+        batched = wall(lambda: gcp.data_set_correspondences(*args(), mode=mode, show=False), reps=3)
+        looped = wall(lambda: per_pair(mode), reps=2)
+        emit_line(dict(kernel="data_set_correspondences", mode=mode, instances=100, objects=2, points=1024, mesh_faces=2 * 31 * 31,
+                       batched_us=batched, per_pair_loop_us=looped, speedup=round(looped / batched, 2),
+                       peak_extra_MiB=peak_extra(lambda: gcp.data_set_correspondences(*args(), mode=mode, show=False))))
+    out_path = os.environ.get("FSG_KMEANS_BENCH_OUT", os.path.join(ROOT, "profiles", "kmeans_bench.jsonl"))
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
