@@ -145,6 +145,8 @@ SIGNATURES = {
     "fsg_kmeans_prepare_f32": ([_P, _P, _I, _I, _I, ctypes.c_double, _P, ctypes.c_size_t, _P], _I),
     "fsg_kmeans_step_f32": ([_P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P], _I),
     "fsg_kmeans_assign_f32": ([_P, _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P], _I),
+    "fsg_sample_elimination_workspace_bytes": ([_I, _I], ctypes.c_size_t),
+    "fsg_sample_elimination_f32": ([_P, _P, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_random_walk_workspace_bytes": ([_I, _I, _I, _I, _I], ctypes.c_size_t),
     "fsg_random_walk_prep": ([_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P], _I),
     "fsg_random_walk_iterate": ([_P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, ctypes.c_size_t, _P, _P, _P], _I),
@@ -209,6 +211,7 @@ LABEL_U8, LABEL_I32, LABEL_I64 = 0, 1, 2   # include/fsg_hip.h: FSG_LABEL_*
 PCL_NORMALS_MAX_K = 64   # include/fsg_hip.h: fsg_pcl_normals_f32 (what fsg_knn_segment_f32 can deliver)
 ORIENT_MAX_POINTS = 1 << 20   # include/fsg_hip.h: fsg_orient_normals_f32 (20 bits per endpoint in the edge key)
 KMEANS_MAX_K, KMEANS_MAX_POINTS = 4096, 1 << 24   # csrc/kmeans.hip: kMaxK (LDS accumulators), the index range of a point
+SAMPLE_ELIMINATION_MAX_POINTS = 16384   # csrc/poisson_disk.hip: kMaxM (the weights of one item fill LDS)
 RW_BINARY, RW_INTENSITY, RW_MAX_LABELS = 0, 1, 8   # include/fsg_hip.h: FSG_RW_*; csrc/random_walk.hip builds K = 1..8
 KNN_FIX_DIAG, KNN_DROP_FIRST, KNN_FORCE_ROWS, KNN_FORCE_MFMA, KNN_MAX_K = 1, 2, 4, 8, 64
 # debug / cross-check bits of the kNN `flags` (csrc/knn_internal.h has the meanings; any other bit is rejected by the library)

@@ -83,6 +83,31 @@ static __device__ __forceinline__ float wave_max_nonneg_bcast_f(float v) {
     FSG_DPP_LADDER(FSG_DPP_FMAX)
     return wave_lane63_f(v);
 }
+// one step of the maximum of a 64-bit key over the 64 lanes on the DPP network (6 VALU steps instead of 6 LDS-crossbar
+// shuffles): swaps inside the quads, mirrors inside the rows, then the row totals travel down
+static __device__ __forceinline__ u64 dpp_max_step(u64 k, const int ctrl) {
+    const int lo = (int)(unsigned)k, hi = (int)(unsigned)(k >> 32);
+    int olo, ohi;
+    switch (ctrl) {   // the control word must be a compile-time constant
+        case 0: olo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xf, 0xf, false); break;
+        case 1: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xf, 0xf, false); break;
+        case 2: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x141, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x141, 0xf, 0xf, false); break;
+        case 3: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xf, 0xf, false); break;
+        case 4: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xa, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xa, 0xf, false); break;
+        default: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x143, 0xc, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x143, 0xc, 0xf, false); break;
+    }
+    const u64 o = ((u64)(unsigned)ohi << 32) | (unsigned)olo;
+    return o > k ? o : k;
+}
+// maximum of an unsigned 64-bit key over the 64 lanes, returned to EVERY lane (scalar reads of lane 63).  With the value in
+// the high bits and (a constant - index) in the low bits of the key this is an arg-max whose ties go to the lowest index.
+static __device__ __forceinline__ u64 wave_max_u64_bcast(u64 k) {
+#pragma unroll
+    for (int st = 0; st < 6; ++st) k = dpp_max_step(k, st);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), 63);
+    return ((u64)hi << 32) | lo;
+}
 // sum of one int per thread over a workgroup of NT threads, and each thread's exclusive prefix; `red` holds NT / 64 ints
 template <int NT>
 static __device__ __forceinline__ int block_excl_scan(int c, int *red, int &total) {

@@ -51,31 +51,11 @@ __global__ __launch_bounds__(BLOCK) void knn_segment_kernel(const float *__restr
         }
 }
 
-// wave arg-max of a 64-bit key on the DPP network (6 VALU steps instead of 6 LDS-crossbar shuffles); the result is valid in
-// lanes 48..63.  Key = float bits of a non-negative value << 32 | (0x7fffffff - index): larger value wins, lower index
-// on ties.
-__device__ __forceinline__ unsigned long long dpp_max_step(unsigned long long k, const int ctrl, const int row_mask) {
-    const int lo = (int)(unsigned)k, hi = (int)(unsigned)(k >> 32);
-    int olo, ohi;
-    switch (ctrl) {   // the control word must be a compile-time constant
-        case 0: olo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xf, 0xf, false); break;
-        case 1: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xf, 0xf, false); break;
-        case 2: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x141, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x141, 0xf, 0xf, false); break;
-        case 3: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xf, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xf, 0xf, false); break;
-        case 4: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xa, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xa, 0xf, false); break;
-        default: olo = __builtin_amdgcn_update_dpp(lo, lo, 0x143, 0xc, 0xf, false); ohi = __builtin_amdgcn_update_dpp(hi, hi, 0x143, 0xc, 0xf, false); break;
-    }
-    (void)row_mask;
-    const unsigned long long o = ((unsigned long long)(unsigned)ohi << 32) | (unsigned)olo;
-    return o > k ? o : k;
-}
+// wave arg-max on the DPP network (wave_max_u64_bcast).  Key = float bits of a non-negative value << 32 | (0x7fffffff -
+// index): larger value wins, lower index on ties.
 __device__ __forceinline__ unsigned long long wave_argmax_key(float bv, int bj) {
-    unsigned long long k = bv >= 0.f ? (((unsigned long long)__float_as_uint(bv) << 32) | (unsigned)(0x7fffffff - bj)) : 0ull;
-#pragma unroll
-    for (int st = 0; st < 6; ++st) k = dpp_max_step(k, st, 0);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, 63);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), 63);
-    return ((unsigned long long)hi << 32) | lo;   // wave-uniform
+    const unsigned long long k = bv >= 0.f ? (((unsigned long long)__float_as_uint(bv) << 32) | (unsigned)(0x7fffffff - bj)) : 0ull;
+    return wave_max_u64_bcast(k);   // wave-uniform
 }
 
 // Farthest point sampling of one segment by one WORKGROUP of FW waves (segments up to 64*FW*PPL points): the segment's points

@@ -2249,6 +2249,68 @@ def kmeans(points, n_clusters=None, init='fps', max_iter=300, tol=1e-4, start=0,
     return (*out, extra) if return_info else tuple(out)
 
 
+# ------------------------------------------------------------------ weighted sample elimination (open3d's sample_points_poisson_disk)
+def _per_item_radius(v, B, dev, name):
+    """a scalar or a (B,) tensor / sequence -> (B,) fp32 on `dev`"""
+    if torch.is_tensor(v):
+        _need_gpu(v)
+        if v.numel() not in (1, B) or v.dim() > 1 or not v.is_floating_point():
+            raise ValueError(f"sample_elimination: {name} must be a scalar or a floating-point ({B},) tensor, got "
+                             f"{tuple(v.shape)} {v.dtype}")
+        return v.detach().to(device=dev, dtype=torch.float32).reshape(-1).expand(B)
+    t = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+    if t.numel() not in (1, B):
+        raise ValueError(f"sample_elimination: {name} must be a scalar or hold one value per item ({B}), got {t.numel()}")
+    return t.to(torch.float32).to(dev).expand(B)
+
+
+def sample_elimination(points, n_keep, r_max, r_min, return_order=False):
+    """Weighted sample elimination (Yuksel 2015) of B independent 3-D clouds on the GPU (fsg_sample_elimination_f32): points
+    (M,3) or (B,M,3) -> keep (B,n_keep) int64, the surviving rows in ascending order [, order (B, M - n_keep) int64, the rows in
+    the order they were removed]; a 2-D input comes back without the batch axis.
+
+    r_max (the paper's 2 r_max: samples closer than it are neighbours) and r_min are scalars or (B,); tensors stay on the
+    device (a Python number is copied there: inside a graph capture pass device tensors).  Pair weight, in fp32:
+    d = max(|p_i - p_j|, r_min), w = max(1 - d / r_max, 0)^8, quantised to rint(w 2^24); a
+    sample's weight is the integer sum over its alive neighbours; every round removes the heaviest alive sample, the lowest row
+    on ties, and lowers its neighbours' weights.  r_max <= 0, or nobody within r_max of anybody: rows leave in index order.
+    Deterministic bit for bit, and an item's result does not depend on the batch it is in.  No host synchronisation.  Not
+    differentiable."""
+    if not torch.is_tensor(points):
+        raise TypeError(f"sample_elimination: points must be a torch tensor on the GPU, got {type(points).__name__}")
+    squeeze = points.dim() == 2
+    if squeeze:
+        points = points[None]
+    if points.dim() != 3 or points.shape[2] != 3 or not points.is_floating_point():
+        raise ValueError(f"sample_elimination: expected floating-point points (M,3) or (B,M,3), got {tuple(points.shape)} "
+                         f"{points.dtype}")
+    B, M, _ = points.shape
+    if B == 0:
+        raise ValueError("sample_elimination: empty batch")
+    if B > 65535:
+        raise ValueError(f"sample_elimination: B={B} items, the kernel serves B <= 65535")
+    if not 1 <= M <= _lib.SAMPLE_ELIMINATION_MAX_POINTS:
+        raise ValueError(f"sample_elimination: M={M} points per item, the kernel serves 1 <= M <= "
+                         f"{_lib.SAMPLE_ELIMINATION_MAX_POINTS}")
+    if isinstance(n_keep, bool) or not isinstance(n_keep, int) or not 1 <= n_keep <= M:
+        raise ValueError(f"sample_elimination: n_keep must be an integer with 1 <= n_keep <= M={M}, got {n_keep!r}")
+    _need_gpu(points)
+    dev = points.device
+    with torch.no_grad():
+        radii = torch.stack([_per_item_radius(r_max, B, dev, "r_max"), _per_item_radius(r_min, B, dev, "r_min")], 1).contiguous()
+        pc = _f32c(points)
+        keep = torch.empty(B, n_keep, dtype=torch.int32, device=dev)
+        order = torch.empty(B, M - n_keep, dtype=torch.int32, device=dev) if return_order else None
+        ws = _lib.workspace("fsg_sample_elimination", B, M, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("fsg_sample_elimination_f32", _p(pc), _p(radii), B, M, n_keep, _p(keep), _p(order), _p(ws), ws.numel(),
+                      _stream())
+        out = [keep.long()] + ([order.long()] if return_order else [])
+    if squeeze:
+        out = [t[0] for t in out]
+    return tuple(out) if return_order else out[0]
+
+
 # ------------------------------------------------------------------ segmentation loss (losses/nnu_loss.py:6-19)
 class _NNULoss(torch.autograd.Function):
     @staticmethod

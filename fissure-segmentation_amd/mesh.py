@@ -2,6 +2,9 @@
 takes from pytorch3d for `train_pc_ae.py --loss mesh` (losses/mesh_loss.py:28-57, models/folding_net.py:76-77, 225-226,
 285-286): `Meshes`, `join_meshes_as_batch`, `sample_points_from_meshes`, `mesh_edge_loss`, `mesh_normal_consistency`,
 `mesh_laplacian_smoothing(method="uniform")`.  `mesh_regularizers` is the one-launch form of the three terms.
+`Meshes.sample_points_poisson_disk` / `sample_points_poisson_disk` stand in for open3d's TriangleMesh method of that name
+(shape_model/point_cloud_registration.py:224, :338): the uniform sampler followed by weighted sample elimination on the GPU
+(csrc/poisson_disk.hip), for the whole batch at once.
 
 `Meshes` carries only what the reference's callers use.  It is a container on any device; everything that computes refuses
 CPU tensors like the rest of the package.  Connectivity (unique edges, neighbour lists, the face pairs across an edge and the
@@ -15,6 +18,8 @@ Vertex normals are CARRIED, not computed: `Meshes(verts, faces, verts_normals=..
 Not here: the cotangent / cotcurv Laplacian, a non-zero target edge length, textures, vertex normals of arbitrary meshes, and the
 random stream of pytorch3d's sampler (the picks come from `torch.rand` through a fixed rule; which points are drawn for a given seed
 differs from pytorch3d's multinomial)."""
+import math
+
 import torch
 from torch.multiprocessing.reductions import StorageWeakRef
 
@@ -334,6 +339,53 @@ class Meshes:
         u = torch.rand(len(self), int(n), 3, device=self._device, dtype=torch.float32, generator=generator)
         return sample_points_from_uniforms(self, u, return_faces)
 
+    def sample_points_poisson_disk(self, number_of_points, init_factor=5, generator=None, return_indices=False):
+        """open3d's TriangleMesh.sample_points_poisson_disk for the whole batch: N = number_of_points blue-noise points per
+        mesh -> (B, N, 3) fp32 [, the kept rows (B, N) int64 of the M initial samples, ascending].
+
+        M = init_factor * N uniform surface samples are drawn from torch.rand(B, M, 3, generator=generator) through
+        sample_points_from_uniforms and thinned by weighted sample elimination (functional.sample_elimination) with the
+        constants open3d takes from Yuksel's paper: with A the mesh's surface area (the fp64 sum of face areas the sampler
+        forms), R = 2 sqrt((A / N) / (2 sqrt 3)) and r_min = R / 2 (1 - (N / M)^1.5), evaluated in fp64 on the device and
+        rounded to fp32.  Survivors keep their sample order.  Runs under no_grad and returns constants: no gradient reaches
+        the vertices.  No host synchronisation.  Parity with open3d's own random stream and loop is unpinned."""
+        N = number_of_points
+        if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+            raise ValueError(f"sample_points_poisson_disk: number_of_points must be a positive integer, got {N!r}")
+        if isinstance(init_factor, bool) or not isinstance(init_factor, (int, float)) or not init_factor >= 1:
+            raise ValueError(f"sample_points_poisson_disk: init_factor must be a number >= 1, got {init_factor!r}")
+        M = int(init_factor * N)
+        if M > _lib.SAMPLE_ELIMINATION_MAX_POINTS:
+            raise ValueError(f"sample_points_poisson_disk: init_factor * number_of_points = {M} initial samples, the elimination "
+                             f"kernel serves at most {_lib.SAMPLE_ELIMINATION_MAX_POINTS}")
+        self._check_computable("sample_points_poisson_disk", True)
+        B = len(self)
+        with torch.no_grad():
+            u = torch.rand(B, M, 3, device=self._device, dtype=torch.float32, generator=generator)
+            st = self._sample_struct()
+            pts, _, _, cdf = _mesh_sample_raw(self.verts_packed(), u, st)
+            last = (torch.tensor(self._nf, dtype=torch.int64) - 1).to(self._device)
+            R, r_min = poisson_disk_radii(cdf.gather(1, last[:, None])[:, 0], N, M)
+            keep = F_hip.sample_elimination(pts, N, R, r_min)
+            out = torch.gather(pts, 1, keep[:, :, None].expand(B, N, 3))
+        return (out, keep) if return_indices else out
+
+
+def poisson_disk_radii(area, n, m):
+    """open3d's constants of the weighted sample elimination for n points from m samples of a surface of area `area` ((B,)
+    tensor): R = 2 sqrt((A / n) / (2 sqrt 3)), r_min = R / 2 (1 - (n / m)^1.5), in fp64, rounded to fp32 -> (R, r_min)"""
+    a = area.to(torch.float64)
+    # (tensor divisors: torch divides by a Python number through its reciprocal, which is not the quotient to the last bit)
+    R = 2.0 * torch.sqrt((a / torch.full_like(a, n)) / torch.full_like(a, 2.0 * math.sqrt(3.0)))
+    r_min = R * 0.5 * (1.0 - (n / m) ** 1.5)
+    return R.to(torch.float32), r_min.to(torch.float32)
+
+
+def sample_points_poisson_disk(meshes, number_of_points, init_factor=5, generator=None, return_indices=False):
+    """`meshes.sample_points_poisson_disk(...)`"""
+    return meshes.sample_points_poisson_disk(number_of_points, init_factor=init_factor, generator=generator,
+                                             return_indices=return_indices)
+
 
 def join_meshes_as_batch(meshes):
     """list of Meshes -> one Meshes holding all their meshes in order"""
@@ -345,21 +397,28 @@ def join_meshes_as_batch(meshes):
 
 
 # ----------------------------------------------------------------------------------------------------------- sampling
+def _mesh_sample_raw(verts, u, st):
+    """fsg_mesh_sample_f32 -> (pts, face, w, cdf): cdf (N, max_F) fp64 is the kernel's inclusive prefix sum of the face areas of
+    every mesh (its workspace)"""
+    vc, uc = _f32c(verts), _f32c(u)
+    N, n = uc.shape[0], uc.shape[1]
+    dev = vc.device
+    pts = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(N, n, dtype=torch.int32, device=dev)
+    w = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("fsg_mesh_sample", N, st.max_F, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("fsg_mesh_sample_f32", _p(vc), _p(st.faces), _p(st.sdesc), N, st.max_F, _p(uc), n, _p(pts), _p(face),
+                  _p(w), _p(ws), ws.numel(), _stream())
+    return pts, face, w, ws.view(torch.float64).view(N, st.max_F)
+
+
 class _MeshSample(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
     def forward(ctx, verts, u, st):
-        vc, uc = _f32c(verts), _f32c(u)
-        N, n = uc.shape[0], uc.shape[1]
-        dev = vc.device
-        pts = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
-        face = torch.empty(N, n, dtype=torch.int32, device=dev)
-        w = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
-        ws = _lib.workspace("fsg_mesh_sample", N, st.max_F, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("fsg_mesh_sample_f32", _p(vc), _p(st.faces), _p(st.sdesc), N, st.max_F, _p(uc), n, _p(pts), _p(face),
-                      _p(w), _p(ws), ws.numel(), _stream())
-        ctx.st, ctx.n = st, n
+        pts, face, w, _ = _mesh_sample_raw(verts, u, st)
+        ctx.st, ctx.n = st, u.shape[1]
         ctx.save_for_backward(face, w)
         ctx.mark_non_differentiable(face, w)
         return pts, face, w

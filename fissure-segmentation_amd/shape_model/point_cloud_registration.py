@@ -20,13 +20,23 @@ of this package, and parity with it is unpinned: the yardstick is the fp64 resta
 
 numpy arrays go in the way the reference passes them and come out as numpy (the work still runs on the current GPU); torch
 tensors must be on a GPU and stay there.  A 2-D Y is a batch of one, returned without the batch axis.  Not reproduced either:
-the thin-plate-spline interpolation mode (out of scope, it raises), the open3d / matplotlib driver `register_all`."""
+the thin-plate-spline interpolation mode (out of scope, it raises).
+
+`register_all` (:191-297) is the driver that turns a data set of meshes into the arrays `data_set_correspondences` consumes.
+The reference rests it on open3d; here `TriangleMesh.sample_points_poisson_disk` is `mesh.Meshes.sample_points_poisson_disk`
+(weighted sample elimination on the GPU, all meshes of one object in one call), `evaluate_registration` and
+`correspondence_distance_heuristic` are the functions of those names below, the rigid step runs once for all instances and
+the deformable step `pair_batch` (instance, object) pairs at a time.  It writes no files and draws no plots: the five pickled
+objects and the rows of correspondences.csv come back in a dict.  Parity with open3d's sampler (its random stream, its heap
+loop) is unpinned."""
 import numbers
 
 import numpy as np
 import torch
 
 from .. import functional as F_hip
+from ..mesh import Meshes
+from ..metrics import _device, _mesh_arrays
 
 INTERPOLATION_MODES = ['knn', 'tps']
 CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
@@ -287,3 +297,159 @@ def inverse_transformation_at_sampled_points(deformed_pc_np, moving_displacement
     if as_numpy:
         return sample_point_cloud - interpolated.cpu().numpy().astype(sample_point_cloud.dtype)
     return sample - interpolated.to(sample.dtype)
+
+
+# ------------------------------------------------------------------ the driver (point_cloud_registration.py:180-297)
+def correspondence_distance_heuristic(pc):
+    """point_cloud_registration.py:180-188: 5 % of the longest diagonal through the bounding box of a cloud (N,3) -- a float for
+    numpy, a 0-d tensor for a tensor -- or of every cloud of a batch (B,N,3) -> (B,)."""
+    if isinstance(pc, np.ndarray):
+        if pc.ndim not in (2, 3) or pc.shape[-1] != 3 or pc.shape[-2] < 1:
+            raise ValueError(f"pc must be (points, 3) or (batch, points, 3), got {pc.shape}")
+        diag = np.linalg.norm(pc.max(-2) - pc.min(-2), ord=2, axis=-1)
+        return diag.item() * 0.05 if pc.ndim == 2 else diag * 0.05
+    pc = _as_tensor(pc, "pc")
+    return torch.linalg.vector_norm(pc.amax(-2) - pc.amin(-2), ord=2, dim=-1) * 0.05
+
+
+def evaluate_registration(source, target, max_correspondence_distance):
+    """open3d.pipelines.registration.evaluate_registration without a transformation, batched through functional.chamfer_nn:
+    source (N,3) or (B,N,3), target (M,3) or (B,M,3), max_correspondence_distance a number or (B,) -> dict with
+    `n_correspondences`, the number of source points whose nearest target point lies within the distance (<=; the length of
+    open3d's correspondence_set), `fitness` = that count / N and `inlier_rmse`, the root mean square of those nearest
+    distances (0 without inliers).  The nearest squared distance is the kernel's fp32 value; its root is compared in fp64.
+    numpy in, numpy out (Python numbers for a 2-D source); GPU tensors in, GPU tensors out."""
+    as_numpy = isinstance(source, np.ndarray)
+    if isinstance(target, np.ndarray) != as_numpy:
+        raise TypeError("source and target must both be numpy arrays or both be torch tensors")
+    src, tgt = _as_tensor(source, "source"), _as_tensor(target, "target")
+    squeeze = src.dim() == 2
+    if tgt.dim() != src.dim():
+        raise ValueError(f"source {tuple(src.shape)} and target {tuple(tgt.shape)} must both be single clouds or both batches")
+    if squeeze:
+        src, tgt = src[None], tgt[None]
+    B, N = src.shape[0], src.shape[1]
+    if tgt.shape[0] != B:
+        raise ValueError(f"source holds {B} clouds, target {tgt.shape[0]}")
+    if not as_numpy:
+        F_hip._need_gpu(src, tgt)
+    dev = _device() if as_numpy else src.device
+    with torch.no_grad():
+        limit = torch.as_tensor(max_correspondence_distance, dtype=torch.float64).to(dev).reshape(-1)
+        if limit.numel() not in (1, B):
+            raise ValueError(f"max_correspondence_distance must be one value or one per cloud ({B}), got {limit.numel()}")
+        d2, _ = F_hip.chamfer_nn(src.to(device=dev, dtype=torch.float32).contiguous(),
+                                 tgt.to(device=dev, dtype=torch.float32).contiguous())
+        d2 = d2.detach().double()
+        inlier = d2.sqrt() <= limit[:, None]
+        count = inlier.sum(1)
+        rmse = torch.where(count > 0, ((d2 * inlier).sum(1) / count.clamp(min=1)).sqrt(), torch.zeros_like(limit.expand(B)))
+        # (a tensor divisor: torch divides by a Python number through its reciprocal, which is not count / N to the last bit)
+        out = {"n_correspondences": count, "fitness": count.double() / torch.full_like(rmse, N), "inlier_rmse": rmse}
+    if squeeze:
+        out = {k: v[0] for k, v in out.items()}
+    if as_numpy:
+        out = {k: (v.item() if squeeze else v.cpu().numpy()) for k, v in out.items()}
+    return out
+
+
+def _fixed_clouds(fixed_pcs):
+    """a sequence of (P,3) clouds or an (objects, P, 3) array -> (as_numpy, list of per-object arrays / tensors); ragged
+    objects are refused before anything runs"""
+    clouds = list(fixed_pcs)
+    if not clouds:
+        raise ValueError("register_all: no fixed point clouds")
+    as_numpy = not torch.is_tensor(clouds[0])
+    if as_numpy:
+        clouds = [np.asarray(c) for c in clouds]
+    elif not all(torch.is_tensor(c) for c in clouds):
+        raise TypeError("register_all: fixed_pcs must be all numpy arrays or all torch tensors")
+    for c in clouds:
+        if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] < 1:
+            raise ValueError(f"register_all: a fixed cloud must be (points, 3), got {tuple(c.shape)}")
+    counts = [int(c.shape[0]) for c in clouds]
+    if len(set(counts)) != 1:
+        raise ValueError(f"register_all: the fixed clouds of the objects hold {counts} points; every object must hold the same "
+                         f"number (data_set_correspondences needs equal counts)")
+    return as_numpy, clouds
+
+
+def register_all(fixed_pcs, all_moving_meshes, ids=None, base_dir=None, n_sample_points=1024, show=False, generator=None,
+                 pair_batch=32):
+    """point_cloud_registration.py:191-297.  fixed_pcs: one (P,3) cloud per object (a sequence or an (objects, P, 3) array);
+    all_moving_meshes[instance][object]: a mesh in any form `metrics._mesh_arrays` takes (a (verts, faces) pair, an open3d
+    TriangleMesh); surplus objects of an instance are dropped as in the reference.  Steps:
+      1. every moving mesh is sampled to P points with `Meshes.sample_points_poisson_disk` -- the meshes of one object over all
+         instances in one call, objects in order, all drawing from `generator`;
+      2. ONE batched RigidRegistration of the concatenated objects (fixed: shared, moving: one row per instance);
+      3. the result is split per object and registered with `register_cpd_deformable`, `pair_batch` (instance, object) pairs
+         at a time in instance-major order (the M x M fp64 systems of a chunk set the memory);
+      4. `evaluate_registration` of every deformed cloud (as fp32, like the reference) against its fixed cloud within
+         `correspondence_distance_heuristic` of that fixed cloud.
+    -> dict: `displacements`, `moved_pcs`, `moving_pcs` (instances, objects, P, 3) fp64; `transforms`, one dict per instance
+    with `scale`, `translation` and `rotation` (transposed to the column-vector form A x, :237); `ids`;
+    `n_correspondences` and `corr_distances` (instances, objects); `correspondences`, the rows of the reference's
+    correspondences.csv as a dict of lists (per object, then the overall value; numpy's population std).
+    numpy in, numpy out; GPU tensors in, GPU tensors out.  `base_dir`, `show` and `n_sample_points` are accepted and ignored
+    (no files, no plots; the reference does not use n_sample_points either).  The first four arrays feed
+    `data_set_correspondences(fixed_pcs, all_moving_meshes, out['moving_pcs'], out['transforms'], out['moved_pcs'],
+    out['displacements'], mode=...)` unchanged."""
+    as_numpy, clouds = _fixed_clouds(fixed_pcs)
+    O, P = len(clouds), int(clouds[0].shape[0])
+    all_moving_meshes = [list(m)[:O] for m in all_moving_meshes]
+    I = len(all_moving_meshes)
+    if I == 0 or any(len(m) != O for m in all_moving_meshes):
+        raise ValueError(f"register_all: every instance must hold a mesh for each of the {O} objects")
+    ids = list(range(I)) if ids is None else list(ids)
+    if len(ids) != I:
+        raise ValueError(f"register_all: {len(ids)} ids for {I} instances")
+    if isinstance(pair_batch, bool) or not isinstance(pair_batch, int) or pair_batch < 1:
+        raise ValueError(f"register_all: pair_batch must be a positive integer, got {pair_batch!r}")
+    if not as_numpy:
+        F_hip._need_gpu(*clouds)
+    dev = _device() if as_numpy else clouds[0].device
+    with torch.no_grad():
+        fixed = torch.stack([(torch.from_numpy(np.ascontiguousarray(c)) if as_numpy else c).to(device=dev, dtype=torch.float64)
+                             for c in clouds])                                                       # (O, P, 3)
+        moving = []
+        for obj in range(O):
+            arrays = [_mesh_arrays(m[obj]) for m in all_moving_meshes]
+            meshes = Meshes([v.to(dev) for v, _ in arrays], [f.to(dev) for _, f in arrays])
+            moving.append(meshes.sample_points_poisson_disk(P, generator=generator))
+        moving = torch.stack(moving, 1).double()                                                     # (I, O, P, 3)
+
+        rigid = RigidRegistration(X=fixed.reshape(O * P, 3), Y=moving.reshape(I, O * P, 3))
+        prereg, (scale, rotation, translation) = rigid.register()
+        rotation = rotation.transpose(1, 2).contiguous()
+
+        X = fixed[None].expand(I, O, P, 3).reshape(I * O, P, 3)
+        Y = prereg.reshape(I * O, P, 3)
+        moved, disp = [], []
+        for p0 in range(0, I * O, pair_batch):
+            deformed, d = register_cpd_deformable(X[p0:p0 + pair_batch].contiguous(), Y[p0:p0 + pair_batch].contiguous())
+            moved.append(deformed)
+            disp.append(d)
+        moved, disp = torch.cat(moved), torch.cat(disp)
+
+        corr_dist = correspondence_distance_heuristic(fixed)                                         # (O,)
+        corr_distances = corr_dist[None].expand(I, O)
+        found = evaluate_registration(moved.float(), X.float(), corr_distances.reshape(-1))
+        n_corr = found["n_correspondences"].reshape(I, O)
+
+    n_host, dist_host = n_corr.cpu().numpy(), corr_distances.cpu().numpy()
+    portion = n_host / float(P)
+    rows = {"Object No.": [str(obj + 1) for obj in range(O)] + ["mean"],
+            "Mean corresponding": portion.mean(0).tolist() + [portion.mean().item()],
+            "StdDev corresponding": portion.std(0).tolist() + [portion.std().item()],
+            "Max. corr dist": dist_host.mean(0).tolist() + [dist_host.mean().item()]}
+    out = {"displacements": disp.reshape(I, O, P, 3), "moved_pcs": moved.reshape(I, O, P, 3), "moving_pcs": moving,
+           "n_correspondences": n_corr, "corr_distances": corr_distances.contiguous()}
+    if as_numpy:
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        s, R, t = scale.cpu().numpy(), rotation.cpu().numpy(), translation.cpu().numpy()
+        out["transforms"] = [{"scale": float(s[i]), "translation": t[i], "rotation": R[i]} for i in range(I)]
+    else:
+        out["transforms"] = [{"scale": scale[i], "translation": translation[i], "rotation": rotation[i]} for i in range(I)]
+    out["ids"] = np.asarray(ids)
+    out["correspondences"] = rows
+    return out

@@ -1006,6 +1006,31 @@ int fsg_kmeans_step_f32(const float *points, float *centroids, int32_t *labels, 
 int fsg_kmeans_assign_f32(const float *points, const float *centroids, int32_t *labels, int B, int n, int K, void *workspace,
                           size_t workspace_bytes, int32_t *counts, double *stats, int32_t *info, fsg_stream_t stream);
 
+/* Weighted sample elimination (Yuksel, "Sample Elimination for Generating Poisson Disk Sample Sets", 2015), batched and
+ * bit-reproducible (csrc/poisson_disk.hip).  Serves TriangleMesh.sample_points_poisson_disk, which the reference takes from
+ * open3d on the host, one mesh at a time (shape_model/point_cloud_registration.py:224, :338).  B independent items:
+ *   points (B, M, 3) fp32, radii (B, 2) fp32 = (R, r_min) per item, keep (B, n_keep) int32, order (B, M - n_keep) int32 or
+ *   NULL, all DEVICE and contiguous; coordinates finite.  1 <= n_keep <= M <= 16384 (FSG_ERR_UNSUPPORTED above: the weights of
+ *   an item live in LDS), B <= 65535.  workspace: fsg_sample_elimination_workspace_bytes(B, M) bytes (8 M per item), 8-byte
+ *   aligned.  NULL pointers, bad shapes and a short or misaligned workspace are FSG_ERR_ARG before any launch.
+ * The rule (ours, not open3d's loop):
+ *   pair    d2 = ((dx dx + dy dy) + dz dz) in fp32 in that order; samples i != j are neighbours iff R > 0 and d2 < R R (the
+ *     fp32 product); d = fmaxf(sqrtf(d2), r_min), t = fmaxf(1 - d / R, 0), w = ((t t)^2)^2 (alpha = 8 by three fp32
+ *     squarings), q = rintf(w 2^24) as an integer.  Exact duplicates are neighbours with d = r_min.  The clamp of t acts only
+ *     for r_min > R.
+ *   weight  of a sample = the int64 sum of q over its alive neighbours: no summation order, tiling or batch neighbour can
+ *     change it, and the subtractions below are exact.
+ *   round   M - n_keep times: remove the alive sample with the largest weight, the LOWEST index on ties, and subtract
+ *     q(removed, j) from every alive neighbour j.  R <= 0 (or NaN), or no neighbours anywhere: all weights are 0 and the
+ *     removal runs in index order; that is defined behaviour.
+ * keep receives the surviving indices in ASCENDING order (survivors keep their sample order), order the removal sequence.
+ * n_keep == M writes 0 .. M-1 and removes nothing.  Two launches (weights over (item, tile); one workgroup per item for the
+ * rounds), no atomics, nothing read on the host, capturable in a graph; the same inputs give the same bits on every run,
+ * alone or in a batch. */
+size_t fsg_sample_elimination_workspace_bytes(int B, int M);
+int fsg_sample_elimination_f32(const float *points, const float *radii, int B, int M, int n_keep, int32_t *keep, int32_t *order,
+                               void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+
 /* Random-walker lobe filling and lobes-to-fissures (csrc/random_walk.hip).  Volumes are (B, D, H, W), DEVICE, contiguous.
  *
  * The graph of compute_laplace_matrix (data_processing/random_walk.py:15-77) is never a matrix: nodes are the voxels, edges

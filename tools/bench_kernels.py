@@ -1539,3 +1539,99 @@ if "kmeans" in which:
     out_path = os.environ.get("FSG_KMEANS_BENCH_OUT", os.path.join(ROOT, "profiles", "kmeans_bench.jsonl"))
     with open(out_path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+if "poisson" in which:
+    # Weighted sample elimination (csrc/poisson_disk.hip) at the reference's size, N = 1024 points from M = 5 N uniform samples
+    # of a unit square with open3d's radii, for B = 1, 8 and 256 items; beside it, in the same run, a torch composition of the
+    # same rule on the device (the dense quantised pair matrix, built item by item into int32, and a host-free loop of
+    # M - N rounds: key maximum, row gather, subtraction) and, on the host for item 0, the heap / KD-tree implementation
+    # (tests/poisson_disk_oracle.eliminate_heap) and the numpy restatement; peak extra memory; whether the three agree with the
+    # kernel.  Writes profiles/poisson_disk_bench.jsonl.
+    import json
+    import time
+    import numpy as np
+    import poisson_disk_oracle as po
+    lines = []
+    N, M = 1024, 5120
+
+    def emit_line(rec):
+        lines.append(json.dumps(rec))
+        print("POISSON " + lines[-1], flush=True)
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            keep = fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+            del keep
+        return round(statistics.median(ts), 1)
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 1)
+
+    def torch_elimination(pts, n_keep, R, r_min):
+        """the rule of the kernel out of torch operations: -> (keep (B, n_keep) ascending, order (B, M - n_keep))"""
+        B, m = pts.shape[0], pts.shape[1]
+        Q = torch.empty(B, m, m, dtype=torch.int32, device=pts.device)
+        eye = torch.eye(m, dtype=torch.bool, device=pts.device)
+        for b in range(B):
+            p = pts[b]
+            dx, dy, dz = (p[:, None, c] - p[None, :, c] for c in range(3))
+            d2 = (dx * dx + dy * dy) + dz * dz
+            t = (1.0 - torch.maximum(d2.sqrt(), r_min[b]) / R[b]).clamp_min(0.0)
+            t = t * t
+            t = t * t
+            t = t * t
+            Q[b] = torch.where((d2 < R[b] * R[b]) & ~eye & (R[b] > 0), torch.round(t * 16777216.0), 0.0).to(torch.int32)
+        w = Q.sum(2, dtype=torch.int64)
+        rows = torch.arange(B, device=pts.device)
+        low = (16383 - torch.arange(m, device=pts.device))[None]
+        alive = torch.ones(B, m, dtype=torch.bool, device=pts.device)
+        order = torch.empty(B, m - n_keep, dtype=torch.int64, device=pts.device)
+        for r in range(m - n_keep):
+            i = 16383 - torch.where(alive, w * 16384 + low, -1).amax(1) % 16384
+            order[:, r] = i
+            alive[rows, i] = False
+            w -= Q[rows, i]
+        return alive.nonzero()[:, 1].view(B, n_keep), order
+
+    R0, r0 = po.radii(1.0, N, M)
+    for B in (1, 8, 256):
+        pts = torch.from_numpy(np.stack([po.unit_square(100 + b, M) for b in range(B)])).to(dev)
+        R, r_min = torch.full((B,), float(R0), device=dev), torch.full((B,), float(r0), device=dev)
+        keep, order = F.sample_elimination(pts, N, R, r_min, return_order=True)
+        us = timeit(lambda: F.sample_elimination(pts, N, R, r_min, return_order=True), iters=7, warm=2)
+        first = timeit(lambda: F.sample_elimination(pts, M - 1, R, r_min, return_order=True), iters=7, warm=2)
+        rec = dict(kernel="sample_elimination", B=B, N=N, M=M, R=float(R0), r_min=float(r0), us=round(us[0], 1),
+                   min_us=round(us[1], 1), us_per_round=round(us[0] / (M - N), 3),
+                   weights_launch_plus_one_round_us=round(first[0], 1),
+                   peak_extra_MiB=peak_extra(lambda: F.sample_elimination(pts, N, R, r_min, return_order=True)))
+        ck, co = torch_elimination(pts, N, R, r_min)
+        rec.update(torch_composition_equal=bool(torch.equal(ck, keep) and torch.equal(co, order)),
+                   torch_composition_us=wall(lambda: torch_elimination(pts, N, R, r_min), reps=1 if B > 8 else 2),
+                   torch_composition_peak_extra_MiB=peak_extra(lambda: torch_elimination(pts, N, R, r_min)))
+        del ck, co
+        p0 = pts[0].cpu().numpy()
+        t0 = time.perf_counter()
+        hk, ho = po.eliminate_heap(p0, N, R0, r0)
+        rec["host_heap_kdtree_us_item0"] = round((time.perf_counter() - t0) * 1e6, 1)
+        t0 = time.perf_counter()
+        ak, ao = po.eliminate(p0, N, R0, r0)
+        rec["host_numpy_restatement_us_item0"] = round((time.perf_counter() - t0) * 1e6, 1)
+        rec["host_equal_item0"] = bool(np.array_equal(hk, keep[0].cpu().numpy()) and np.array_equal(ho, order[0].cpu().numpy())
+                                       and np.array_equal(ak, hk) and np.array_equal(ao, ho))
+        rec["min_nn_distance_over_R_item0"] = round(po.min_nn_distance(p0[hk]) / float(R0), 4)
+        emit_line(rec)
+        del pts, keep, order
+    out_path = os.environ.get("FSG_POISSON_BENCH_OUT", os.path.join(ROOT, "profiles", "poisson_disk_bench.jsonl"))
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
