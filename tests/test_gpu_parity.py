@@ -2997,6 +2997,109 @@ def test_pointops_fused_glue_vs_torch(fsg, device, n, m, c, ns):
     assert torch.equal((x1.grad != 0).sum(1) <= 1, torch.ones(m, c, dtype=torch.bool, device=device))
 
 
+GLUE_GRID_CAP = 16384 * 256       # csrc/pointops.hip grid_for(): at most 16384 workgroups of BLOCK = 256 threads
+
+
+def _past_cap(total):
+    """the grid-stride loop takes a second step, and (where the shape allows it) that step ends inside a workgroup"""
+    assert total > GLUE_GRID_CAP
+    return (total - GLUE_GRID_CAP) % 256 != 0
+
+
+def _within(got, want, mag, rel):
+    """|got - fp64| <= rel x the sum of the absolute summands, element by element"""
+    return bool(((got.double().cpu() - want).abs() <= rel * mag).all())
+
+
+def _scatter64(idx, rows, n):
+    """fp64 sum of `rows` (E, c) into the destinations idx (E,) -> (sum, sum of absolute values), each (n, c)"""
+    z = torch.zeros(n, rows.shape[1], dtype=torch.float64)
+    return z.index_add(0, idx, rows), z.index_add(0, idx, rows.abs())
+
+
+@pytest.mark.parametrize("op", ["group_gather", "group_xyz_feat", "rows_max", "interpolate", "vec_attn"])
+def test_pointops_fused_glue_past_the_grid_cap(fsg, device, op):
+    """The same one-launch glue with MORE work items than the 16384 x 256 threads its grid is capped at, so that every
+    grid-stride loop (group_*, group_xyz_feat_*, rows_max_*, interp_*, vec_attn_*) takes a second step: against the fp64 tensor
+    expression on the CPU, forward and gradient.  Gathers, the max and the routing of its gradient are exact; sums are held to
+    the bounds of the tests above (2e-6 interpolation, 1e-5 the atomics and vec_attn) times the sum of the absolute summands."""
+    F_hip = fsg.functional
+    g = np.random.default_rng(len(op))
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))   # noqa: E731
+    if op in ("group_gather", "group_xyz_feat"):
+        n, m, ns, c = 1000, 4100, 16, 64
+        xyz, nxyz, feat = f32(g.standard_normal((n, 3))), f32(g.standard_normal((m, 3))), f32(g.standard_normal((n, c)))
+        idx = torch.from_numpy(g.integers(0, n, (m, ns)).astype(np.int32))
+        f1 = feat.to(device).requires_grad_(True)
+        if op == "group_gather":
+            _past_cap(m * ns * c)                                  # ns c = 1024 divides the total: the second step ends on a workgroup
+            go = f32(g.standard_normal((m, ns, c)))
+            got = F_hip.group_gather(f1, idx.to(device))
+            assert torch.equal(got.cpu(), feat[idx.long()])
+            go_feat = go
+        else:
+            assert _past_cap(m * ns * (c + 3))                     # forward; the backward walks m ns c items like group_gather's
+            _past_cap(m * ns * c)
+            go = f32(g.standard_normal((m, ns, c + 3)))
+            got = F_hip.group_xyz_feat(xyz.to(device), nxyz.to(device), f1, idx.to(device))
+            assert torch.equal(got.cpu(), torch.cat((xyz[idx.long()] - nxyz.unsqueeze(1), feat[idx.long()]), -1))
+            go_feat = go[:, :, 3:]
+        got.backward(go.to(device))
+        want, mag = _scatter64(idx.long().reshape(-1), go_feat.double().reshape(m * ns, c), n)
+        assert _within(f1.grad, want, mag, 1e-5)
+    elif op == "rows_max":
+        for m, ns, c in ((4100, 16, 64), (66001, 2, 64)):          # backward (m ns c) past the cap; forward (m c) past the cap
+            _past_cap(m * ns * c)
+            assert m * c <= GLUE_GRID_CAP or _past_cap(m * c)
+            x = g.standard_normal((m, ns, c)).astype(np.float32)
+            x[::3, 1, :] = x[::3, 0, :]                            # exact ties: the first row takes the gradient
+            x, go = f32(x), f32(g.standard_normal((m, c)))
+            x1 = x.to(device).requires_grad_(True)
+            got = F_hip.rows_max(x1)
+            want = x.max(dim=1)[0]
+            assert torch.equal(got.cpu(), want)
+            got.backward(go.to(device))
+            first = (x == want.unsqueeze(1)).int().argmax(dim=1)   # first row holding the max
+            gx = torch.zeros(m, ns, c).scatter_(1, first.unsqueeze(1), go.unsqueeze(1))
+            assert torch.equal(x1.grad.cpu(), gx)
+    elif op == "interpolate":
+        n, m, c, k = 5000, 66001, 64, 3
+        assert _past_cap(m * c)
+        feat, go = f32(g.standard_normal((n, c))), f32(g.standard_normal((m, c)))
+        idx = torch.from_numpy(g.integers(0, n, (m, k)).astype(np.int32))
+        d2 = g.uniform(0.0, 2.0, (m, k)).astype(np.float32)
+        d2[0, 0] = d2[m - 1, 2] = 0.0
+        d2 = f32(d2)
+        f1 = feat.to(device).requires_grad_(True)
+        got = F_hip.interpolate(f1, idx.to(device), d2.to(device))
+        w = 1.0 / (torch.sqrt(d2.double()) + 1e-8)
+        w = w / w.sum(dim=1, keepdim=True)
+        terms = feat.double()[idx.long()] * w.unsqueeze(-1)        # (m, k, c)
+        assert _within(got, terms.sum(1), terms.abs().sum(1), 2e-6)
+        got.backward(go.to(device))
+        rows = (go.double().unsqueeze(1) * w.unsqueeze(-1)).reshape(m * k, c)
+        want, mag = _scatter64(idx.long().reshape(-1), rows, n)
+        assert _within(f1.grad, want, mag, 1e-5)
+    else:
+        n, ns, c, cw = 66001, 4, 64, 32
+        assert _past_cap(n * c) and _past_cap(n * ns * cw)
+        v, pos, w = f32(g.standard_normal((n, c))), f32(g.standard_normal((n, ns, c))), f32(g.random((n, ns, cw)))
+        idx = torch.from_numpy(g.integers(0, n, (n, ns)).astype(np.int32))
+        go = f32(g.standard_normal((n, c)))
+        v1, p1, w1 = (t.to(device).requires_grad_(True) for t in (v, pos, w))
+        got = F_hip.vec_attn(v1, p1, w1, idx.to(device))
+        got.backward(go.to(device))
+        vp = v.double()[idx.long()] + pos.double()                 # (n, ns, c)
+        wf = w.double().repeat(1, 1, c // cw)                      # w[i, j, ch % cw]
+        assert _within(got, (vp * wf).sum(1), (vp * wf).abs().sum(1), 1e-5)
+        gterm = go.double().unsqueeze(1) * vp                      # d out / d w, before the sum over the share planes
+        assert _within(w1.grad, gterm.view(n, ns, c // cw, cw).sum(2), gterm.abs().view(n, ns, c // cw, cw).sum(2), 1e-5)
+        gpos = go.double().unsqueeze(1) * wf
+        assert _within(p1.grad, gpos, gpos.abs(), 1e-6)            # one product
+        want, mag = _scatter64(idx.long().reshape(-1), gpos.reshape(n * ns, c), n)
+        assert _within(v1.grad, want, mag, 1e-5)
+
+
 @pytest.mark.parametrize("M,N,K", [(16384, 96, 32), (256, 256, 256), (1000, 77, 64), (64, 512, 512), (4096, 64, 67)])
 def test_gemm_small_bf16_matches_rounded_operands(fsg, device, M, N, K):
     """fsg_gemm_small_bf16 (the nn.Linear products of the PointTransformer in bf16 mode): operands rounded to bf16 inside the
