@@ -42,14 +42,15 @@ __device__ __forceinline__ void load_softmax(const float *__restrict__ logits, l
         s += o.p[c];
     }
     const float inv = 1.0f / s;
-    const float lse = m + logf(s);
+    const float ls = logf(s);
     const long yl = labels[pt];
     o.y = (yl >= 0 && yl < C) ? (int)yl : -1;
     o.logp_y = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
         o.p[c] *= inv;
-        if (c == o.y) o.logp_y = z[c] - lse;
+        // (z - m) - log s, not z - (m + log s): m + log s rounds to an ulp of the logits' common offset (1e-3 at 1e4), z - m does not
+        if (c == o.y) o.logp_y = (z[c] - m) - ls;
     }
 }
 

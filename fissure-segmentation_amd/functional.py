@@ -94,7 +94,10 @@ def set_deterministic(flag=True):
     """Reproducible (ordered) reductions where the default scatters with fp32 atomics: today the Chamfer backward, whose
     ordered form walks the reverse graph of the arg-min and is slow when many points share one nearest neighbour (a
     collapsed reconstruction early in training: 5.3 -> 6.3 ms per PC-AE step).  Also on under
-    `torch.use_deterministic_algorithms(True)` and FSG_DETERMINISTIC=1.  The DGCNN path is reproducible regardless."""
+    `torch.use_deterministic_algorithms(True)` and FSG_DETERMINISTIC=1.  The DGCNN path is reproducible regardless.
+    Limit: the reverse-graph builder keeps one counter per target in LDS and takes at most 16384 targets per cloud; a Chamfer
+    backward onto more targets than that uses the atomics even with the flag set (same values to fp32 rounding, not the same
+    bits from run to run; tests/test_loss_family_gpu.py, case 300 -> 16400)."""
     global _deterministic
     _deterministic = bool(flag)
 
