@@ -43,6 +43,7 @@ def install_reference_aliases():
         "models.seg_logits_to_mesh": ".models.seg_logits_to_mesh", "losses.dpsr_loss": ".losses.dpsr_loss",
         "models.seg_cnn": ".models.seg_cnn", "models.mobilenet": ".models.mobilenet", "models.aspp_3d": ".models.aspp_3d",
         "data_processing.process_lung_mask": ".data_processing.process_lung_mask",
+        "dseg_ae_regularization": ".dseg_ae_regularization",
     }
     for ref_name, ours in pairs.items():
         sys.modules[ref_name] = importlib.import_module(ours, __name__)

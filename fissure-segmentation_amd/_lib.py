@@ -198,6 +198,10 @@ SIGNATURES = {
     "fsg_mbconv3d_fwd_f32": ([_P] * 10 + [_I] * 10 + [_P, _P], _I),
     "fsg_patch_accumulate_f32": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "fsg_patch_finalize_f32": ([_P, _P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_label_partition_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
+    "fsg_label_partition": ([_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "fsg_segment_jitter_extend_f32": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
+    "fsg_fps_start_f32": ([_P, _P, _P, _P, _I, _I, _P, _P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

@@ -1435,6 +1435,38 @@ int fsg_patch_accumulate_f32(const float *logits, int P, int K, int pd, int ph, 
                              float *sum, float *wsum, int B, int D, int H, int W, fsg_stream_t stream);
 int fsg_patch_finalize_f32(const float *sum, const float *wsum, int B, int K, int D, int H, int W, float *out, fsg_stream_t stream);
 
+/* DSEG-AE: from a labelled cloud to the auto-encoder's inputs (csrc/dseg_ae.hip), for every (item, object) group of a batch at
+ * once -- what dseg_ae_regularization.py:62-138 of the reference does per object of one cloud.  All pointers DEVICE.
+ *
+ * fsg_label_partition: stable split of B labelled clouds into packed segments.  labels (B, N) of label_kind FSG_LABEL_*;
+ *   x (B, C, N) fp32 channel-major, C >= 3, of which channels 0..2 are read; objects first_label .. first_label + L - 1,
+ *   1 <= L <= 16; any other label is dropped.  -> counts (B, L) int32; offset (B L) int32, the END of every segment, cumulative
+ *   in (item, object) order; xyz (B N, 3) fp32 and src (B N) int32, of which the first offset[B L - 1] rows are written: a
+ *   segment's points in ascending order of src, their index inside the item.  Two launches: per-tile counts from wave ballots,
+ *   then every tile takes its base from the counts in a fixed order and scatters by ballot rank.  B N < 2^31.
+ * fsg_segment_jitter_extend_f32: random_extend_points for G packed segments, one workgroup each.  xyz (n, 3) with offset (G);
+ *   nn_d2 (n): squared distance of every point to the nearest OTHER point of its segment (column 1 of
+ *   fsg_knn_segment_f32(nsample = 2) of the cloud against itself); new_offset (G): every segment at least as long as before,
+ *   n_new = new_offset[G - 1]; the caller's draws over the P = n_new - n padded rows, packed in segment order: src_idx (P) int32,
+ *   the source row inside the segment (clamped to it), direction (P, 3), z (P).  -> out (n_new, 3): the segment, then
+ *   xyz[src] + direction / |direction| * (z * std + mean); stats (G, 2) = { mean, std } of sqrtf(nn_d2) over the segment, the
+ *   unbiased deviation, from fp64 sums in a fixed order (two passes); both 0 for fewer than two points.  A zero direction
+ *   gives NaN, as in the reference.
+ * fsg_fps_start_f32: fsg_fps_f32 with a first sample: start (b) int32, the index INSIDE each segment (clamped to it), or NULL
+ *   for 0.  One workgroup of 1024 threads per segment; up to 16 384 points a segment lives in registers, longer ones in
+ *   global memory with tmp (n) fp32 as the running distances.  Same arithmetic and tie rule as fsg_fps_f32 (largest distance,
+ *   then lowest index): with start NULL the same idx bit for bit.
+ * No atomics: the same bits on every run, a group the same alone and in a batch.  Bad arguments are FSG_ERR_ARG. */
+size_t fsg_label_partition_workspace_bytes(int B, int N, int L);
+int fsg_label_partition(const void *labels, int label_kind, const float *x, int B, int C, int N, int first_label, int L,
+                        int32_t *counts, int32_t *offset, float *xyz, int32_t *src, void *workspace, size_t workspace_bytes,
+                        fsg_stream_t stream);
+int fsg_segment_jitter_extend_f32(const float *xyz, const int32_t *offset, const float *nn_d2, const int32_t *new_offset,
+                                  const int32_t *src_idx, const float *direction, const float *z, int G, int n, int n_new, float *out,
+                                  float *stats, fsg_stream_t stream);
+int fsg_fps_start_f32(const float *xyz, const int32_t *offset, const int32_t *new_offset, const int32_t *start, int b, int n,
+                      float *tmp, int32_t *idx, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

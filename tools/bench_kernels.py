@@ -1635,3 +1635,164 @@ if "poisson" in which:
     out_path = os.environ.get("FSG_POISSON_BENCH_OUT", os.path.join(ROOT, "profiles", "poisson_disk_bench.jsonl"))
     with open(out_path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+if "dsegae" in which:
+    # DSEG-AE (csrc/dseg_ae.hip, dseg_ae_regularization.py): a cloud of 32 768 points with three objects of about 3 000, 6 000 and
+    # 12 000 points, n_points_ae = 2048, at B = 1 and B = 8.  (1) fps_start against functional.fps on the same segments, each
+    # length alone and all together; (2) reconstruct_packed against the reference-shaped loop on the device (boolean masks, the
+    # reference's pure-torch sampling loop, one auto-encoder call per object); (3) the partition and extension launches alone and
+    # peak extra memory.  HIP-event medians of whole calls after warm-up, the two sides of a comparison alternating in one run,
+    # with the spread (min .. max) of the repeats.  Appends to profiles/dseg_ae_bench.jsonl.
+    import json
+    import tempfile
+    import numpy as np
+    from golden_util import fill_state_dict
+    from fissure_segmentation_amd.dseg_ae_regularization import RegularizedSegDGCNN
+    from fissure_segmentation_amd.models.dgcnn import DGCNNSeg
+    from fissure_segmentation_amd.models.folding_net import DGCNNFoldingNet
+    lines = []
+    N, N_AE, SIZES = 32768, 2048, (3000, 6000, 12000)
+
+    def emit_line(rec):
+        lines.append(json.dumps(rec))
+        print("DSEGAE " + lines[-1], flush=True)
+
+    def event_us(fn):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record(); keep = fn(); e.record(); torch.cuda.synchronize()
+        del keep
+        return s.elapsed_time(e) * 1e3
+
+    def alternate(sides, reps, warm=2):
+        """{name: fn} -> {name: (median, min, max)} in us, the sides taking turns inside every repeat"""
+        for _ in range(warm):
+            for fn in sides.values():
+                fn()
+        torch.cuda.synchronize()
+        ts = {k: [] for k in sides}
+        for _ in range(reps):
+            for k, fn in sides.items():
+                ts[k].append(event_us(fn))
+        return {k: (round(statistics.median(v), 1), round(min(v), 1), round(max(v), 1)) for k, v in ts.items()}
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 2)
+
+    def labelled(seed, B, sizes):
+        rng = np.random.default_rng(seed)
+        x = torch.from_numpy(cloud(seed, B, 3, N)).to(dev)
+        seg = np.zeros((B, N), np.int64)
+        for b in range(B):
+            perm, q = rng.permutation(N), 0
+            for o, s in enumerate(sizes):
+                n = int(s * rng.uniform(0.95, 1.05))
+                seg[b, perm[q:q + n]] = o + 1
+                q += n
+        return x, torch.from_numpy(seg).to(dev)
+
+    def reference_loop(model, x, seg):
+        """per object: boolean mask, the oracle's restatement of the pure-torch sampling loop (oracle/ref_cpu.py: device tensors
+        in, the index list on the host, so one arg-max round trip per sample) with a drawn start, one auto-encoder call"""
+        from oracle import ref_cpu
+        out = []
+        for b in range(x.shape[0]):
+            xb, sb = x[b:b + 1], seg[b:b + 1]
+            for obj in range(1, model.seg_model.num_classes):
+                pts = xb[:, :3].transpose(1, 2)[sb == obj].view(1, -1, 3)
+                if pts.shape[1] < model.ae.encoder.k:
+                    continue
+                start = int(torch.randint(pts.shape[1], (1,)))
+                sampled = ref_cpu.farthest_point_sampling(pts, model.n_points_ae, start)[0].transpose(1, 2)
+                out.append(model.ae(sampled.contiguous()))
+        return out
+
+    with tempfile.TemporaryDirectory() as tmp:
+        seg_net = fill_state_dict(DGCNNSeg(k=20, in_features=3, num_classes=4), 1)
+        ae = fill_state_dict(DGCNNFoldingNet(k=20, n_embedding=512, shape_type='plane', n_input_points=N_AE, decode_mesh=True), 2)
+        seg_net.save(os.path.join(tmp, "seg.pth"))
+        ae.save(os.path.join(tmp, "ae.pth"))
+        model = RegularizedSegDGCNN(os.path.join(tmp, "seg.pth"), os.path.join(tmp, "ae.pth"), n_points_seg=2048,
+                                    n_points_ae=N_AE).to(dev).eval()
+    for B in (1, 8):
+        x, seg = labelled(50 + B, B, SIZES)
+        counts, offset, xyz, src = F.label_partition(seg, x, 3)
+        lens = counts.flatten().tolist()
+        n = int(offset[-1])
+        xyz = xyz[:n].contiguous()
+        G_ = len(lens)
+        new_off = torch.arange(1, G_ + 1, dtype=torch.int32, device=dev) * N_AE
+        # (1) sampling: every length alone (item 0's three objects), then all groups in one call
+        if B == 1:
+            st = 0
+            for ln in lens:
+                one = xyz[st:st + ln].contiguous()
+                o1 = torch.tensor([ln], dtype=torch.int32, device=dev)
+                m1 = torch.tensor([N_AE], dtype=torch.int32, device=dev)
+                assert torch.equal(F.fps_start(one, o1, m1, N_AE), F.fps(one, o1, m1, N_AE))
+                r = alternate({"fps_start": lambda: F.fps_start(one, o1, m1, N_AE), "fps": lambda: F.fps(one, o1, m1, N_AE)}, reps=7)
+                emit_line(dict(kernel="fps_start_vs_fps", segments=1, length=ln, samples=N_AE, fps_start_us=r["fps_start"],
+                               fps_us=r["fps"], speedup=round(r["fps"][0] / r["fps_start"][0], 2), equal=True,
+                               columns="median, min, max over 7 alternating repeats"))
+                st += ln
+        assert torch.equal(F.fps_start(xyz, offset, new_off, G_ * N_AE), F.fps(xyz, offset, new_off, G_ * N_AE))
+        r = alternate({"fps_start": lambda: F.fps_start(xyz, offset, new_off, G_ * N_AE),
+                       "fps": lambda: F.fps(xyz, offset, new_off, G_ * N_AE)}, reps=7)
+        emit_line(dict(kernel="fps_start_vs_fps", B=B, segments=G_, lengths=lens, samples=N_AE, fps_start_us=r["fps_start"],
+                       fps_us=r["fps"], speedup=round(r["fps"][0] / r["fps_start"][0], 2), equal=True,
+                       columns="median, min, max over 7 alternating repeats"))
+        # (2) the pipeline after the segmentation
+        with torch.no_grad():
+            r = alternate({"packed": lambda: model.reconstruct_packed(x, seg), "loop": lambda: reference_loop(model, x, seg)},
+                          reps=3, warm=1)
+            emit_line(dict(kernel="reconstruct_packed_vs_reference_loop", B=B, N=N, lengths=lens, n_points_ae=N_AE,
+                           ae="k=20, n_embedding=512, folding decoder, m=2025", packed_us=r["packed"], loop_us=r["loop"],
+                           speedup=round(r["loop"][0] / r["packed"][0], 2),
+                           packed_peak_extra_MiB=peak_extra(lambda: model.reconstruct_packed(x, seg)),
+                           loop_peak_extra_MiB=peak_extra(lambda: reference_loop(model, x, seg)),
+                           columns="median, min, max over 3 alternating repeats"))
+        # (3) the partition alone, against the boolean masks it replaces; the extension on objects shorter than n_points_ae
+        masks = lambda: [x[b:b + 1, :3].transpose(1, 2)[seg[b:b + 1] == o] for b in range(B) for o in (1, 2, 3)]   # noqa: E731
+        r = alternate({"partition": lambda: F.label_partition(seg, x, 3), "masks": masks}, reps=15)
+        xs, ss = labelled(60 + B, B, (500, 1000, 1500))
+        c2, o2, p2, _ = F.label_partition(ss, xs, 3)
+        l2 = c2.flatten().tolist()
+        p2 = p2[:int(o2[-1])].contiguous()
+        P_ = sum(N_AE - v for v in l2)
+        d_src = torch.cat([torch.randint(v, (N_AE - v,)) for v in l2]).to(dev)
+        d_dir, d_z = torch.randn(P_, 3, device=dev), torch.randn(P_, device=dev)
+        nn_d2 = F.knn_segment(2, p2, p2, o2, o2)[1][:, 1].contiguous()
+        ends2 = o2.tolist()
+        e = alternate({"extend_with_knn": lambda: F.segment_jitter_extend(p2, ends2, N_AE, d_src, d_dir, d_z),
+                       "extend_given_nn": lambda: F.segment_jitter_extend(p2, ends2, N_AE, d_src, d_dir, d_z, nn_d2=nn_d2)}, reps=15)
+        emit_line(dict(kernel="partition_and_extension", B=B, N=N, partition_us=r["partition"], boolean_masks_us=r["masks"],
+                       partition_peak_extra_MiB=peak_extra(lambda: F.label_partition(seg, x, 3)),
+                       boolean_masks_peak_extra_MiB=peak_extra(masks), extension_lengths=l2, extension_target=N_AE,
+                       extension_with_knn_us=e["extend_with_knn"], extension_given_nn_us=e["extend_given_nn"],
+                       extension_peak_extra_MiB=peak_extra(lambda: F.segment_jitter_extend(p2, ends2, N_AE, d_src, d_dir, d_z)),
+                       columns="median, min, max over 15 alternating repeats (host-side wrapper included)"))
+        # (4) random_extend: two objects shorter than n_points_ae beside a long one.  On: only the short groups are extended, one
+        # auto-encoder forward; off: they go in at their own size, one forward per distinct size
+        xm, sm = labelled(70 + B, B, (500, 1500, 12000))
+
+        def packed_extend(flag):
+            model.random_extend = flag
+            try:
+                return model.reconstruct_packed(xm, sm)
+            finally:
+                model.random_extend = False
+        with torch.no_grad():
+            r = alternate({"on": lambda: packed_extend(True), "off": lambda: packed_extend(False)}, reps=7)
+        emit_line(dict(kernel="reconstruct_packed_random_extend", B=B, N=N, lengths=F.label_partition(sm, xm, 3)[0].flatten().tolist(),
+                       n_points_ae=N_AE, random_extend_on_us=r["on"], random_extend_off_us=r["off"],
+                       on_peak_extra_MiB=peak_extra(lambda: packed_extend(True)),
+                       off_peak_extra_MiB=peak_extra(lambda: packed_extend(False)),
+                       columns="median, min, max over 7 alternating repeats"))
+    out_path = os.environ.get("FSG_DSEGAE_BENCH_OUT", os.path.join(ROOT, "profiles", "dseg_ae_bench.jsonl"))
+    with open(out_path, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
