@@ -202,6 +202,9 @@ SIGNATURES = {
     "fsg_label_partition": ([_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "fsg_segment_jitter_extend_f32": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], _I),
     "fsg_fps_start_f32": ([_P, _P, _P, _P, _I, _I, _P, _P, _P], _I),
+    "fsg_tps_system_f64": ([_P, _I, _I, ctypes.c_double, _P, _P], _I),
+    "fsg_tps_eval_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "fsg_tps_grid_sample_f32": ([_P, _P, _P] + [_I] * 10 + [_P, _P], _I),
 }
 for _name, (_args, _res) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of sync

@@ -2252,6 +2252,152 @@ def kmeans(points, n_clusters=None, init='fps', max_iter=300, tol=1e-4, start=0,
     return (*out, extra) if return_info else tuple(out)
 
 
+# ------------------------------------------------------------------ thin-plate splines (shape_model/point_cloud_registration.py:24-89,119-133)
+TPS_MAX_CHANNELS = 4   # csrc/tps.hip: kMaxC
+
+
+def _tps_points(t, name, who):
+    """(n,3) or (B,n,3) floating-point -> (B,n,3), and whether the batch axis was added"""
+    if not torch.is_tensor(t) or t.dim() not in (2, 3) or t.shape[-1] != 3 or t.shape[-2] < 1 or not t.is_floating_point():
+        got = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{who}: {name} must be a floating-point (points, 3) or (batch, points, 3) tensor, got {got}")
+    return (t[None], True) if t.dim() == 2 else (t, False)
+
+
+def _tps_theta(theta, B, n, who):
+    if not torch.is_tensor(theta) or theta.dtype != torch.float64:
+        raise ValueError(f"{who}: theta must be an fp64 tensor (tps_fit returns one), got "
+                         f"{theta.dtype if torch.is_tensor(theta) else type(theta).__name__}")
+    if theta.dim() == 2:
+        theta = theta[None]
+    if theta.dim() != 3 or theta.shape[0] != B or theta.shape[1] != n + 4:
+        raise ValueError(f"{who}: theta must be ({B}, {n + 4}, C) for {B} x {n} control points, got {tuple(theta.shape)}")
+    if not 1 <= theta.shape[2] <= TPS_MAX_CHANNELS:
+        raise ValueError(f"{who}: C={theta.shape[2]} channels, the kernel serves 1 <= C <= {TPS_MAX_CHANNELS}")
+    return theta
+
+
+def _tps_same_device(who, *tensors):
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError(f"{who}: the tensors are on different devices ({', '.join(str(t.device) for t in tensors)})")
+
+
+def _tps_size(size, what):
+    try:
+        size = tuple(int(s) for s in size)
+    except (TypeError, ValueError):
+        size = ()
+    if len(size) != 3 or min(size) < 1 or max(size) > 1 << 24 or size[0] * size[1] * size[2] >= 1 << 31:
+        raise ValueError(f"{what} must be three positive integers (D, H, W) with fewer than 2^31 nodes, got {size!r}")
+    return size
+
+
+def tps_system(control, lambd=0.):
+    """The matrix of the reference's TPS.fit (fsg_tps_system_f64): control (B,n,3) or (n,3) -> (B,n+4,n+4) or (n+4,n+4) fp64,
+    u(|c_i - c_j|) + lambd I with u(r) = r^2 log(r + 1e-6), bordered by [1 | c], its transpose and zeros.  Distances are sums of
+    squared differences in fp64 (ours, not the reference's fp32 ra + rb - 2 ab): symmetric bit for bit, the diagonal exactly
+    lambd."""
+    c, squeeze = _tps_points(control, "control", "tps_system")
+    _need_gpu(c)
+    B, n, _ = c.shape
+    if n > 32764:
+        raise ValueError(f"tps_system: n={n} control points, the kernel serves n <= 32764")
+    with torch.no_grad():
+        cc = _f32c(c)
+        A = torch.empty(B, n + 4, n + 4, dtype=torch.float64, device=cc.device)
+        with torch.cuda.device(cc.device):
+            _lib.call("fsg_tps_system_f64", _p(cc), B, n, float(lambd), _p(A), _stream())
+    return A[0] if squeeze else A
+
+
+def tps_fit(control, values, lambd=0., fit_batch=32):
+    """TPS.fit for a batch: control (B,n,3), values (B,n,C) (or (n,3), (n,C)) -> theta (B,n+4,C) fp64, the n spline weights and
+    the four affine rows.  The systems come from `tps_system`, the solve is torch's batched fp64 linalg.solve, `fit_batch`
+    systems at a time (100 systems of 1028^2 in fp64 are 0.85 GB).  n >= 4 points not in one plane (or lambd > 0 with
+    distinct points) make the system regular; a singular one raises as linalg.solve does."""
+    c, squeeze = _tps_points(control, "control", "tps_fit")
+    if not torch.is_tensor(values) or not values.is_floating_point() or values.dim() != control.dim() \
+            or values.shape[:-1] != control.shape[:-1]:
+        got = f"{tuple(values.shape)} {values.dtype}" if torch.is_tensor(values) else type(values).__name__
+        raise ValueError(f"tps_fit: values must be floating-point {tuple(control.shape[:-1])} + (C,), got {got}")
+    v = values[None] if squeeze else values
+    if not 1 <= v.shape[2] <= TPS_MAX_CHANNELS:
+        raise ValueError(f"tps_fit: C={v.shape[2]} channels, the kernels serve 1 <= C <= {TPS_MAX_CHANNELS}")
+    if isinstance(fit_batch, bool) or not isinstance(fit_batch, int) or fit_batch < 1:
+        raise ValueError(f"tps_fit: fit_batch must be a positive integer, got {fit_batch!r}")
+    _need_gpu(c, v)
+    _tps_same_device("tps_fit", c, v)
+    B, n, C = v.shape
+    with torch.no_grad():
+        theta = torch.empty(B, n + 4, C, dtype=torch.float64, device=c.device)
+        for b0 in range(0, B, fit_batch):
+            A = tps_system(c[b0:b0 + fit_batch], lambd)
+            rhs = torch.zeros(A.shape[0], n + 4, C, dtype=torch.float64, device=c.device)
+            rhs[:, :n] = v[b0:b0 + fit_batch]
+            theta[b0:b0 + fit_batch] = torch.linalg.solve(A, rhs)
+    return theta[0] if squeeze else theta
+
+
+def tps_eval(queries, control, theta):
+    """TPS.z (fsg_tps_eval_f32): the spline theta (B,n+4,C) fp64 on control (B,n,3) at queries (B,Q,3) -> (B,Q,C) fp32.
+    `queries` may instead be a lattice size (D1,H1,W1): the nodes of an align_corners=True lattice over [-1,1]^3 in
+    (z,y,x)-major order with (x,y,z) coordinates, as thin_plate_dense builds them with affine_grid -- no coordinate tensor is
+    read; -> (B, D1 H1 W1, C).  u and the sum over the control points are fp64.  2-D inputs are a batch of one."""
+    c, squeeze = _tps_points(control, "control", "tps_eval")
+    B, n, _ = c.shape
+    th = _tps_theta(theta, B, n, "tps_eval")
+    C = th.shape[2]
+    if torch.is_tensor(queries):
+        q, _ = _tps_points(queries, "queries", "tps_eval")
+        if q.shape[0] != B or queries.dim() != control.dim():
+            raise ValueError(f"tps_eval: queries {tuple(queries.shape)} and control {tuple(control.shape)} do not share a batch")
+        _need_gpu(q, c, th)
+        _tps_same_device("tps_eval", q, c, th)
+        Q, lattice = q.shape[1], (0, 0, 0)
+    else:
+        lattice = _tps_size(queries, "tps_eval: a lattice")
+        q, Q = None, lattice[0] * lattice[1] * lattice[2]
+        _need_gpu(c, th)
+        _tps_same_device("tps_eval", c, th)
+    with torch.no_grad():
+        cc, tc = _f32c(c), th.detach().contiguous()
+        qc = _f32c(q) if q is not None else None
+        out = torch.empty(B, Q, C, dtype=torch.float32, device=cc.device)
+        with torch.cuda.device(cc.device):
+            _lib.call("fsg_tps_eval_f32", _p(qc), _p(cc), _p(tc), B, Q, n, C, *lattice, _p(out), _stream())
+    return out[0] if squeeze else out
+
+
+def tps_grid_sample(grid, control, theta, size, step=4):
+    """What the reference reads out of its dense displacement field, without the field (fsg_tps_grid_sample_f32):
+    F.grid_sample(align_corners=False, zeros padding) at grid (B,Q,3) (x,y,z in [-1,1], x along the last axis) of the trilinear
+    align_corners=True upsample to size = (D,H,W) of the spline theta (B,n+4,C) on control (B,n,3), evaluated on the lattice
+    (D//step, H//step, W//step) -> (B,Q,C) fp32.  A sample depends on at most 3 coarse nodes per axis; the spline is evaluated
+    at those only.  A sample whose taps all lie outside the volume is exactly 0.  2-D inputs are a batch of one."""
+    c, squeeze = _tps_points(control, "control", "tps_grid_sample")
+    B, n, _ = c.shape
+    th = _tps_theta(theta, B, n, "tps_grid_sample")
+    g, _ = _tps_points(grid, "grid", "tps_grid_sample")
+    if g.shape[0] != B or grid.dim() != control.dim():
+        raise ValueError(f"tps_grid_sample: grid {tuple(grid.shape)} and control {tuple(control.shape)} do not share a batch")
+    size = _tps_size(size, "tps_grid_sample: size")
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"tps_grid_sample: step must be a positive integer, got {step!r}")
+    if min(size) < step:
+        raise ValueError(f"tps_grid_sample: every axis of size {size} must hold at least step={step} voxels (the coarse lattice "
+                         f"would be empty)")
+    coarse = tuple(s // step for s in size)
+    _need_gpu(g, c, th)
+    _tps_same_device("tps_grid_sample", g, c, th)
+    Q, C = g.shape[1], th.shape[2]
+    with torch.no_grad():
+        gc, cc, tc = _f32c(g), _f32c(c), th.detach().contiguous()
+        out = torch.empty(B, Q, C, dtype=torch.float32, device=cc.device)
+        with torch.cuda.device(cc.device):
+            _lib.call("fsg_tps_grid_sample_f32", _p(gc), _p(cc), _p(tc), B, Q, n, C, *size, *coarse, _p(out), _stream())
+    return out[0] if squeeze else out
+
+
 # ------------------------------------------------------------------ weighted sample elimination (open3d's sample_points_poisson_disk)
 def _per_item_radius(v, B, dev, name):
     """a scalar or a (B,) tensor / sequence -> (B,) fp32 on `dev`"""

@@ -9,7 +9,8 @@ result is scored against the instance's mesh and moving cloud.
 
 The reference runs this as a Python double loop (objects x instances: one kNN interpolation, one open3d point-to-mesh query and
 one pytorch3d Chamfer call per pair) and clusters with sklearn on the CPU.  Here every object is ONE call of each of
-`interpolate_displacements_weighted_knn`, `inverse_affine_transform_batch`, `functional.point_mesh_distance` and
+`interpolate_displacements_weighted_knn` (or, with interpolation_mode='tps', `interpolate_displacements_tps`: one batched spline
+fit and one fused sampling kernel, csrc/tps.hip), `inverse_affine_transform_batch`, `functional.point_mesh_distance` and
 `functional.chamfer_nn` over all its instances, and 'kmeans' is one `functional.kmeans` over all objects (csrc/kmeans.hip).
 
 Kept from the reference: the displacements are interpolated from the moved cloud; the evaluation always uses the cloud with the
@@ -17,8 +18,9 @@ affine pre-registration undone, whatever `undo_affine_reg` says; `std` is torch'
 every transform dict gets ['is_applied'] = not undo_affine_reg; 'parzen' raises NotImplementedError, an unknown mode ValueError.
 Different: 'kmeans' is seeded by farthest point sampling instead of k-means++ on numpy's random stream and an emptied cluster
 keeps its centre (see functional.kmeans) -- deterministic, but not sklearn's centres; `plot_dir` and `show` are accepted and
-ignored (no matplotlib); OPTICS ('cluster') and the thin-plate-spline interpolation ('tps') are not part of this package and
-raise NotImplementedError; the file-reading `__main__` driver is not mirrored.
+ignored (no matplotlib); OPTICS ('cluster') is not part of this package and raises NotImplementedError; 'tps' needs
+`fixed_img_shape` = (D, H, W) and raises NotImplementedError without it (the reference fails there as well; a grid-free spline is
+out of scope); the file-reading `__main__` driver is not mirrored.
 
 numpy arrays in give numpy arrays out, with the evaluation as CPU tensors, as in the reference (the work still runs on the current
 GPU); GPU tensors in give GPU tensors out."""
@@ -27,7 +29,8 @@ import torch
 
 from .. import functional as F_hip
 from ..metrics import _device, _mesh_arrays
-from .point_cloud_registration import INTERPOLATION_MODES, interpolate_displacements_weighted_knn
+from .point_cloud_registration import (INTERPOLATION_MODES, TPS_NEEDS_SHAPE, interpolate_displacements_tps,
+                                       interpolate_displacements_weighted_knn)
 
 CORRESPONDENCE_MODES = ["kmeans", "cluster", "simple"]
 
@@ -95,14 +98,22 @@ def _mesh_distances(points, meshes):
     return torch.cat([F_hip.point_mesh_distance(points[i:i + 1], v[None], f) for i, (v, f) in enumerate(arrays)])
 
 
-def object_correspondences(centroids, moved, displacements, moving, meshes, scale, rotation, translation, undo_affine_reg=True):
+def object_correspondences(centroids, moved, displacements, moving, meshes, scale, rotation, translation, undo_affine_reg=True,
+                           interpolation_mode='knn', img_shape=None):
     """One object, all instances at once: centroids (Q,3) the sampling locations, moved / displacements (I,P,3) the registered
     clouds and their displacements, moving (I,Pm,3) the original clouds, one mesh per instance, the pre-registration as
     scale (I,), rotation (I,3,3), translation (I,3) -> (corresponding points (I,Q,3) in the dtype of the centroids, mean, std,
-    hd, cf (I,) fp32).  GPU tensors."""
+    hd, cf (I,) fp32).  GPU tensors.  interpolation_mode 'tps' needs img_shape = (D, H, W)."""
     I = moved.shape[0]
     sample = centroids[None].expand(I, -1, -1).contiguous()
-    interpolated = interpolate_displacements_weighted_knn(moved.float(), displacements.float(), sample.float())
+    if interpolation_mode == 'tps':
+        if img_shape is None:
+            raise NotImplementedError(TPS_NEEDS_SHAPE.format("object_correspondences", "img_shape"))
+        interpolated = interpolate_displacements_tps(moved.float(), displacements.float(), sample.float(), img_shape)
+    elif interpolation_mode == 'knn':
+        interpolated = interpolate_displacements_weighted_knn(moved.float(), displacements.float(), sample.float())
+    else:
+        raise ValueError(f"interpolation_mode must be one of {INTERPOLATION_MODES}, got {interpolation_mode!r}")
     sampled = sample - interpolated.to(sample.dtype)
     not_affine = inverse_affine_transform_batch(sampled.double(), scale, rotation, translation).to(sample.dtype)
     dist = _mesh_distances(not_affine.float(), meshes).double()
@@ -122,7 +133,8 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
     form `metrics._mesh_arrays` takes; all_moving_pcs, all_moved_pcs, all_displacements (instances, objects, P, 3);
     all_prereg_transforms one dict per instance with 'scale', 'rotation', 'translation' ->
     (corresponding_pcs (instances, sum of points, 3), all_prereg_transforms, corresponding_fixed_pc (sum of points, 3),
-    labels (sum of points,), {'mean', 'std', 'hd', 'cf'} each (instances, objects) fp32)."""
+    labels (sum of points,), {'mean', 'std', 'hd', 'cf'} each (instances, objects) fp32).  fixed_img_shape = (D, H, W) is read by
+    interpolation_mode='tps' only."""
     if mode == 'parzen':
         raise NotImplementedError('Parzen mode is unfinished')
     if mode == 'cluster':
@@ -130,11 +142,10 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
                                   "this package (a sequential reachability ordering, no GPU form here); use 'kmeans' or 'simple'")
     if mode not in CORRESPONDENCE_MODES:
         raise ValueError(f'No mode named {mode}.')
-    if interpolation_mode == 'tps':
-        raise NotImplementedError("data_set_correspondences(interpolation_mode='tps'): the thin-plate-spline interpolation of the "
-                                  "reference is out of scope of this package; use 'knn'")
-    if interpolation_mode != 'knn':
+    if interpolation_mode not in INTERPOLATION_MODES:
         raise ValueError(f"interpolation_mode must be one of {INTERPOLATION_MODES}, got {interpolation_mode!r}")
+    if interpolation_mode == 'tps' and fixed_img_shape is None:
+        raise NotImplementedError(TPS_NEEDS_SHAPE.format("data_set_correspondences", "fixed_img_shape"))
     as_numpy = not torch.is_tensor(all_moved_pcs)
     dev = _device() if as_numpy else all_moved_pcs.device
     moved = _clouds(all_moved_pcs, "all_moved_pcs", 4, as_numpy, dev)
@@ -159,7 +170,7 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
         for obj in range(O):
             out = object_correspondences(centroids[obj], moved[:, obj], disp[:, obj], moving[:, obj],
                                          [all_moving_meshes[i][obj] for i in range(I)], scale, rotation, translation,
-                                         undo_affine_reg)
+                                         undo_affine_reg, interpolation_mode, fixed_img_shape)
             pcs.append(out[0])
             evaluation.append(out[1:])
         for t in all_prereg_transforms:

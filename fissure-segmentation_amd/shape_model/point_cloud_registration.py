@@ -19,8 +19,18 @@ exponent relative to each fixed point's nearest moving point and so keeps the ma
 of this package, and parity with it is unpinned: the yardstick is the fp64 restatement in tests/cpd_oracle.py.
 
 numpy arrays go in the way the reference passes them and come out as numpy (the work still runs on the current GPU); torch
-tensors must be on a GPU and stay there.  A 2-D Y is a batch of one, returned without the batch axis.  Not reproduced either:
-the thin-plate-spline interpolation mode (out of scope, it raises).
+tensors must be on a GPU and stay there.  A 2-D Y is a batch of one, returned without the batch axis.
+
+The thin-plate-spline interpolation (:24-89 `TPS` and `thin_plate_dense`, :119-133 `interpolate_displacements_tps`) is here too.
+The reference fits a spline on the moved cloud, evaluates it on a lattice of a quarter of the image's resolution, upsamples that
+to a dense displacement field of the whole image and reads the sample points out of it with grid_sample.  Here the system matrix
+is one kernel (fp64, functional.tps_system), the solve torch's batched fp64 linalg.solve, and the samples come from one fused
+kernel (functional.tps_grid_sample) that evaluates the spline only at the at most 27 lattice nodes a sample depends on: no
+lattice, no field.  `thin_plate_dense` still returns the field for callers that want it.  The reference's conventions are kept,
+odd as they are: step = 4, lambd = 0.1; coordinates and displacements are normalised by [W-1, H-1, D-1] of img_shape = (D, H, W);
+the lattice and the field are sized from shape = (W, H, D), so that grid_sample's x runs along an axis of D voxels; the sampled
+displacements are un-normalised by [H-1, W-1, D-1].  Without an image shape 'tps' raises: the reference fails there too, and a
+grid-free variant (the spline evaluated at the samples themselves) is out of scope.
 
 `register_all` (:191-297) is the driver that turns a data set of meshes into the arrays `data_set_correspondences` consumes.
 The reference rests it on open3d; here `TriangleMesh.sample_points_poisson_disk` is `mesh.Meshes.sample_points_poisson_disk`
@@ -33,6 +43,7 @@ import numbers
 
 import numpy as np
 import torch
+from torch.nn import functional as F
 
 from .. import functional as F_hip
 from ..mesh import Meshes
@@ -40,6 +51,85 @@ from ..metrics import _device, _mesh_arrays
 
 INTERPOLATION_MODES = ['knn', 'tps']
 CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
+TPS_STEP, TPS_LAMBDA = 4, 0.1   # point_cloud_registration.py:129: the lattice has a quarter of the resolution; the ridge of the fit
+
+
+class TPS:
+    """point_cloud_registration.py:24-67, the reference's signatures.  c (n,3) control points, f (n,C) their values (C <= 4),
+    theta (n+4,C): n spline weights, then the affine rows; every method also takes a leading batch axis.  `fit` and `z` run on
+    the kernels of csrc/tps.hip and need GPU tensors; theta is fp64 (the weights sum to zero and cancel by a factor of
+    thousands in `z`), `z` returns fp32.  `d` and `u` are the plain formulas for callers that want them; the kernels do not
+    go through them."""
+
+    @staticmethod
+    def fit(c, f, lambd=0.):
+        return F_hip.tps_fit(c, f, lambd)
+
+    @staticmethod
+    def d(a, b):
+        """pairwise distances (.., Na, Nb) as roots of sums of squared differences (the reference expands ra + rb - 2 ab)"""
+        d2 = torch.zeros(*a.shape[:-1], b.shape[-2], dtype=a.dtype, device=a.device)
+        for k in range(a.shape[-1]):   # one coordinate at a time: no (Na, Nb, 3) intermediate
+            d2 += (a[..., :, None, k] - b[..., None, :, k]).square()
+        return d2.sqrt()
+
+    @staticmethod
+    def u(r):
+        return (r ** 2) * torch.log(r + 1e-6)
+
+    @staticmethod
+    def z(x, c, theta):
+        return F_hip.tps_eval(x, c, theta)
+
+
+def thin_plate_dense(x1, y1, shape, step, lambd=.0, unroll_step_size=2 ** 12):
+    """point_cloud_registration.py:70-89: the spline through values y1 (B,n,C) at control points x1 (B,n,3) in [-1,1]^3 (x along
+    the last axis of `shape`), evaluated on the align_corners=True lattice (D//step, H//step, W//step) of shape = (D,H,W) and
+    upsampled trilinearly (align_corners=True) -> the dense field (B,D,H,W,C) fp32.  The lattice nodes are implied (the kernel
+    reads no coordinate tensor); the upsampling is torch's.  The reference fits x1[0] only; here every item of the batch gets
+    its field.  `unroll_step_size` is accepted and ignored (the kernel needs no chunking).  For callers that want the field:
+    `interpolate_displacements_tps` does not build it."""
+    D, H, W = (int(s) for s in shape)
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1 or min(D, H, W) < step:
+        raise ValueError(f"thin_plate_dense: step={step!r} must be a positive integer no larger than any axis of shape {tuple(shape)}")
+    if x1.dim() != 3 or y1.dim() != 3:
+        raise ValueError(f"thin_plate_dense: expected x1 (B,n,3) and y1 (B,n,C), got {tuple(x1.shape)} and {tuple(y1.shape)}")
+    D1, H1, W1 = D // step, H // step, W // step
+    with torch.no_grad():
+        theta = F_hip.tps_fit(x1, y1, lambd)
+        y2 = F_hip.tps_eval((D1, H1, W1), x1, theta)
+        y2 = y2.view(-1, D1, H1, W1, y2.shape[-1]).permute(0, 4, 1, 2, 3)
+        return F.interpolate(y2, (D, H, W), mode='trilinear', align_corners=True).permute(0, 2, 3, 4, 1)
+
+
+def interpolate_displacements_tps(existing_points, values_at_existing_points, interpolation_points, img_shape):
+    """point_cloud_registration.py:119-133 for a batch: existing_points and values_at_existing_points (B,n,3),
+    interpolation_points (B,Q,3) in voxel units of an image img_shape = (D,H,W) -> displacements (B,Q,3) fp32 (2-D inputs: a
+    batch of one, returned 2-D).  The reference's conventions, see the module docstring; any Q, also 1 (the reference's
+    squeeze() breaks there).  A sample outside the volume reads grid_sample's zero padding.  GPU tensors in, GPU tensor out."""
+    e, v, q = existing_points, values_at_existing_points, interpolation_points
+    try:
+        D, H, W = (int(s) for s in img_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"interpolate_displacements_tps: img_shape must be (D, H, W), got {img_shape!r}") from None
+    if min(D, H, W) < TPS_STEP:
+        raise ValueError(f"interpolate_displacements_tps: every axis of img_shape {(D, H, W)} must hold at least {TPS_STEP} voxels")
+    for name, t in (("existing_points", e), ("values_at_existing_points", v), ("interpolation_points", q)):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3) or t.dim() != e.dim() or t.shape[-1] != 3 or not t.is_floating_point():
+            raise ValueError(f"interpolate_displacements_tps: {name} must be a floating-point (points, 3) or (batch, points, 3) "
+                             f"tensor like the others, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if e.shape != v.shape or e.shape[:-2] != q.shape[:-2]:
+        raise ValueError(f"interpolate_displacements_tps: expected existing (..,n,3), values (..,n,3) and query (..,Q,3), got "
+                         f"{tuple(e.shape)}, {tuple(v.shape)} and {tuple(q.shape)}")
+    F_hip._need_gpu(e, v, q)
+    with torch.no_grad():
+        e, v, q = e.float(), v.float(), q.float()
+        norm = torch.tensor([W - 1, H - 1, D - 1], dtype=torch.float32, device=e.device)
+        normalize = lambda grid: (grid / norm) * 2   # noqa: E731  (no -1 for displacements)
+        control = normalize(e) - 1
+        theta = F_hip.tps_fit(control, normalize(v), TPS_LAMBDA)
+        sampled = F_hip.tps_grid_sample(normalize(q) - 1, control, theta, size=(W, H, D), step=TPS_STEP)
+        return (sampled * torch.tensor([H - 1, W - 1, D - 1], dtype=torch.float32, device=e.device)) / 2
 
 
 def _as_tensor(a, name):
@@ -276,16 +366,19 @@ def interpolate_displacements_weighted_knn(existing_points, values_at_existing_p
     return out.view(*q.shape[:-1], C)
 
 
+TPS_NEEDS_SHAPE = ("{}(interpolation_mode='tps') without {}: the thin-plate-spline interpolation samples a displacement field on the "
+                   "image grid, and a grid-free variant is out of scope of this package; pass the image shape (D, H, W) or use 'knn'")
+
+
 def inverse_transformation_at_sampled_points(deformed_pc_np, moving_displacements, sample_point_cloud, img_shape=None,
                                              interpolation_mode='knn'):
     """point_cloud_registration.py:151-177: the displacements of the moved cloud, interpolated at the sample locations and
     subtracted from them -> the sample points in the moving cloud's space.  numpy in, numpy out (as the reference); GPU
-    tensors in, GPU tensor out.  Only the 'knn' interpolation is part of this package."""
-    if interpolation_mode == 'tps':
-        raise NotImplementedError("inverse_transformation_at_sampled_points(interpolation_mode='tps'): the thin-plate-spline "
-                                  "interpolation of the reference is out of scope of this package; use 'knn'")
-    if interpolation_mode != 'knn':
+    tensors in, GPU tensor out.  'knn' needs no image shape; 'tps' needs img_shape = (D, H, W) and raises without it."""
+    if interpolation_mode not in INTERPOLATION_MODES:
         raise ValueError(f"interpolation_mode must be one of {INTERPOLATION_MODES}, got {interpolation_mode!r}")
+    if interpolation_mode == 'tps' and img_shape is None:
+        raise NotImplementedError(TPS_NEEDS_SHAPE.format("inverse_transformation_at_sampled_points", "img_shape"))
     as_numpy = isinstance(sample_point_cloud, np.ndarray)
     if as_numpy:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -293,7 +386,10 @@ def inverse_transformation_at_sampled_points(deformed_pc_np, moving_displacement
                                   for a in (deformed_pc_np, moving_displacements, sample_point_cloud))
     else:
         deformed, disp, sample = deformed_pc_np, moving_displacements, sample_point_cloud
-    interpolated = interpolate_displacements_weighted_knn(deformed, disp, sample)
+    if interpolation_mode == 'tps':
+        interpolated = interpolate_displacements_tps(deformed, disp, sample, img_shape)
+    else:
+        interpolated = interpolate_displacements_weighted_knn(deformed, disp, sample)
     if as_numpy:
         return sample_point_cloud - interpolated.cpu().numpy().astype(sample_point_cloud.dtype)
     return sample - interpolated.to(sample.dtype)

@@ -1467,6 +1467,33 @@ int fsg_segment_jitter_extend_f32(const float *xyz, const int32_t *offset, const
 int fsg_fps_start_f32(const float *xyz, const int32_t *offset, const int32_t *new_offset, const int32_t *start, int b, int n,
                       float *tmp, int32_t *idx, fsg_stream_t stream);
 
+/* Thin-plate-spline interpolation of displacements (csrc/tps.hip).  Serves the 'tps' interpolation mode of the reference,
+ * shape_model/point_cloud_registration.py:24-67 (class TPS), :70-89 (thin_plate_dense) and :119-133
+ * (interpolate_displacements_tps), which fits on n control points, evaluates on a (D/4, H/4, W/4) lattice, upsamples to the
+ * dense (D, H, W, 3) field and grid_samples Q points out of it.  u(r) = r^2 log(r + 1e-6).  B independent items, DEVICE
+ * pointers, contiguous rows; control (B, n, 3) fp32; theta (B, n + 4, C) fp64 = n spline weights, then the affine rows
+ * (1, x, y, z); 1 <= C <= 4; B <= 65535.
+ * fsg_tps_system_f64: the matrix of TPS.fit (:32-44) -> A (B, n + 4, n + 4) fp64: u(|c_i - c_j|) off the diagonal, lambda ON it,
+ *   then [1 | c], its transpose and a zero block.  Distances are sums of squared differences, in fp64 (NOT the reference's
+ *   ra + rb - 2 ab in fp32): the matrix is symmetric bit for bit.  1 <= n <= 32764.  The solve is the caller's.
+ * fsg_tps_eval_f32: TPS.z (:63-67) -> out (B, Q, C) fp32 = a0 + a1 x + a2 y + a3 z + sum_j w_j u(|q - c_j|).  query (B, Q, 3)
+ *   fp32, or NULL for the nodes of an align_corners=True lattice (D1, H1, W1) with Q = D1 H1 W1 (thin_plate_dense's x2, :75):
+ *   node q = (iz H1 + iy) W1 + ix lies at (x, y, z) = (c(ix, W1), c(iy, H1), c(iz, D1)), c(i, L) = -1 + 2 i / (L - 1) rounded to
+ *   fp32, 0 for L = 1.  One lane per query; u and the sum over j (ascending) are fp64.
+ * fsg_tps_grid_sample_f32: :86-87 and :131-132 without the lattice and without the field -> out (B, Q, C) fp32, what
+ *   grid_sample(align_corners=False, zeros padding) at grid (B, Q, 3) fp32 (x, y, z in [-1, 1]; x runs along W) reads from the
+ *   trilinear align_corners=True upsample to (D, H, W) of the spline on the lattice (D1, H1, W1) above.  Per axis the two fine
+ *   taps and their two coarse nodes each fold into weights of at most 3 consecutive nodes (fp64); the spline is evaluated at
+ *   those 27 nodes as in fsg_tps_eval_f32 and the products are added in node order (z slowest).  A sample whose taps all fall
+ *   outside gives exactly 0.  1 <= coarse <= fine <= 2^24 per axis.
+ * No atomics, no workspace, nothing read on the host: the same inputs give the same bits, an item's output does not depend on
+ * the batch, and every entry can be captured in a graph.  Bad arguments are FSG_ERR_ARG. */
+int fsg_tps_system_f64(const float *control, int B, int n, double lambd, double *A, fsg_stream_t stream);
+int fsg_tps_eval_f32(const float *query, const float *control, const double *theta, int B, int Q, int n, int C, int D1, int H1,
+                     int W1, float *out, fsg_stream_t stream);
+int fsg_tps_grid_sample_f32(const float *grid, const float *control, const double *theta, int B, int Q, int n, int C, int D, int H,
+                            int W, int D1, int H1, int W1, float *out, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1796,3 +1796,102 @@ if "dsegae" in which:
     out_path = os.environ.get("FSG_DSEGAE_BENCH_OUT", os.path.join(ROOT, "profiles", "dseg_ae_bench.jsonl"))
     with open(out_path, "a") as fh:
         fh.write("\n".join(lines) + "\n")
+if "tps" in which:
+    # Thin-plate-spline interpolation (csrc/tps.hip) at the workload's shape: B = 32 (instance, object) pairs, n = Q = 1024, image
+    # 256 x 256 x 320.  The fit split into assembly and solve; the sparse route (functional.tps_grid_sample) and the whole
+    # interpolate_displacements_tps; thin_plate_dense for ONE pair (a 251 MB field); and, in the same run, the reference-shaped
+    # dense route for one pair as a torch composition on the device (fp32 fit with expanded distances, the lattice in chunks of
+    # 4096, F.interpolate, F.grid_sample), with peak extra memory and what the routes differ by.  Writes profiles/tps_bench.jsonl.
+    import json
+    import numpy as np
+    import tps_oracle as to
+    from fissure_segmentation_amd.shape_model import point_cloud_registration as pcr
+    lines = []
+
+    def emit_line(rec):
+        lines.append(json.dumps(rec))
+        print("TPS " + lines[-1], flush=True)
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 1)
+
+    def us(fn, iters=10, warm=2):
+        med, mn = timeit(fn, iters=iters, warm=warm)
+        return round(med, 1)
+
+    B, n, Q, shape = 32, 1024, 1024, (320, 256, 256)   # img_shape = (D, H, W)
+    D, H, W = shape
+    cases = [to.voxel_case(shape, n, Q, 500 + b) for b in range(B)]
+    e, v, q = (torch.from_numpy(np.stack([c[k] for c in cases])).to(dev) for k in range(3))
+    norm = torch.tensor([W - 1, H - 1, D - 1], dtype=torch.float32, device=dev)
+    control, values, grid = e / norm * 2 - 1, v / norm * 2, q / norm * 2 - 1
+    size = (W, H, D)
+
+    def u32(r):
+        return r.square() * torch.log(r + 1e-6)
+
+    def d32(a, b):
+        return (a.square().sum(1)[:, None] + b.square().sum(1)[None, :] - 2.0 * (a @ b.t())).clamp_(min=0.0).sqrt()
+
+    def dense_composition(c, f, g):
+        """one pair, the reference's shape of the computation, fp32 on the device"""
+        A = torch.zeros(n + 4, n + 4, device=dev)
+        A[:n, :n] = u32(d32(c, c)) + to.LAMBDA * torch.eye(n, device=dev)
+        A[:n, n] = A[n, :n] = 1.0
+        A[:n, n + 1:] = c
+        A[n + 1:, :n] = c.t()
+        rhs = torch.zeros(n + 4, 3, device=dev)
+        rhs[:n] = f
+        theta = torch.linalg.solve(A, rhs)
+        D1, H1, W1 = (s // to.STEP for s in size)
+        x2 = torch.nn.functional.affine_grid(torch.eye(3, 4, device=dev)[None], (1, 1, D1, H1, W1), align_corners=True).view(-1, 3)
+        y2 = torch.cat([u32(d32(x2[j:j + 4096], c)) @ theta[:n] + theta[n] + x2[j:j + 4096] @ theta[n + 1:]
+                        for j in range(0, len(x2), 4096)])
+        y2 = y2.view(1, D1, H1, W1, 3).permute(0, 4, 1, 2, 3)
+        field = torch.nn.functional.interpolate(y2, size, mode="trilinear", align_corners=True)
+        out = torch.nn.functional.grid_sample(field, g.view(1, -1, 1, 1, 3), align_corners=False)
+        return out.reshape(3, -1).t()
+
+    with torch.no_grad():
+        A = F.tps_system(control, to.LAMBDA)
+        rhs = torch.zeros(B, n + 4, 3, dtype=torch.float64, device=dev)
+        rhs[:, :n] = values
+        theta = F.tps_fit(control, values, to.LAMBDA)
+        sparse = F.tps_grid_sample(grid, control, theta, size)
+        rec = dict(kernel="tps", B=B, n=n, Q=Q, img_shape=list(shape), lattice=[s // to.STEP for s in size],
+                   assembly_us=us(lambda: F.tps_system(control, to.LAMBDA)),
+                   solve_us=us(lambda: torch.linalg.solve(A, rhs), iters=5, warm=1),
+                   fit_us=us(lambda: F.tps_fit(control, values, to.LAMBDA), iters=5, warm=1),
+                   grid_sample_us=us(lambda: F.tps_grid_sample(grid, control, theta, size)),
+                   interpolate_displacements_tps_us=us(lambda: pcr.interpolate_displacements_tps(e, v, q, shape), iters=5, warm=1),
+                   fit_peak_extra_MiB=peak_extra(lambda: F.tps_fit(control, values, to.LAMBDA)),
+                   grid_sample_peak_extra_MiB=peak_extra(lambda: F.tps_grid_sample(grid, control, theta, size)))
+        emit_line(rec)
+        del A, rhs
+        one = lambda: pcr.thin_plate_dense(control[:1], values[:1], size, to.STEP, to.LAMBDA)   # noqa: E731
+        lattice_us = us(lambda: F.tps_eval(tuple(s // to.STEP for s in size), control[:1], theta[:1]))
+        comp = lambda: dense_composition(control[0], values[0], grid[0])   # noqa: E731
+        field = one()
+        via_field = torch.nn.functional.grid_sample(field.permute(0, 4, 1, 2, 3), grid[:1].view(1, -1, 1, 1, 3),
+                                                    align_corners=False).reshape(3, -1).t()
+        del field
+        ref = comp()
+        scale = float(sparse[0].abs().max())
+        emit_line(dict(kernel="tps_one_pair", n=n, Q=Q, img_shape=list(shape),
+                       sparse_route_fit_plus_sample_us=us(lambda: F.tps_grid_sample(grid[:1], control[:1], F.tps_fit(control[:1], values[:1], to.LAMBDA), size), iters=5, warm=1),
+                       lattice_eval_us=lattice_us, thin_plate_dense_us=us(one, iters=5, warm=1),
+                       reference_shaped_dense_route_us=us(comp, iters=5, warm=1),
+                       thin_plate_dense_peak_extra_MiB=peak_extra(one), reference_shaped_dense_route_peak_extra_MiB=peak_extra(comp),
+                       sparse_vs_thin_plate_dense_plus_grid_sample=float((sparse[0] - via_field).abs().max()) / scale,
+                       sparse_vs_reference_shaped_fp32_route=float((sparse[0] - ref).abs().max()) / scale,
+                       note="errors relative to the largest sampled displacement of the pair"))
+    out_path = os.environ.get("FSG_TPS_BENCH_OUT", os.path.join(ROOT, "profiles", "tps_bench.jsonl"))
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
