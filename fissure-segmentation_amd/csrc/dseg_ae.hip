@@ -14,7 +14,7 @@ constexpr int PTILE = 1024;           // points of a tile
 constexpr int PR = PTILE / PT;        // rounds of a tile: point j = t PTILE + r PT + tid
 constexpr int PW = PT / 64;           // waves
 constexpr int PSLOT = PR * PW;        // (round, wave) slots of a tile, in ascending point order
-constexpr int MAXL = 16;
+constexpr int MAXL = FSG_PARTITION_MAX_LABELS;
 
 // the label of point i relative to first_label, or -1 outside [0, L)
 __device__ __forceinline__ int rel_label(const void *__restrict__ lab, int kind, long i, int first, int L) {

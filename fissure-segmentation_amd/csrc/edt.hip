@@ -35,9 +35,9 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int TJ = NT / 64;          // line positions per workgroup (one per wave)
-constexpr int MAX_DIM = 16384;
+constexpr int MAX_DIM = FSG_EDT_MAX_DIM;
 constexpr int MAX_GRID = 1 << 20;    // grid-strided launches
-constexpr int MAX_PLANES = 64;
+constexpr int MAX_PLANES = FSG_EDT_MAX_LABELS;
 
 template <typename T>
 struct Arith;

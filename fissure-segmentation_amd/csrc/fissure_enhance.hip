@@ -35,7 +35,7 @@
 
 namespace {
 
-constexpr int MAXR = 4;   // derivation sigma <= 1 (radius int(4 sigma + 0.5)); DiscreteGaussian of variance <= ~1.3
+constexpr int MAXR = FSG_ENHANCE_MAX_TAP_RADIUS;   // derivation sigma <= 1 (radius int(4 sigma + 0.5)); DiscreteGaussian of variance <= ~1.3
 constexpr int TZ = 8, TY = 8, TX = 32, NT = 256;
 constexpr size_t LDS_MAX = 160 * 1024;
 

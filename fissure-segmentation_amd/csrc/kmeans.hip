@@ -30,7 +30,7 @@ namespace {
 
 constexpr int kThreads = 256;   // assign: points of one tile, one per lane
 constexpr int kChunk = 1024;    // centres staged at a time (16 KiB as float4)
-constexpr int kMaxK = 4096;
+constexpr int kMaxK = FSG_KMEANS_MAX_K;
 constexpr int kRed = 1024;      // threads of the per-item kernels (prepare, finalize)
 constexpr int kBlocksTarget = 2048;   // workgroups of one assign launch the tiles are spread over (about 8 per CU)
 
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(kRed) void kmeans_finalize_kernel(float *__restrict
 }
 
 int check(const char *who, int B, int n, int K) {
-    FSG_REQUIRE(B >= 0 && B <= 65535 && n >= 1 && n <= (1 << 24) && K >= 1 && K <= kMaxK && K <= n,
+    FSG_REQUIRE(B >= 0 && B <= 65535 && n >= 1 && n <= FSG_KMEANS_MAX_POINTS && K >= 1 && K <= kMaxK && K <= n,
                 "%s: bad shape B=%d n=%d K=%d (1 <= K <= min(n, %d), n <= 2^24, B <= 65535)", who, B, n, K, kMaxK);
     return FSG_OK;
 }

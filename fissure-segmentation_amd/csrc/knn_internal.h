@@ -5,16 +5,16 @@
 #include "fsg_common.h"
 
 // ---- debug / cross-check bits of `flags`, above the public FSG_KNN_FIX_DIAG 1, _DROP_FIRST 2, _FORCE_ROWS 4, _FORCE_MFMA 8.
-// Tests, tools and bench.py pass the numbers: the values are fixed.  _lib.py mirrors the names.
+// The values are the FSG_KNN_DBG_* defines of include/fsg_hip.h (tests, tools and bench.py pass the numbers: they are fixed).
 enum : int {
-    KNN_DBG_HALF_CHUNKS = 1 << 11,   // 2048        two-phase kernel: its 512-candidate-chunk variant (k + drop <= 32, > 16 channels)
-    KNN_DBG_TWO_PHASE = 1 << 21,     // 2097152     the two-phase kernel (knn_rows_mfma.hip) instead of the split kernel
-    KNN_DBG_ALL_SLOW = 1 << 22,      // 4194304     split kernel: every query through the slow exact path
-    KNN_DBG_STATS = 1 << 25,         // 33554432    split kernel: nominee statistics (fsg_debug_knn_split_stats)
-    KNN_DBG_STAMPS = 1 << 28,        // 268435456   split kernel: cycle stamps (fsg_debug_knn_split_stamps / _refine_stamps);
-                                     //             forces the two-launch form unless KNN_DBG_ONE_LAUNCH is set too
-    KNN_DBG_ONE_LAUNCH = 1 << 29,    // 536870912   split kernel: the one-launch (monolithic) kernel
-    KNN_DBG_BF16 = 1 << 30,          // 1073741824  split kernel: the bf16 three-product form above 4 channels
+    KNN_DBG_HALF_CHUNKS = FSG_KNN_DBG_HALF_CHUNKS,   // two-phase kernel: 512-candidate chunks (k + drop <= 32, > 16 channels)
+    KNN_DBG_TWO_PHASE = FSG_KNN_DBG_TWO_PHASE,       // the two-phase kernel (knn_rows_mfma.hip) instead of the split kernel
+    KNN_DBG_ALL_SLOW = FSG_KNN_DBG_ALL_SLOW,         // split kernel: every query through the slow exact path
+    KNN_DBG_STATS = FSG_KNN_DBG_STATS,               // split kernel: nominee statistics (fsg_debug_knn_split_stats)
+    KNN_DBG_STAMPS = FSG_KNN_DBG_STAMPS,             // split kernel: cycle stamps (fsg_debug_knn_split_stamps / _refine_stamps);
+                                                     // forces the two-launch form unless KNN_DBG_ONE_LAUNCH is set too
+    KNN_DBG_ONE_LAUNCH = FSG_KNN_DBG_ONE_LAUNCH,     // split kernel: the one-launch (monolithic) kernel
+    KNN_DBG_BF16 = FSG_KNN_DBG_BF16,                 // split kernel: the bf16 three-product form above 4 channels
 };
 // every bit a public entry accepts; anything else is FSG_ERR_ARG (a stale tool fails loudly instead of timing the default path)
 constexpr int KNN_FLAGS_ALL = FSG_KNN_FIX_DIAG | FSG_KNN_DROP_FIRST | FSG_KNN_FORCE_ROWS | FSG_KNN_FORCE_MFMA | KNN_DBG_HALF_CHUNKS |

@@ -43,7 +43,7 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr unsigned long long NOKEY = ~0ull;
-constexpr int ORIENT_MAX_N = 1 << 20;     // 20 bits per endpoint in the key
+constexpr int ORIENT_MAX_N = FSG_ORIENT_MAX_POINTS;     // 20 bits per endpoint in the key
 
 __device__ __forceinline__ int ld32(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st32(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -40,7 +40,7 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAXR = 8;
+constexpr int MAXR = FSG_MORPH_MAX_RADIUS;
 constexpr int MAX_TAPS = (2 * MAXR + 1) * (2 * MAXR + 1);
 constexpr int MAX_BLOCKS = 4096;   // grid-strided launches
 

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(BLOCK) void pcl_normals_kernel(const float *__restr
 extern "C" int fsg_pcl_normals_f32(const float *xyz, const int32_t *idx, const int32_t *offset, int b, int n, int K,
                                    int disambiguate, float *normals, float *curvatures, float *frames, fsg_stream_t stream) {
     FSG_REQUIRE(xyz && idx && offset && normals && curvatures, "fsg_pcl_normals_f32: NULL pointer");
-    FSG_REQUIRE(b > 0 && n >= 0 && n <= (1 << 28) && K >= 2 && K <= 64, "fsg_pcl_normals_f32: bad shape b=%d n=%d K=%d", b, n, K);
+    FSG_REQUIRE(b > 0 && n >= 0 && n <= (1 << 28) && K >= 2 && K <= FSG_PCL_NORMALS_MAX_K, "fsg_pcl_normals_f32: bad shape b=%d n=%d K=%d", b, n, K);
     if (n == 0) return FSG_OK;
     const int lanes = K <= 32 ? 4 : 8;
     const dim3 grid(fsg_cdiv((long)n * lanes, BLOCK)), block(BLOCK);

@@ -27,8 +27,8 @@
 
 namespace {
 
-enum { PW_STORE = 1, PW_STATS = 2, PW_SEL = 4, PW_BWDSTATS = 8, PW_BIAS = 16 };
-enum { PRO_NONE = 0, PRO_BNACT = 1, PRO_BNBWD = 2 };
+enum { PW_STORE = FSG_PW_STORE, PW_STATS = FSG_PW_STATS, PW_SEL = FSG_PW_SEL, PW_BWDSTATS = FSG_PW_BWDSTATS, PW_BIAS = FSG_PW_BIAS };
+enum { PRO_NONE = FSG_PW_PRO_NONE, PRO_BNACT = FSG_PW_PRO_BNACT, PRO_BNBWD = FSG_PW_PRO_BNBWD };
 
 // B operand image of a (N, K) matrix W(n, k) = W[n * sn + k * sk] * scale:  blocks [nb][ks][piece][lane] of 16 bytes, lane
 // (n = 32 nb + (lane & 31), k = 16 ks + 8 (lane >> 5) + 0..7); rows >= N and columns >= K read as zero.  `ks0`/`KS`: the

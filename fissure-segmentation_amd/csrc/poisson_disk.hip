@@ -45,7 +45,7 @@
 
 namespace {
 
-constexpr int kMaxM = 16384;          // 14 index bits of the key; 8 kMaxM bytes of weights are 128 KiB of LDS
+constexpr int kMaxM = FSG_SAMPLE_ELIMINATION_MAX_POINTS;          // 14 index bits of the key; 8 kMaxM bytes of weights are 128 KiB of LDS
 constexpr int kCoordLdsMax = 8128;    // 20 M bytes of weights and coordinates + the static slots <= 160 KiB
 constexpr int kMaxThreads = 1024;
 constexpr int kMaxWaves = kMaxThreads / 64;

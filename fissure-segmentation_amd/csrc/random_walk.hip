@@ -30,7 +30,7 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAXK = 8;
+constexpr int MAXK = FSG_RW_MAX_LABELS;
 constexpr int MAX_BLOCKS = 1024;   // streaming launches are grid-strided; this is also the number of partials per system
 constexpr uint8_t ST_OUTSIDE = 0, ST_UNKNOWN = 1, ST_SEED0 = 2;   // ST_SEED0 + (label - 1); 255: a seed of no system
 

@@ -320,9 +320,9 @@ int fsg_mbconv3d_fwd_f32(const float *x, const float *w1, const float *s1, const
     FSG_REQUIRE(x != y, "fsg_mbconv3d_fwd_f32: x and y must differ");
     FSG_REQUIRE(B >= 1 && D >= 1 && H >= 1 && W >= 1, "fsg_mbconv3d_fwd_f32: bad shape: B=%d D=%d H=%d W=%d must be >= 1", B, D, H, W);
     FSG_REQUIRE((long)D * H * W < (1L << 31), "fsg_mbconv3d_fwd_f32: bad shape: D H W must be < 2^31");
-    FSG_REQUIRE(Cin >= 1 && Cin <= 64, "fsg_mbconv3d_fwd_f32: Cin=%d outside 1..64", Cin);
-    FSG_REQUIRE(Cmid >= 16 && Cmid <= 384 && Cmid % 16 == 0, "fsg_mbconv3d_fwd_f32: Cmid=%d must be a multiple of 16 in 16..384", Cmid);
-    FSG_REQUIRE(Cout >= 1 && Cout <= 64, "fsg_mbconv3d_fwd_f32: Cout=%d outside 1..64", Cout);
+    FSG_REQUIRE(Cin >= 1 && Cin <= FSG_MBCONV_MAX_CIN, "fsg_mbconv3d_fwd_f32: Cin=%d outside 1..64", Cin);
+    FSG_REQUIRE(Cmid >= 16 && Cmid <= FSG_MBCONV_MAX_CMID && Cmid % 16 == 0, "fsg_mbconv3d_fwd_f32: Cmid=%d must be a multiple of 16 in 16..384", Cmid);
+    FSG_REQUIRE(Cout >= 1 && Cout <= FSG_MBCONV_MAX_COUT, "fsg_mbconv3d_fwd_f32: Cout=%d outside 1..64", Cout);
     FSG_REQUIRE(stride == 1 || stride == 2, "fsg_mbconv3d_fwd_f32: stride=%d must be 1 or 2", stride);
     FSG_REQUIRE(!first || Cin == 1, "fsg_mbconv3d_fwd_f32: the dense first layer takes one input channel, got Cin=%d", Cin);
     FSG_REQUIRE(!residual || (!first && stride == 1 && Cin == Cout),

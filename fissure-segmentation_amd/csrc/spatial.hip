@@ -34,7 +34,7 @@ constexpr int NT = 256;
 constexpr int PAD = FSG_BSPLINE_PAD;
 constexpr int MAX_GRID = 1 << 16;
 constexpr int MAX_RADIUS = 1020;          // int(4 * 255 + 0.5)
-constexpr float MAX_SIGMA = 255.f;
+constexpr float MAX_SIGMA = FSG_ELASTIC_MAX_SIGMA;
 constexpr int GB = 4;                    // outputs per thread along the filtered axis
 constexpr float POLE = -0.26794919243112270647f;   // sqrt(3) - 2
 

@@ -31,7 +31,7 @@
 namespace {
 
 constexpr int MAX_NT = 1024;
-constexpr int MAX_WORDS = 8192;   // words of one slice: 64 KiB per buffer; 512 x 1024 and 1024 x 512 voxels still fit
+constexpr int MAX_WORDS = FSG_THIN_MAX_WORDS;   // words of one slice: 64 KiB per buffer; 512 x 1024 and 1024 x 512 voxels still fit
 
 struct Slice {
     int H, W, WW, n;   // n = H * WW words

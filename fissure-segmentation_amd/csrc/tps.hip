@@ -23,7 +23,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 512;        // control points staged at a time: 8 KiB of float4 + 16 KiB of weights
-constexpr int kMaxC = 4;
+constexpr int kMaxC = FSG_TPS_MAX_CHANNELS;
 constexpr int kSlots = 32;         // lanes per sample in grid_sample; 27 carry a node
 constexpr int kSamples = kThreads / kSlots;
 

@@ -22,7 +22,7 @@
 
 namespace {
 
-constexpr int MAXR = 4;                // Gaussian radius N / 2 (sigma <= 2.66)
+constexpr int MAXR = FSG_FRONTEND_MAX_TAP_RADIUS;   // Gaussian radius N / 2 (sigma <= 2.66)
 constexpr int MAXN = 2 * MAXR + 1;
 constexpr int MAXCH = 12;
 constexpr int MAXDIL = 4;

@@ -1263,8 +1263,8 @@ def pw_linear(x, image, N, bias=None, tile=0):
         _lib.call("fsg_pw_linear_f32", _p(x), x.stride(0), _p(image), _p(bias), _p(y), N, M, N, K, tile, _stream())
     return y
 
-PW_STORE, PW_STATS, PW_SEL, PW_BWDSTATS, PW_BIAS = 1, 2, 4, 8, 16
-PRO_NONE, PRO_BNACT, PRO_BNBWD = 0, 1, 2
+PW_STORE, PW_STATS, PW_SEL, PW_BWDSTATS, PW_BIAS = _lib.PW_STORE, _lib.PW_STATS, _lib.PW_SEL, _lib.PW_BWDSTATS, _lib.PW_BIAS
+PRO_NONE, PRO_BNACT, PRO_BNBWD = _lib.PW_PRO_NONE, _lib.PW_PRO_BNACT, _lib.PW_PRO_BNBWD
 
 
 def _ptr(t):
@@ -2025,7 +2025,7 @@ def mesh_labelmap_cover(verts, faces, shape, spacing, validate=True):
 
 
 # ------------------------------------------------------------------ DG-SSM: shape-model decode + similarity transform
-SSM_MAX_MODES = 64
+SSM_MAX_MODES = _lib.SSM_MAX_MODES
 
 
 class _SSMDecodeAffine(torch.autograd.Function):
@@ -2253,7 +2253,7 @@ def kmeans(points, n_clusters=None, init='fps', max_iter=300, tol=1e-4, start=0,
 
 
 # ------------------------------------------------------------------ thin-plate splines (shape_model/point_cloud_registration.py:24-89,119-133)
-TPS_MAX_CHANNELS = 4   # csrc/tps.hip: kMaxC
+TPS_MAX_CHANNELS = _lib.TPS_MAX_CHANNELS
 
 
 def _tps_points(t, name, who):
@@ -2543,7 +2543,7 @@ def fps(xyz, offset, new_offset, m):
 
 
 # ------------------------------------------------------------------ DSEG-AE glue (csrc/dseg_ae.hip)
-PARTITION_MAX_LABELS = 16   # csrc/dseg_ae.hip: MAXL
+PARTITION_MAX_LABELS = _lib.PARTITION_MAX_LABELS
 
 
 def label_partition(labels, x, num_labels, first_label=1):
@@ -3277,7 +3277,7 @@ def mind_keypoints(img, kp, dilation, sigma, shifts, outch, box, mean=None):
 
 
 # ------------------------------------------------------------------ Hessian fissure enhancement (csrc/fissure_enhance.hip)
-MAX_TAP_RADIUS = 4   # of the derivative taps (derivation sigma <= 1) and of the keypoint smoothing taps
+MAX_TAP_RADIUS = _lib.ENHANCE_MAX_TAP_RADIUS   # of the derivative taps (derivation sigma <= 1) and of the keypoint smoothing taps
 
 
 def gaussian_derivative_taps(sigma, order, truncate=4.0):
@@ -3777,8 +3777,8 @@ def relabel_by_size(labels, n):
 
 
 # ------------------------------------------------------------------ Euclidean distance transform (csrc/edt.hip)
-EDT_MAX_DIM = 16384          # csrc/edt.hip: MAX_DIM (3 * 16383^2 fits an int32)
-EDT_MAX_LABELS = 64          # csrc/edt.hip: MAX_PLANES
+EDT_MAX_DIM = _lib.EDT_MAX_DIM
+EDT_MAX_LABELS = _lib.EDT_MAX_LABELS
 EDT_INT_INF = 2 ** 31 - 1    # the int32 mode's +inf
 
 
@@ -3933,7 +3933,7 @@ def labelmap_distances(a, b, spacing=(1., 1., 1.)):
 
 # ------------------------------------------------------------------ voxel patch augmentation, resampling (csrc/spatial.hip)
 BSPLINE_PAD = _lib.BSPLINE_PAD      # edge-replicated samples the prefilter adds on every side (scipy's own for mode='nearest')
-ELASTIC_MAX_SIGMA = 255.0           # csrc/spatial.hip: MAX_SIGMA (the tap table in LDS)
+ELASTIC_MAX_SIGMA = _lib.ELASTIC_MAX_SIGMA
 _LABEL_KINDS = {torch.uint8: _lib.LABEL_U8, torch.int32: _lib.LABEL_I32, torch.int64: _lib.LABEL_I64}
 
 
@@ -4769,7 +4769,7 @@ def reg_objective(disp, feat_fix, feat_mov, lambda_weight, cost_scale=12., chann
 
 
 # ------------------------------------------------------------------ voxel CNN inference (csrc/seg_cnn.hip)
-MBCONV_MAX_CIN, MBCONV_MAX_CMID, MBCONV_MAX_COUT = 64, 384, 64   # include/fsg_hip.h: fsg_mbconv3d_fwd_f32
+MBCONV_MAX_CIN, MBCONV_MAX_CMID, MBCONV_MAX_COUT = _lib.MBCONV_MAX_CIN, _lib.MBCONV_MAX_CMID, _lib.MBCONV_MAX_COUT
 
 
 def _ndhwc(x):

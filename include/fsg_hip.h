@@ -33,8 +33,15 @@ extern "C" {
 #define FSG_KNN_FORCE_ROWS 4 /* use the general "rows in LDS" kernel even where the MFMA kernel applies (tests) */
 
 #define FSG_KNN_FORCE_MFMA 8 /* (experimental kernels: libfsg_hip_experiments.so only; rejected by libfsg_hip.so)     */
-/* Higher bits of `flags` are debug / cross-check selectors for tests and tools (csrc/knn_internal.h lists them, _lib.py mirrors the
- * names); a bit that list does not know is FSG_ERR_ARG. */
+/* Higher bits of `flags` are debug / cross-check selectors for tests and tools (csrc/knn_internal.h has the meanings); a bit that
+ * is not listed here is FSG_ERR_ARG.  Tests, tools and bench.py pass the numbers: the values are fixed. */
+#define FSG_KNN_DBG_HALF_CHUNKS (1 << 11)
+#define FSG_KNN_DBG_TWO_PHASE (1 << 21)
+#define FSG_KNN_DBG_ALL_SLOW (1 << 22)
+#define FSG_KNN_DBG_STATS (1 << 25)
+#define FSG_KNN_DBG_STAMPS (1 << 28)
+#define FSG_KNN_DBG_ONE_LAUNCH (1 << 29)
+#define FSG_KNN_DBG_BF16 (1 << 30)
 
 #define FSG_KNN_MAX_K 64
 
@@ -738,6 +745,14 @@ int fsg_pw_linear_bf16(const float *A, int64_t lda, const void *image, const flo
  *   rows_per_cloud to be multiples of the tile's rows.  Only the combinations the head uses are instantiated
  *   (FSG_ERR_UNSUPPORTED otherwise).
  */
+#define FSG_PW_PRO_NONE 0 /* the prologue codes `pro` above */
+#define FSG_PW_PRO_BNACT 1
+#define FSG_PW_PRO_BNBWD 2
+#define FSG_PW_STORE 1 /* the epilogue bits `epi` above */
+#define FSG_PW_STATS 2
+#define FSG_PW_SEL 4
+#define FSG_PW_BWDSTATS 8
+#define FSG_PW_BIAS 16
 typedef struct fsg_pw_rowgemm_args {
     const float *A1, *Y1, *A2;
     int64_t lda1, lda2;
@@ -925,6 +940,7 @@ int fsg_pw_rowgemm_scatter_f32(const fsg_pw_rowgemm_args *args, const void *sort
  *   the whole volume (out (B, nch, D, H, W)) or for K voxels kp (K, 3) int64 (z, y, x) of ONE volume (out (nch, K));
  *   coordinates outside the volume are clamped).  Both run the same code, so the values are bitwise equal.
  */
+#define FSG_FRONTEND_MAX_TAP_RADIUS 4 /* `weights`: N <= 2 * 4 + 1 taps */
 int fsg_foerstner_dist_f32(const float *img, int B, int D, int H, int W, const float *weights, int N, float *out,
                            fsg_stream_t stream);
 int fsg_nms_keypoints(const float *dist, const uint8_t *mask, int B, int D, int H, int W, int d, float thresh, float *maxout,
@@ -955,6 +971,7 @@ int fsg_mind_eval_kp_f32(const float *img, int D, int H, int W, int dilation, in
  *   keypoint_extraction.py:134-141): separable smoothing with per-axis taps wz, wy, wx (odd counts, at most 9; axis order
  *   0, 1, 2; replicate padding), then out = s > thresh ? s : 0 and flags (bytes) = s > thresh.  Either output may be NULL.
  */
+#define FSG_ENHANCE_MAX_TAP_RADIUS 4 /* k1 / k2 and wz / wy / wx: at most 2 * 4 + 1 taps each (derivation sigma <= 1) */
 int fsg_fissure_enhance_f32(const float *img, const uint8_t *mask, int B, int D, int H, int W, const float *k1, const float *k2,
                             int N, float mu, float sigma_hu, float *out, float *planeness, float *hu_weight,
                             fsg_stream_t stream);
@@ -998,6 +1015,8 @@ int fsg_cpd_estep_f32(const float *X, int64_t x_batch_stride, const float *TY, c
  * Outputs of step and assign, each may be NULL: counts (B, K) int32; stats (B, 2) fp64 = inertia (the sum of the squared
  *   distances of this assignment), squared centroid shift; info (B, 4) int32 = labels changed, empty clusters, iterations
  *   run, active. */
+#define FSG_KMEANS_MAX_K 4096           /* K: the accumulators of the clusters live in LDS */
+#define FSG_KMEANS_MAX_POINTS (1 << 24) /* n: the index range of a point */
 size_t fsg_kmeans_workspace_bytes(int B, int n, int K);
 int fsg_kmeans_prepare_f32(const float *points, const float *centroids, int B, int n, int K, double tol, void *workspace,
                            size_t workspace_bytes, fsg_stream_t stream);
@@ -1027,6 +1046,7 @@ int fsg_kmeans_assign_f32(const float *points, const float *centroids, int32_t *
  * n_keep == M writes 0 .. M-1 and removes nothing.  Two launches (weights over (item, tile); one workgroup per item for the
  * rounds), no atomics, nothing read on the host, capturable in a graph; the same inputs give the same bits on every run,
  * alone or in a batch. */
+#define FSG_SAMPLE_ELIMINATION_MAX_POINTS 16384 /* M: 14 index bits in the selection key, the weights of one item fill LDS */
 size_t fsg_sample_elimination_workspace_bytes(int B, int M);
 int fsg_sample_elimination_f32(const float *points, const float *radii, int B, int M, int n_keep, int32_t *keep, int32_t *order,
                                void *workspace, size_t workspace_bytes, fsg_stream_t stream);
@@ -1061,6 +1081,7 @@ int fsg_sample_elimination_f32(const float *points, const float *radii, int B, i
  */
 #define FSG_RW_BINARY 0
 #define FSG_RW_INTENSITY 1
+#define FSG_RW_MAX_LABELS 8 /* K */
 size_t fsg_random_walk_workspace_bytes(int B, int K, int D, int H, int W);
 int fsg_random_walk_prep(const void *im, int mode, const void *labels, int labels_are_i32, const uint8_t *mask, int B, int K, int D,
                          int H, int W, void *workspace, size_t workspace_bytes, int32_t *stop_iter, float *relres,
@@ -1096,6 +1117,7 @@ int fsg_lobes_to_fissures_u8(const uint8_t *lobes, int B, int D, int H, int W, i
  * Relabel: out[i] = lut[b][labels[i]] (0 for a label outside 0..lut_len-1); lut (B, lut_len) int32; out int32 or int64.
  * Bad arguments (a radius outside 0..8, a connectivity other than 6 / 18 / 26, a NULL pointer, a short workspace, 2^31 or more
  *   voxels) are FSG_ERR_ARG. */
+#define FSG_MORPH_MAX_RADIUS 8 /* rz, ry, rx of fsg_ball_dilate_bits */
 int fsg_bits_pack_u8(const uint8_t *vol, int B, int D, int H, int W, int value, uint64_t *bits, fsg_stream_t stream);
 int fsg_bits_unpack_u8(const uint64_t *bits, int B, int D, int H, int W, uint8_t *vol, fsg_stream_t stream);
 int fsg_bits_window(const uint64_t *in, int B, int Di, int Hi, int Wi, int oz, int oy, int ox, int Do, int Ho, int Wo,
@@ -1128,6 +1150,8 @@ int fsg_relabel_lut_i32(const int32_t *labels, int B, int64_t n_per_item, const 
  *   where keep (V) uint8, if given, is 0 (process_lung_mask.py:88).
  * Bad arguments (a dimension above 16384, 2^31 voxels or more, a spacing that is not positive, a NULL pointer, a short
  *   workspace) are FSG_ERR_ARG. */
+#define FSG_EDT_MAX_DIM 16384 /* D, H, W: 3 * 16383^2 fits an int32 */
+#define FSG_EDT_MAX_LABELS 64 /* K of fsg_edt_nearest_label */
 size_t fsg_edt_workspace_bytes(int B, int D, int H, int W, int with_indices);
 int fsg_edt_sq_i32(const uint64_t *bits, int B, int D, int H, int W, int32_t *out_d2, int32_t *out_idx, void *workspace,
                    size_t workspace_bytes, fsg_stream_t stream);
@@ -1149,6 +1173,7 @@ int fsg_edt_nearest_label(const void *d2, int is_f32, int K, int64_t V, const in
  *   depend on its neighbours or its batch.
  * A slice holds at most fsg_thin_max_words() = 8192 words, H * ceil(W / 64) (512 x 1024 or 1024 x 512 voxels); a larger one, a
  *   NULL plane or a non-positive dimension is FSG_ERR_ARG. */
+#define FSG_THIN_MAX_WORDS 8192 /* what fsg_thin_max_words() returns: 64 KiB of LDS per copy of the slice */
 int fsg_thin_max_words(void);
 int fsg_thin_bits(const uint64_t *in, int B, int D, int H, int W, uint64_t *out, int32_t *iterations, fsg_stream_t stream);
 
@@ -1177,6 +1202,7 @@ int fsg_thin_bits(const uint64_t *in, int B, int D, int H, int W, uint64_t *out,
  *   coordinate outside [0, n - 1] on any axis gives 0 (scipy's mode='constant', cval=0).  out_seg (B, Cs, pd, ph, pw) int64.
  *   mirror (B, 3) uint8 or NULL: a nonzero flag stores the item's output reversed along that axis.
  * Volumes (padded) and patches hold fewer than 2^31 voxels, B <= 65535.  Bad arguments are FSG_ERR_ARG. */
+#define FSG_ELASTIC_MAX_SIGMA 255.0f /* sigma of fsg_gauss_axis_f32: its tap table lives in LDS */
 #define FSG_BSPLINE_PAD 12
 #define FSG_LABEL_U8 0
 #define FSG_LABEL_I32 1
@@ -1319,6 +1345,7 @@ int fsg_mc_emit_labels_i32(const int32_t *labels, int first_label, int B, int D,
  * Rank-deficient C (coincident, collinear, planar neighbours) gives finite orthonormal vectors.  A non-finite coordinate makes
  * the rows that list it non-finite and nothing else.  fp32, no atomics: the same input gives the same bits.
  * 2 <= K <= 64, b >= 1, n <= 2^28; bad shapes and NULL pointers are FSG_ERR_ARG before any launch. */
+#define FSG_PCL_NORMALS_MAX_K 64 /* K: what fsg_knn_segment_f32 can deliver */
 int fsg_pcl_normals_f32(const float *xyz, const int32_t *idx, const int32_t *offset, int b, int n, int K, int disambiguate,
                         float *normals, float *curvatures, float *frames, fsg_stream_t stream);
 
@@ -1356,6 +1383,7 @@ int fsg_pcl_normals_f32(const float *xyz, const int32_t *idx, const int32_t *off
  *   face_keep (NULL = all) is set; vert_used marks the vertices of surviving faces.  The caller scans the flags it wants to
  *   keep (exclusive prefix sums vert_new, face_new, int64); compact writes survivors in their old order, faces re-indexed and
  *   LOCAL to their mesh (int64), normals alongside when given. */
+#define FSG_ORIENT_MAX_POINTS (1 << 20) /* n of fsg_orient_normals_f32: 20 bits per endpoint in the edge key */
 size_t fsg_orient_normals_workspace_bytes(int n, int K);
 int fsg_orient_normals_f32(const float *xyz, const float *normals, const int32_t *idx, const int32_t *offset, int b, int n, int K,
                            void *workspace, size_t workspace_bytes, float *out, int8_t *signs, int32_t *comp, fsg_stream_t stream);
@@ -1428,6 +1456,9 @@ int fsg_reg_objective_f16(const float *disp, const void *feat_fix, const void *f
  *   wsum (B, 1, D, H, W).  One launch per patch in the order of `starts` on `stream`: overlapping patches add in that order.
  * fsg_patch_finalize_f32: out (B, K, D, H, W) = softmax over K of sum / wsum (the reference applies its activation to every
  *   patch AND to the normalised sum); out may be sum. */
+#define FSG_MBCONV_MAX_CIN 64
+#define FSG_MBCONV_MAX_CMID 384
+#define FSG_MBCONV_MAX_COUT 64
 int fsg_mbconv3d_fwd_f32(const float *x, const float *w1, const float *s1, const float *b1, const float *wd, const float *s2,
                          const float *b2, const float *w3, const float *s3, const float *b3, int B, int Cin, int Cmid, int Cout,
                          int D, int H, int W, int stride, int first, int residual, float *y, fsg_stream_t stream);
@@ -1457,6 +1488,7 @@ int fsg_patch_finalize_f32(const float *sum, const float *wsum, int B, int K, in
  *   global memory with tmp (n) fp32 as the running distances.  Same arithmetic and tie rule as fsg_fps_f32 (largest distance,
  *   then lowest index): with start NULL the same idx bit for bit.
  * No atomics: the same bits on every run, a group the same alone and in a batch.  Bad arguments are FSG_ERR_ARG. */
+#define FSG_PARTITION_MAX_LABELS 16 /* L of fsg_label_partition */
 size_t fsg_label_partition_workspace_bytes(int B, int N, int L);
 int fsg_label_partition(const void *labels, int label_kind, const float *x, int B, int C, int N, int first_label, int L,
                         int32_t *counts, int32_t *offset, float *xyz, int32_t *src, void *workspace, size_t workspace_bytes,
@@ -1488,6 +1520,7 @@ int fsg_fps_start_f32(const float *xyz, const int32_t *offset, const int32_t *ne
  *   outside gives exactly 0.  1 <= coarse <= fine <= 2^24 per axis.
  * No atomics, no workspace, nothing read on the host: the same inputs give the same bits, an item's output does not depend on
  * the batch, and every entry can be captured in a graph.  Bad arguments are FSG_ERR_ARG. */
+#define FSG_TPS_MAX_CHANNELS 4 /* C */
 int fsg_tps_system_f64(const float *control, int B, int n, double lambd, double *A, fsg_stream_t stream);
 int fsg_tps_eval_f32(const float *query, const float *control, const double *theta, int B, int Q, int n, int C, int D1, int H1,
                      int W1, float *out, fsg_stream_t stream);

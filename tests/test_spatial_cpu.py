@@ -1,5 +1,6 @@
 """CPU tests of the voxel patch augmentation port (csrc/spatial.hip): the oracle's own claims (tests/spatial_oracle.py), the
 scenes the GPU tests use, the declarations of the new entry points, the host-side helpers and the argument checks."""
+import ctypes
 import os
 import re
 
@@ -96,7 +97,7 @@ def test_header_and_binding_declare_the_same_entry_points():
         m = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
         assert m, f"{name} is not declared in include/fsg_hip.h"
         args, res = _lib.SIGNATURES[name]
-        assert len(m.group(1).split(",")) == len(args) and res is _lib._I
+        assert len(m.group(1).split(",")) == len(args) and res is ctypes.c_int
         assert hasattr(_lib.lib, name)
     assert re.search(r"#define FSG_BSPLINE_PAD (\d+)", header).group(1) == str(_lib.BSPLINE_PAD) == str(so.PAD)
     kinds = [int(re.search(rf"#define FSG_LABEL_{k} (\d+)", header).group(1)) for k in ("U8", "I32", "I64")]
