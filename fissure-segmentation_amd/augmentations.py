@@ -86,7 +86,7 @@ class Transform3d:
 
 def _sample_transform(x, sample, affine):
     """x (B,C,N) on the GPU -> (B,C,S): column subset (`sample` (B,S) int64 or None) and/or affine map of rows 0..2"""
-    from . import _lib
+    from ._launch import launch
     if not x.is_cuda:
         raise RuntimeError("the HIP sampling/augmentation path needs its input on the GPU")
     x = x.to(torch.float32).contiguous()
@@ -102,9 +102,7 @@ def _sample_transform(x, sample, affine):
             raise ValueError(f"affine must be (B,12), got {tuple(affine.shape)}")
     out = torch.empty(B, C, S, dtype=torch.float32, device=x.device)
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    with torch.cuda.device(x.device):
-        _lib.call("fsg_sample_transform_f32", P(x), B, C, N, P(sample), S, P(affine), P(out),
-                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    launch(x.device, "fsg_sample_transform_f32", P(x), B, C, N, P(sample), S, P(affine), P(out))
     return out
 
 

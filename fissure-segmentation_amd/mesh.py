@@ -25,7 +25,7 @@ from torch.multiprocessing.reductions import StorageWeakRef
 
 from . import _lib
 from . import functional as F_hip
-from .functional import _amp_bwd, _amp_fwd, _f32c, _need_gpu, _p, _stream
+from ._launch import _amp_bwd, _amp_fwd, _f32c, _need_gpu, _p, launch
 
 
 # ---------------------------------------------------------------------------------------------------------- topology
@@ -407,9 +407,8 @@ def _mesh_sample_raw(verts, u, st):
     face = torch.empty(N, n, dtype=torch.int32, device=dev)
     w = torch.empty(N, n, 3, dtype=torch.float32, device=dev)
     ws = _lib.workspace("fsg_mesh_sample", N, st.max_F, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("fsg_mesh_sample_f32", _p(vc), _p(st.faces), _p(st.sdesc), N, st.max_F, _p(uc), n, _p(pts), _p(face),
-                  _p(w), _p(ws), ws.numel(), _stream())
+    launch(dev, "fsg_mesh_sample_f32", _p(vc), _p(st.faces), _p(st.sdesc), N, st.max_F, _p(uc), n, _p(pts), _p(face),
+           _p(w), _p(ws), ws.numel())
     return pts, face, w, ws.view(torch.float64).view(N, st.max_F)
 
 
@@ -430,9 +429,8 @@ class _MeshSample(torch.autograd.Function):
         st = ctx.st
         gc = _f32c(g)
         gv = torch.empty(st.total_verts, 3, dtype=torch.float32, device=gc.device)
-        with torch.cuda.device(gc.device):
-            _lib.call("fsg_mesh_sample_bwd_f32", _p(gc), _p(face), _p(w), _p(st.faces), _p(st.sdesc), st.N, st.max_V, ctx.n,
-                      _p(gv), _stream())
+        launch(gc.device, "fsg_mesh_sample_bwd_f32", _p(gc), _p(face), _p(w), _p(st.faces), _p(st.sdesc), st.N, st.max_V, ctx.n,
+               _p(gv))
         return gv, None, None
 
 
@@ -463,9 +461,8 @@ class _MeshReg(torch.autograd.Function):
         mean = torch.empty(3, dtype=torch.float32, device=dev)
         grads = torch.empty(3, st.total_verts, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         ws = _lib.workspace("fsg_mesh_reg", st.N, st.max_V, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("fsg_mesh_reg_f32", _p(vc), st.total_verts, _p(st.desc), st.N, st.max_V, _p(st.nbr_off), _p(st.nbr),
-                      _p(st.pairs), _p(st.inc_off), _p(st.inc), _p(terms), _p(mean), _p(grads), _p(ws), ws.numel(), _stream())
+        launch(dev, "fsg_mesh_reg_f32", _p(vc), st.total_verts, _p(st.desc), st.N, st.max_V, _p(st.nbr_off), _p(st.nbr),
+               _p(st.pairs), _p(st.inc_off), _p(st.inc), _p(terms), _p(mean), _p(grads), _p(ws), ws.numel())
         ctx.N = st.N
         if grads is not None:
             ctx.save_for_backward(grads)

@@ -1,0 +1,431 @@
+"""Shape-model ops: DG-SSM decode, the CPD E-step, k-means, thin-plate splines, weighted sample elimination."""
+import torch
+
+from .. import _lib
+from .._launch import _amp_bwd, _amp_fwd, _f32c, _need_gpu, _p, launch
+from .packed import fps
+
+
+# ------------------------------------------------------------------ DG-SSM: shape-model decode + similarity transform
+SSM_MAX_MODES = _lib.SSM_MAX_MODES
+
+
+class _SSMDecodeAffine(torch.autograd.Function):
+    """shape_model/ssm.py:74-83 + models/dg_ssm.py:133-135 (compose_transform, transform_points): one launch forward, two
+    backward; the decoded shape is recomputed in the backward, mean and eigenvectors are frozen (ssm.py:33)"""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, w, mean, evec, v, s, tr):
+        wc, mc, ec = _f32c(w), _f32c(mean), _f32c(evec)
+        B, M = wc.shape
+        P = mc.numel() // 3
+        affine = v is not None
+        vc, sc, tc = (_f32c(v), _f32c(s), _f32c(tr)) if affine else (None, None, None)
+        out = torch.empty(B, P, 3, dtype=torch.float32, device=w.device)
+        launch(w.device, "fsg_ssm_decode_fwd_f32", _p(wc), _p(mc), _p(ec), _p(vc), _p(sc), _p(tc), B, P, M, _p(out))
+        ctx.save_for_backward(wc, mc, ec, vc, sc)
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, g):
+        wc, mc, ec, vc, sc = ctx.saved_tensors
+        B, M = wc.shape
+        P = mc.numel() // 3
+        dev = wc.device
+        dw = torch.empty_like(wc)
+        dv, ds, dt = (torch.empty(B, 3, dtype=torch.float32, device=dev) for _ in range(3)) if vc is not None else (None,) * 3
+        ws = _lib.workspace("fsg_ssm_decode_bwd", B, P, M, device=dev)
+        launch(dev, "fsg_ssm_decode_bwd_f32", _p(_f32c(g)), _p(wc), _p(mc), _p(ec), _p(vc), _p(sc), B, P, M, _p(dw), _p(dv),
+               _p(ds), _p(dt), _p(ws), ws.numel())
+        return dw, None, None, dv, ds, dt
+
+
+def ssm_decode_affine(w, mean, evec, v=None, s=None, tr=None):
+    """w (B,M) mode weights, mean (3P) [or (1,3P)], evec (3P,M) [or (1,3P,M)] -> (B,P,3): the decoded shapes
+    mean + evec w, moved -- when v, s, tr (B,3) are given -- by x -> (x R(v)) * s + tr with R = so3_exp_map(v) in the
+    row-vector convention of augmentations.Transform3d.  Differentiable in w, v, s, tr; s may be (B,1)."""
+    _need_gpu(w, mean, evec, v, s, tr)
+    evec = evec.reshape(-1, evec.shape[-1])
+    mean = mean.reshape(-1)
+    if w.dim() != 2 or w.shape[1] != evec.shape[1] or mean.numel() != evec.shape[0] or mean.numel() % 3 != 0:
+        raise ValueError(f"expected w (B,M), mean (3P), evec (3P,M), got {tuple(w.shape)}, {tuple(mean.shape)}, "
+                         f"{tuple(evec.shape)}")
+    if (v is None) != (s is None) or (v is None) != (tr is None):
+        raise ValueError("v, s and tr come together (all or none)")
+    if v is not None:
+        B = w.shape[0]
+        if tuple(v.shape) != (B, 3) or tuple(tr.shape) != (B, 3) or s.dim() != 2 or s.shape[0] != B or s.shape[1] not in (1, 3):
+            raise ValueError(f"expected v, tr (B,3) and s (B,3) or (B,1), got {tuple(v.shape)}, {tuple(tr.shape)}, "
+                             f"{tuple(s.shape)}")
+        s = s.expand(B, 3)
+    return _SSMDecodeAffine.apply(w, mean, evec, v, s, tr)
+
+
+# ------------------------------------------------------------------ coherent point drift, E-step (shape_model/point_cloud_registration.py)
+def cpd_estep(X, TY, sigma2, w=0.):
+    """The reductions of CPD's responsibility matrix P (M, N) that the M-steps need, without P (fsg_cpd_estep_f32).
+
+    X (B,N,3) fixed points or one (N,3) cloud shared by the batch, TY (B,M,3) transformed moving points, sigma2 (B) on the
+    device (it is never read on the host), w in [0, 1) the outlier weight -> (P1 (B,M), Pt1 (B,N), PX (B,M,3), Np (B)), fp32.
+    Deterministic, and item b's outputs do not depend on the other items.  An evaluation primitive, not differentiable."""
+    _need_gpu(X, TY, sigma2)
+    if TY.dim() != 3 or TY.shape[2] != 3 or X.dim() not in (2, 3) or X.shape[-1] != 3 or (X.dim() == 3 and X.shape[0] != TY.shape[0]):
+        raise ValueError(f"expected X (B,N,3) or (N,3) and TY (B,M,3), got {tuple(X.shape)} and {tuple(TY.shape)}")
+    B, M, _ = TY.shape
+    N = X.shape[-2]
+    if N < 1 or M < 1:
+        raise ValueError(f"cpd_estep: empty cloud (N={N}, M={M})")
+    if sigma2.numel() != B:
+        raise ValueError(f"expected one sigma2 per item ({B}), got {tuple(sigma2.shape)}")
+    if not 0. <= w < 1.:
+        raise ValueError(f"the outlier weight w must lie in [0, 1), got {w}")
+    with torch.no_grad():
+        xc, yc, sc = _f32c(X), _f32c(TY), _f32c(sigma2).reshape(B)
+        dev = yc.device
+        P1 = torch.empty(B, M, dtype=torch.float32, device=dev)
+        Pt1 = torch.empty(B, N, dtype=torch.float32, device=dev)
+        PX = torch.empty(B, M, 3, dtype=torch.float32, device=dev)
+        Np = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = _lib.workspace("fsg_cpd_estep", B, N, M, device=dev)
+        launch(dev, "fsg_cpd_estep_f32", _p(xc), 3 * N if xc.dim() == 3 else 0, _p(yc), _p(sc), float(w), B, N, M, _p(P1),
+               _p(Pt1), _p(PX), _p(Np), _p(ws), ws.numel())
+    return P1, Pt1, PX, Np
+
+
+# ------------------------------------------------------------------ k-means (shape_model/generate_corresponding_points.py:44-48)
+KMEANS_CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
+
+
+def _kmeans_args(points, centroids, who):
+    if points.dim() != 3 or points.shape[2] != 3 or centroids.dim() != 3 or centroids.shape[2] != 3 \
+            or centroids.shape[0] != points.shape[0]:
+        raise ValueError(f"{who}: expected points (B,n,3) and centroids (B,K,3), got {tuple(points.shape)} and "
+                         f"{tuple(centroids.shape)}")
+    B, n, _ = points.shape
+    K = centroids.shape[1]
+    if n < 1 or n > _lib.KMEANS_MAX_POINTS:
+        raise ValueError(f"{who}: n={n} points per item, the kernel serves 1 <= n <= {_lib.KMEANS_MAX_POINTS}")
+    if not 1 <= K <= min(n, _lib.KMEANS_MAX_K):
+        raise ValueError(f"{who}: K={K} clusters, the kernel serves 1 <= K <= min(n, {_lib.KMEANS_MAX_K}) (n={n})")
+    _need_gpu(points, centroids)
+    if points.device != centroids.device:
+        raise ValueError(f"{who}: points are on {points.device}, centroids on {centroids.device}")
+    return B, n, K
+
+
+class _KMeansRun:
+    """the device state of one run: workspace (accumulators, scales, threshold, active flags), labels and the per-item outputs"""
+
+    def __init__(self, points, centroids, tol, prev_labels=None):
+        B, n, K = self.dims = points.shape[0], points.shape[1], centroids.shape[1]
+        dev = self.dev = points.device
+        self.points, self.centroids = points, centroids
+        self.labels = torch.full((B, n), -1, dtype=torch.int32, device=dev) if prev_labels is None else prev_labels
+        self.counts = torch.empty(B, K, dtype=torch.int32, device=dev)
+        self.stats = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+        self.info = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self.ws = _lib.workspace("fsg_kmeans", B, n, K, device=dev)
+        launch(dev, "fsg_kmeans_prepare_f32", _p(points), _p(centroids), B, n, K, float(tol), _p(self.ws), self.ws.numel())
+
+    def launch(self, entry):
+        B, n, K = self.dims
+        launch(self.dev, entry, _p(self.points), _p(self.centroids), _p(self.labels), B, n, K, _p(self.ws), self.ws.numel(),
+               _p(self.counts), _p(self.stats), _p(self.info))
+
+
+def kmeans_step(points, centroids, prev_labels=None):
+    """One Lloyd iteration of B independent k-means problems (fsg_kmeans_step_f32): points (B,n,3), centroids (B,K,3),
+    prev_labels (B,n) integer or None -> (labels (B,n) int32, new_centroids (B,K,3) fp32, counts (B,K) int32, inertia (B,) fp64,
+    n_changed (B,) int32).
+
+    labels[i] = argmin_k ((dx dx + dy dy) + dz dz) in fp32, the lowest k on ties; inertia is the sum of those squared distances,
+    that is the inertia of `centroids`, not of new_centroids; n_changed counts labels that differ from prev_labels (all n
+    without them); a cluster without points keeps its centroid (counts tells which).  Sums are int64 fixed-point: the same
+    inputs give the same bits, whatever else is in the batch.  The inputs are not modified.  Not differentiable."""
+    B, n, K = _kmeans_args(points, centroids, "kmeans_step")
+    if B == 0:
+        raise ValueError("kmeans_step: empty batch")
+    if prev_labels is not None:
+        _need_gpu(prev_labels)
+        if tuple(prev_labels.shape) != (B, n) or prev_labels.is_floating_point():
+            raise ValueError(f"kmeans_step: prev_labels must be integers of shape {(B, n)}, got {tuple(prev_labels.shape)} "
+                             f"{prev_labels.dtype}")
+    with torch.no_grad():
+        prev = None if prev_labels is None else prev_labels.to(torch.int32, copy=True).contiguous()
+        run = _KMeansRun(_f32c(points), _f32c(centroids).clone(), 0., prev)
+        run.launch("fsg_kmeans_step_f32")
+    return run.labels, run.centroids, run.counts, run.stats[:, 0].clone(), run.info[:, 0].clone()
+
+
+def kmeans(points, n_clusters=None, init='fps', max_iter=300, tol=1e-4, start=0, return_info=False):
+    """Lloyd's k-means of B independent 3-D clouds on the GPU: points (n,3) or (B,n,3) -> (centroids (B,K,3) fp32, labels (B,n)
+    int64, inertia (B,) fp64, n_iter (B,) int32); a 2-D input comes back without the batch axis.
+
+    `init` is 'fps' -- farthest point sampling (fsg_fps_f32) of n_clusters points of every item, started at row `start`; the
+    selected rows are the first centres -- or a tensor (B,K,3) / (K,3) of explicit centres (then n_clusters may be omitted).
+    There is no random seeding and no n_init: the run is deterministic, bit for bit, and an item's result does not depend on
+    the batch it is in.  An item stops when no label changes or when the summed squared centre shift is at most
+    tol * mean(var(points, axis=0)) (sklearn's rule) or after max_iter iterations, and is frozen from then on; the host looks at
+    one "any item active" word every KMEANS_CHECK_EVERY iterations.  A cluster that loses all its points keeps its centre
+    (scipy.cluster.vq.kmeans2's behaviour; sklearn relocates it).  The returned labels and inertia are those OF the returned
+    centres (one last assign).  `return_info` appends a dict with `counts` (B,K) and `n_empty` (B,) of that assignment."""
+    if not torch.is_tensor(points):
+        raise TypeError(f"kmeans: points must be a torch tensor on the GPU, got {type(points).__name__}")
+    squeeze = points.dim() == 2
+    if squeeze:
+        points = points[None]
+    if points.dim() != 3 or points.shape[2] != 3 or not points.is_floating_point():
+        raise ValueError(f"kmeans: expected floating-point points (n,3) or (B,n,3), got {tuple(points.shape)} {points.dtype}")
+    B, n, _ = points.shape
+    if B == 0:
+        raise ValueError("kmeans: empty batch")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 0:
+        raise ValueError(f"kmeans: max_iter must be a non-negative integer, got {max_iter!r}")
+    if not tol >= 0:
+        raise ValueError(f"kmeans: tol must not be negative, got {tol!r}")
+    if torch.is_tensor(init):
+        cen = init[None] if init.dim() == 2 else init
+        if n_clusters is not None and cen.dim() == 3 and cen.shape[1] != n_clusters:
+            raise ValueError(f"kmeans: init holds {cen.shape[1]} centres, n_clusters={n_clusters}")
+        _kmeans_args(points, cen, "kmeans")
+    elif isinstance(init, str) and init == 'fps':
+        if n_clusters is None:
+            raise ValueError("kmeans: init='fps' needs n_clusters")
+        K = int(n_clusters)
+        if not 1 <= K <= min(n, _lib.KMEANS_MAX_K):
+            raise ValueError(f"kmeans: n_clusters={n_clusters}, the kernel serves 1 <= K <= min(n, {_lib.KMEANS_MAX_K}) (n={n})")
+        if n > _lib.KMEANS_MAX_POINTS:
+            raise ValueError(f"kmeans: n={n} points per item, the kernel serves n <= {_lib.KMEANS_MAX_POINTS}")
+        if not 0 <= start < n:
+            raise ValueError(f"kmeans: start={start} is no row of a cloud of {n} points")
+        _need_gpu(points)
+    else:
+        raise ValueError(f"kmeans: init must be 'fps' or a tensor of centres, got {init!r}")
+    with torch.no_grad():
+        pc = _f32c(points)
+        if torch.is_tensor(init):
+            cen = _f32c(cen).clone()
+        else:
+            # the sampling kernel starts a segment at its first row: rotate every cloud so that row `start` is there
+            rolled = torch.roll(pc, -start, 1).reshape(B * n, 3) if start else pc.reshape(B * n, 3)
+            seg = torch.arange(1, B + 1, dtype=torch.int32, device=pc.device)
+            rows = fps(rolled, seg * n, seg * K, B * K).long().view(B, K)    # rows of the packed, rotated clouds
+            rows = (rows - (seg.long() - 1)[:, None] * n + start) % n
+            cen = torch.gather(pc, 1, rows[:, :, None].expand(B, K, 3)).contiguous()
+        run = _KMeansRun(pc, cen, tol)
+        for it in range(max_iter):
+            if it and it % KMEANS_CHECK_EVERY == 0 and not bool(run.info[:, 3].any()):   # the only synchronisation of the loop
+                break
+            run.launch("fsg_kmeans_step_f32")
+        run.launch("fsg_kmeans_assign_f32")
+        out = [run.centroids, run.labels.long(), run.stats[:, 0].clone(), run.info[:, 2].clone()]
+        extra = {"counts": run.counts, "n_empty": run.info[:, 1].clone()}
+    if squeeze:
+        out = [t[0] for t in out]
+        extra = {k: v[0] for k, v in extra.items()}
+    return (*out, extra) if return_info else tuple(out)
+
+
+# ------------------------------------------------------------------ thin-plate splines (shape_model/point_cloud_registration.py:24-89,119-133)
+TPS_MAX_CHANNELS = _lib.TPS_MAX_CHANNELS
+
+
+def _tps_points(t, name, who):
+    """(n,3) or (B,n,3) floating-point -> (B,n,3), and whether the batch axis was added"""
+    if not torch.is_tensor(t) or t.dim() not in (2, 3) or t.shape[-1] != 3 or t.shape[-2] < 1 or not t.is_floating_point():
+        got = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{who}: {name} must be a floating-point (points, 3) or (batch, points, 3) tensor, got {got}")
+    return (t[None], True) if t.dim() == 2 else (t, False)
+
+
+def _tps_theta(theta, B, n, who):
+    if not torch.is_tensor(theta) or theta.dtype != torch.float64:
+        raise ValueError(f"{who}: theta must be an fp64 tensor (tps_fit returns one), got "
+                         f"{theta.dtype if torch.is_tensor(theta) else type(theta).__name__}")
+    if theta.dim() == 2:
+        theta = theta[None]
+    if theta.dim() != 3 or theta.shape[0] != B or theta.shape[1] != n + 4:
+        raise ValueError(f"{who}: theta must be ({B}, {n + 4}, C) for {B} x {n} control points, got {tuple(theta.shape)}")
+    if not 1 <= theta.shape[2] <= TPS_MAX_CHANNELS:
+        raise ValueError(f"{who}: C={theta.shape[2]} channels, the kernel serves 1 <= C <= {TPS_MAX_CHANNELS}")
+    return theta
+
+
+def _tps_same_device(who, *tensors):
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError(f"{who}: the tensors are on different devices ({', '.join(str(t.device) for t in tensors)})")
+
+
+def _tps_size(size, what):
+    try:
+        size = tuple(int(s) for s in size)
+    except (TypeError, ValueError):
+        size = ()
+    if len(size) != 3 or min(size) < 1 or max(size) > 1 << 24 or size[0] * size[1] * size[2] >= 1 << 31:
+        raise ValueError(f"{what} must be three positive integers (D, H, W) with fewer than 2^31 nodes, got {size!r}")
+    return size
+
+
+def tps_system(control, lambd=0.):
+    """The matrix of the reference's TPS.fit (fsg_tps_system_f64): control (B,n,3) or (n,3) -> (B,n+4,n+4) or (n+4,n+4) fp64,
+    u(|c_i - c_j|) + lambd I with u(r) = r^2 log(r + 1e-6), bordered by [1 | c], its transpose and zeros.  Distances are sums of
+    squared differences in fp64 (ours, not the reference's fp32 ra + rb - 2 ab): symmetric bit for bit, the diagonal exactly
+    lambd."""
+    c, squeeze = _tps_points(control, "control", "tps_system")
+    _need_gpu(c)
+    B, n, _ = c.shape
+    if n > 32764:
+        raise ValueError(f"tps_system: n={n} control points, the kernel serves n <= 32764")
+    with torch.no_grad():
+        cc = _f32c(c)
+        A = torch.empty(B, n + 4, n + 4, dtype=torch.float64, device=cc.device)
+        launch(cc.device, "fsg_tps_system_f64", _p(cc), B, n, float(lambd), _p(A))
+    return A[0] if squeeze else A
+
+
+def tps_fit(control, values, lambd=0., fit_batch=32):
+    """TPS.fit for a batch: control (B,n,3), values (B,n,C) (or (n,3), (n,C)) -> theta (B,n+4,C) fp64, the n spline weights and
+    the four affine rows.  The systems come from `tps_system`, the solve is torch's batched fp64 linalg.solve, `fit_batch`
+    systems at a time (100 systems of 1028^2 in fp64 are 0.85 GB).  n >= 4 points not in one plane (or lambd > 0 with
+    distinct points) make the system regular; a singular one raises as linalg.solve does."""
+    c, squeeze = _tps_points(control, "control", "tps_fit")
+    if not torch.is_tensor(values) or not values.is_floating_point() or values.dim() != control.dim() \
+            or values.shape[:-1] != control.shape[:-1]:
+        got = f"{tuple(values.shape)} {values.dtype}" if torch.is_tensor(values) else type(values).__name__
+        raise ValueError(f"tps_fit: values must be floating-point {tuple(control.shape[:-1])} + (C,), got {got}")
+    v = values[None] if squeeze else values
+    if not 1 <= v.shape[2] <= TPS_MAX_CHANNELS:
+        raise ValueError(f"tps_fit: C={v.shape[2]} channels, the kernels serve 1 <= C <= {TPS_MAX_CHANNELS}")
+    if isinstance(fit_batch, bool) or not isinstance(fit_batch, int) or fit_batch < 1:
+        raise ValueError(f"tps_fit: fit_batch must be a positive integer, got {fit_batch!r}")
+    _need_gpu(c, v)
+    _tps_same_device("tps_fit", c, v)
+    B, n, C = v.shape
+    with torch.no_grad():
+        theta = torch.empty(B, n + 4, C, dtype=torch.float64, device=c.device)
+        for b0 in range(0, B, fit_batch):
+            A = tps_system(c[b0:b0 + fit_batch], lambd)
+            rhs = torch.zeros(A.shape[0], n + 4, C, dtype=torch.float64, device=c.device)
+            rhs[:, :n] = v[b0:b0 + fit_batch]
+            theta[b0:b0 + fit_batch] = torch.linalg.solve(A, rhs)
+    return theta[0] if squeeze else theta
+
+
+def tps_eval(queries, control, theta):
+    """TPS.z (fsg_tps_eval_f32): the spline theta (B,n+4,C) fp64 on control (B,n,3) at queries (B,Q,3) -> (B,Q,C) fp32.
+    `queries` may instead be a lattice size (D1,H1,W1): the nodes of an align_corners=True lattice over [-1,1]^3 in
+    (z,y,x)-major order with (x,y,z) coordinates, as thin_plate_dense builds them with affine_grid -- no coordinate tensor is
+    read; -> (B, D1 H1 W1, C).  u and the sum over the control points are fp64.  2-D inputs are a batch of one."""
+    c, squeeze = _tps_points(control, "control", "tps_eval")
+    B, n, _ = c.shape
+    th = _tps_theta(theta, B, n, "tps_eval")
+    C = th.shape[2]
+    if torch.is_tensor(queries):
+        q, _ = _tps_points(queries, "queries", "tps_eval")
+        if q.shape[0] != B or queries.dim() != control.dim():
+            raise ValueError(f"tps_eval: queries {tuple(queries.shape)} and control {tuple(control.shape)} do not share a batch")
+        _need_gpu(q, c, th)
+        _tps_same_device("tps_eval", q, c, th)
+        Q, lattice = q.shape[1], (0, 0, 0)
+    else:
+        lattice = _tps_size(queries, "tps_eval: a lattice")
+        q, Q = None, lattice[0] * lattice[1] * lattice[2]
+        _need_gpu(c, th)
+        _tps_same_device("tps_eval", c, th)
+    with torch.no_grad():
+        cc, tc = _f32c(c), th.detach().contiguous()
+        qc = _f32c(q) if q is not None else None
+        out = torch.empty(B, Q, C, dtype=torch.float32, device=cc.device)
+        launch(cc.device, "fsg_tps_eval_f32", _p(qc), _p(cc), _p(tc), B, Q, n, C, *lattice, _p(out))
+    return out[0] if squeeze else out
+
+
+def tps_grid_sample(grid, control, theta, size, step=4):
+    """What the reference reads out of its dense displacement field, without the field (fsg_tps_grid_sample_f32):
+    F.grid_sample(align_corners=False, zeros padding) at grid (B,Q,3) (x,y,z in [-1,1], x along the last axis) of the trilinear
+    align_corners=True upsample to size = (D,H,W) of the spline theta (B,n+4,C) on control (B,n,3), evaluated on the lattice
+    (D//step, H//step, W//step) -> (B,Q,C) fp32.  A sample depends on at most 3 coarse nodes per axis; the spline is evaluated
+    at those only.  A sample whose taps all lie outside the volume is exactly 0.  2-D inputs are a batch of one."""
+    c, squeeze = _tps_points(control, "control", "tps_grid_sample")
+    B, n, _ = c.shape
+    th = _tps_theta(theta, B, n, "tps_grid_sample")
+    g, _ = _tps_points(grid, "grid", "tps_grid_sample")
+    if g.shape[0] != B or grid.dim() != control.dim():
+        raise ValueError(f"tps_grid_sample: grid {tuple(grid.shape)} and control {tuple(control.shape)} do not share a batch")
+    size = _tps_size(size, "tps_grid_sample: size")
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"tps_grid_sample: step must be a positive integer, got {step!r}")
+    if min(size) < step:
+        raise ValueError(f"tps_grid_sample: every axis of size {size} must hold at least step={step} voxels (the coarse lattice "
+                         f"would be empty)")
+    coarse = tuple(s // step for s in size)
+    _need_gpu(g, c, th)
+    _tps_same_device("tps_grid_sample", g, c, th)
+    Q, C = g.shape[1], th.shape[2]
+    with torch.no_grad():
+        gc, cc, tc = _f32c(g), _f32c(c), th.detach().contiguous()
+        out = torch.empty(B, Q, C, dtype=torch.float32, device=cc.device)
+        launch(cc.device, "fsg_tps_grid_sample_f32", _p(gc), _p(cc), _p(tc), B, Q, n, C, *size, *coarse, _p(out))
+    return out[0] if squeeze else out
+
+
+# ------------------------------------------------------------------ weighted sample elimination (open3d's sample_points_poisson_disk)
+def _per_item_radius(v, B, dev, name):
+    """a scalar or a (B,) tensor / sequence -> (B,) fp32 on `dev`"""
+    if torch.is_tensor(v):
+        _need_gpu(v)
+        if v.numel() not in (1, B) or v.dim() > 1 or not v.is_floating_point():
+            raise ValueError(f"sample_elimination: {name} must be a scalar or a floating-point ({B},) tensor, got "
+                             f"{tuple(v.shape)} {v.dtype}")
+        return v.detach().to(device=dev, dtype=torch.float32).reshape(-1).expand(B)
+    t = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+    if t.numel() not in (1, B):
+        raise ValueError(f"sample_elimination: {name} must be a scalar or hold one value per item ({B}), got {t.numel()}")
+    return t.to(torch.float32).to(dev).expand(B)
+
+
+def sample_elimination(points, n_keep, r_max, r_min, return_order=False):
+    """Weighted sample elimination (Yuksel 2015) of B independent 3-D clouds on the GPU (fsg_sample_elimination_f32): points
+    (M,3) or (B,M,3) -> keep (B,n_keep) int64, the surviving rows in ascending order [, order (B, M - n_keep) int64, the rows in
+    the order they were removed]; a 2-D input comes back without the batch axis.
+
+    r_max (the paper's 2 r_max: samples closer than it are neighbours) and r_min are scalars or (B,); tensors stay on the
+    device (a Python number is copied there: inside a graph capture pass device tensors).  Pair weight, in fp32:
+    d = max(|p_i - p_j|, r_min), w = max(1 - d / r_max, 0)^8, quantised to rint(w 2^24); a
+    sample's weight is the integer sum over its alive neighbours; every round removes the heaviest alive sample, the lowest row
+    on ties, and lowers its neighbours' weights.  r_max <= 0, or nobody within r_max of anybody: rows leave in index order.
+    Deterministic bit for bit, and an item's result does not depend on the batch it is in.  No host synchronisation.  Not
+    differentiable."""
+    if not torch.is_tensor(points):
+        raise TypeError(f"sample_elimination: points must be a torch tensor on the GPU, got {type(points).__name__}")
+    squeeze = points.dim() == 2
+    if squeeze:
+        points = points[None]
+    if points.dim() != 3 or points.shape[2] != 3 or not points.is_floating_point():
+        raise ValueError(f"sample_elimination: expected floating-point points (M,3) or (B,M,3), got {tuple(points.shape)} "
+                         f"{points.dtype}")
+    B, M, _ = points.shape
+    if B == 0:
+        raise ValueError("sample_elimination: empty batch")
+    if B > 65535:
+        raise ValueError(f"sample_elimination: B={B} items, the kernel serves B <= 65535")
+    if not 1 <= M <= _lib.SAMPLE_ELIMINATION_MAX_POINTS:
+        raise ValueError(f"sample_elimination: M={M} points per item, the kernel serves 1 <= M <= "
+                         f"{_lib.SAMPLE_ELIMINATION_MAX_POINTS}")
+    if isinstance(n_keep, bool) or not isinstance(n_keep, int) or not 1 <= n_keep <= M:
+        raise ValueError(f"sample_elimination: n_keep must be an integer with 1 <= n_keep <= M={M}, got {n_keep!r}")
+    _need_gpu(points)
+    dev = points.device
+    with torch.no_grad():
+        radii = torch.stack([_per_item_radius(r_max, B, dev, "r_max"), _per_item_radius(r_min, B, dev, "r_min")], 1).contiguous()
+        pc = _f32c(points)
+        keep = torch.empty(B, n_keep, dtype=torch.int32, device=dev)
+        order = torch.empty(B, M - n_keep, dtype=torch.int32, device=dev) if return_order else None
+        ws = _lib.workspace("fsg_sample_elimination", B, M, device=dev)
+        launch(dev, "fsg_sample_elimination_f32", _p(pc), _p(radii), B, M, n_keep, _p(keep), _p(order), _p(ws), ws.numel())
+        out = [keep.long()] + ([order.long()] if return_order else [])
+    if squeeze:
+        out = [t[0] for t in out]
+    return tuple(out) if return_order else out[0]

@@ -88,7 +88,7 @@ class FlatAdam:
 
     def _launch(self, entry, segments):
         """fsg_adam_flat_f32 (segments None: the gradient is the flat buffer) or fsg_adam_flat_segments_f32"""
-        from . import _lib
+        from ._launch import launch
         g = self._groups[0]
         lr = g["lr"]
         lr_dev = None
@@ -98,10 +98,9 @@ class FlatAdam:
             lr_dev, lr = ctypes.c_void_p(lr.data_ptr()), 0.0
         P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         table = () if segments is None else (segments,)
-        with torch.cuda.device(self.flat.device):
-            _lib.call(entry, P(self.flat.data), P(self.flat.grad), P(self.exp_avg), P(self.exp_avg_sq),
-                      P(self._state), self.flat.numel(), *table, float(lr), lr_dev, float(g["betas"][0]), float(g["betas"][1]),
-                      float(g["eps"]), float(g["weight_decay"]), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        launch(self.flat.device, entry, P(self.flat.data), P(self.flat.grad), P(self.exp_avg), P(self.exp_avg_sq),
+               P(self._state), self.flat.numel(), *table, float(lr), lr_dev, float(g["betas"][0]), float(g["betas"][1]),
+               float(g["eps"]), float(g["weight_decay"]))
 
     def _grad_segments(self):
         """the table of fsg_adam_flat_segments_f32 when the update can read every gradient in place, else None: every parameter
