@@ -1,4 +1,4 @@
-"""Shape-model ops: DG-SSM decode, the CPD E-step, k-means, thin-plate splines, weighted sample elimination."""
+"""Shape-model ops: DG-SSM decode, the CPD E-step, k-means, thin-plate splines, weighted sample elimination, the OPTICS ordering."""
 import torch
 
 from .. import _lib
@@ -429,3 +429,66 @@ def sample_elimination(points, n_keep, r_max, r_min, return_order=False):
     if squeeze:
         out = [t[0] for t in out]
     return tuple(out) if return_order else out[0]
+
+
+# ------------------------------------------------------------------ OPTICS (shape_model/generate_corresponding_points.py:50-62)
+def optics(points, min_samples, max_eps=float("inf"), return_squared=False):
+    """OPTICS reachability graph of B independent 3-D clouds on the GPU (fsg_optics_f32): points (n,3) or (B,n,3) -> (ordering
+    (B,n) int64, core_distances (B,n) fp64, reachability (B,n) fp64, predecessor (B,n) int64); a 2-D input comes back without
+    the batch axis.  ordering lists the points in the order they were processed; the other three are indexed by point
+    (reachability inf and predecessor -1 where a walk starts, core distance inf with fewer than min_samples points within
+    max_eps), as the attributes of sklearn.cluster.OPTICS are.
+
+    max_eps is a number (> 0, may be inf) or a (B,) tensor with one radius per item; a tensor stays on the device and its
+    values are not checked there.  Distances are Euclidean, computed in fp64 from the fp32 coordinates and compared as squares;
+    with return_squared the squares come back as the kernel wrote them, otherwise their `torch.sqrt`.  A point's core distance
+    is the distance to its min_samples-th nearest point, itself counted; the next point is the unprocessed one with the
+    smallest reachability, the lowest row on ties (also among the inf ones).  sklearn's rounding of the distances to 15 decimals
+    is not applied.  Deterministic bit for bit (the squares, ordering and predecessor), and an item's result does not depend on
+    the batch it is in.  No host synchronisation.  Not differentiable."""
+    if not torch.is_tensor(points):
+        raise TypeError(f"optics: points must be a torch tensor on the GPU, got {type(points).__name__}")
+    squeeze = points.dim() == 2
+    if squeeze:
+        points = points[None]
+    if points.dim() != 3 or points.shape[2] != 3 or not points.is_floating_point():
+        raise ValueError(f"optics: expected floating-point points (n,3) or (B,n,3), got {tuple(points.shape)} {points.dtype}")
+    B, n, _ = points.shape
+    if B == 0:
+        raise ValueError("optics: empty batch")
+    if B > 65535:
+        raise ValueError(f"optics: B={B} items, the kernel serves B <= 65535")
+    if n > _lib.OPTICS_MAX_POINTS:
+        raise ValueError(f"optics: n={n} points per item, the kernel serves n <= {_lib.OPTICS_MAX_POINTS}")
+    if isinstance(min_samples, bool) or not isinstance(min_samples, int) \
+            or not 2 <= min_samples <= min(n, _lib.OPTICS_MAX_MIN_SAMPLES):
+        raise ValueError(f"optics: min_samples must be an integer with 2 <= min_samples <= min(n, "
+                         f"{_lib.OPTICS_MAX_MIN_SAMPLES}) (n={n}), got {min_samples!r}")
+    if torch.is_tensor(max_eps):
+        if max_eps.dim() != 1 or max_eps.shape[0] != B or not max_eps.is_floating_point():
+            raise ValueError(f"optics: max_eps must be a number or a floating-point ({B},) tensor, got {tuple(max_eps.shape)} "
+                             f"{max_eps.dtype}")
+        _need_gpu(points, max_eps)
+        if max_eps.device != points.device:
+            raise ValueError(f"optics: points are on {points.device}, max_eps on {max_eps.device}")
+        eps = max_eps.detach().to(torch.float64).contiguous()
+    else:
+        if isinstance(max_eps, bool) or not isinstance(max_eps, (int, float)) or not max_eps > 0:
+            raise ValueError(f"optics: max_eps must be a positive number (inf allowed) or a ({B},) tensor, got {max_eps!r}")
+        _need_gpu(points)
+        eps = torch.full((B,), float(max_eps), dtype=torch.float64, device=points.device)
+    dev = points.device
+    with torch.no_grad():
+        pc = _f32c(points)
+        ordering = torch.empty(B, n, dtype=torch.int32, device=dev)
+        pred = torch.empty(B, n, dtype=torch.int32, device=dev)
+        core2 = torch.empty(B, n, dtype=torch.float64, device=dev)
+        reach2 = torch.empty(B, n, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("fsg_optics", B, n, min_samples, device=dev)
+        launch(dev, "fsg_optics_f32", _p(pc), _p(eps), B, n, min_samples, _p(ordering), _p(core2), _p(reach2), _p(pred), _p(ws),
+               ws.numel())
+        out = [ordering.long(), core2 if return_squared else torch.sqrt(core2), reach2 if return_squared else torch.sqrt(reach2),
+               pred.long()]
+    if squeeze:
+        out = [t[0] for t in out]
+    return tuple(out)

@@ -3,7 +3,8 @@ shape_model/generate_corresponding_points.py (:28-178), the step between the CPD
 `SSM.fit`.
 
 For every object (a fissure or a lobe) a set of sampling locations is chosen -- the fixed cloud ('simple', the reference's
-command-line default) or the centres of a k-means over the pooled moved clouds of all instances ('kmeans') --, each instance's
+command-line default), the centres of a k-means over the pooled moved clouds of all instances ('kmeans') or the means of the
+OPTICS clusters of that pool ('cluster', the function's own default) --, each instance's
 displacement field is interpolated there from its MOVED cloud and subtracted, the affine pre-registration is undone, and the
 result is scored against the instance's mesh and moving cloud.
 
@@ -11,14 +12,21 @@ The reference runs this as a Python double loop (objects x instances: one kNN in
 one pytorch3d Chamfer call per pair) and clusters with sklearn on the CPU.  Here every object is ONE call of each of
 `interpolate_displacements_weighted_knn` (or, with interpolation_mode='tps', `interpolate_displacements_tps`: one batched spline
 fit and one fused sampling kernel, csrc/tps.hip), `inverse_affine_transform_batch`, `functional.point_mesh_distance` and
-`functional.chamfer_nn` over all its instances, and 'kmeans' is one `functional.kmeans` over all objects (csrc/kmeans.hip).
+`functional.chamfer_nn` over all its instances, 'kmeans' is one `functional.kmeans` over all objects (csrc/kmeans.hip) and
+'cluster' one `functional.optics` over all objects with a radius per object (csrc/optics.hip), followed by the xi extraction and
+the cluster means on the host (shape_model/optics.py).
 
 Kept from the reference: the displacements are interpolated from the moved cloud; the evaluation always uses the cloud with the
 affine pre-registration undone, whatever `undo_affine_reg` says; `std` is torch's unbiased one; labels are object index + 1;
 every transform dict gets ['is_applied'] = not undo_affine_reg; 'parzen' raises NotImplementedError, an unknown mode ValueError.
 Different: 'kmeans' is seeded by farthest point sampling instead of k-means++ on numpy's random stream and an emptied cluster
 keeps its centre (see functional.kmeans) -- deterministic, but not sklearn's centres; `plot_dir` and `show` are accepted and
-ignored (no matplotlib); OPTICS ('cluster') is not part of this package and raises NotImplementedError; 'tps' needs
+ignored (no matplotlib); 'cluster' follows the rule of functional.optics (sklearn's OPTICS without its rounding of the
+distances to 15 decimals, compared on squares; labels equal sklearn's on the tested inputs), gives as many centroids as there are
+clusters (the reference allocates `len(np.unique(labels)) - 1` rows and so fails when OPTICS leaves no outlier), raises
+ValueError for an object without any cluster and for min_samples = instances // optics_minsamples_divisor outside 2 .. n, and
+NotImplementedError for optics_minsamples_divisor < 1 (the default -1 hands sklearn a negative min_samples, which it rejects:
+pass a positive divisor, the reference's driver passes 16); in that mode the objects differ in their point counts; 'tps' needs
 `fixed_img_shape` = (D, H, W) and raises NotImplementedError without it (the reference fails there as well; a grid-free spline is
 out of scope); the file-reading `__main__` driver is not mirrored.
 
@@ -29,6 +37,7 @@ import torch
 
 from .. import functional as F_hip
 from ..metrics import _device, _mesh_arrays
+from .optics import cluster_means, optics_xi_labels
 from .point_cloud_registration import (INTERPOLATION_MODES, TPS_NEEDS_SHAPE, interpolate_displacements_tps,
                                        interpolate_displacements_weighted_knn)
 
@@ -125,6 +134,30 @@ def object_correspondences(centroids, moved, displacements, moving, meshes, scal
     return pcs, dist.mean(1).float(), std.float(), dist.max(1).values.float(), cf.float()
 
 
+def _optics_centroids(moved, min_samples):
+    """'cluster' (:50-62): moved (I,O,P,3) -> one (C_obj,3) tensor per object in the dtype of `moved`: the cluster means of an
+    OPTICS run over the object's pooled clouds with max_eps = 5 % of the range of all its coordinates.  ONE ordering launch
+    for all objects; the xi labels and the means are taken per object on the host (shape_model/optics.py)."""
+    I, O, P, _ = moved.shape
+    n = I * P
+    if not 2 <= min_samples <= n:
+        raise ValueError(f"data_set_correspondences(mode='cluster'): min_samples = instances // optics_minsamples_divisor = "
+                         f"{min_samples} must be in 2 .. {n} (instances * points), as sklearn's OPTICS demands")
+    pool = moved.transpose(0, 1).reshape(O, n, 3)
+    flat = pool.reshape(O, -1).double()
+    eps = (flat.max(1).values - flat.min(1).values) * 0.05
+    ordering, _, reach2, pred = F_hip.optics(pool, min_samples, eps, return_squared=True)
+    ordering, reach, pred, host = ordering.cpu().numpy(), np.sqrt(reach2.cpu().numpy()), pred.cpu().numpy(), pool.float().cpu().numpy()
+    centroids = []
+    for obj in range(O):
+        labels = optics_xi_labels(reach[obj], pred[obj], ordering[obj], min_samples)
+        if labels.max() < 0:
+            raise ValueError(f"data_set_correspondences(mode='cluster'): OPTICS found no cluster in object {obj + 1} "
+                             f"(min_samples={min_samples}, max_eps={float(eps[obj]):.6g})")
+        centroids.append(torch.from_numpy(cluster_means(host[obj], labels)).to(device=moved.device, dtype=moved.dtype))
+    return centroids
+
+
 def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_prereg_transforms, all_moved_pcs,
                              all_displacements, fixed_img_shape=None, plot_dir=None,
                              mode='cluster', undo_affine_reg=True, show=True, optics_minsamples_divisor=-1,
@@ -137,9 +170,12 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
     interpolation_mode='tps' only."""
     if mode == 'parzen':
         raise NotImplementedError('Parzen mode is unfinished')
-    if mode == 'cluster':
-        raise NotImplementedError("data_set_correspondences(mode='cluster'): the OPTICS clustering of the reference is not part of "
-                                  "this package (a sequential reachability ordering, no GPU form here); use 'kmeans' or 'simple'")
+    if mode == 'cluster' and (isinstance(optics_minsamples_divisor, bool) or not isinstance(optics_minsamples_divisor, int)
+                              or optics_minsamples_divisor < 1):
+        raise NotImplementedError(f"data_set_correspondences(mode='cluster'): OPTICS needs min_samples = instances // "
+                                  f"optics_minsamples_divisor >= 2, and optics_minsamples_divisor={optics_minsamples_divisor!r} "
+                                  f"gives none (the reference hands sklearn a negative min_samples here, which it rejects); "
+                                  f"pass a positive divisor (the reference's driver passes 16)")
     if mode not in CORRESPONDENCE_MODES:
         raise ValueError(f'No mode named {mode}.')
     if interpolation_mode not in INTERPOLATION_MODES:
@@ -164,6 +200,8 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
             # the moved clouds of all instances pooled per object, n_clusters = P: one batched run for all objects
             pool = moved.transpose(0, 1).reshape(O, I * P, 3)
             centroids = F_hip.kmeans(pool, n_clusters=P, init='fps')[0].to(moved.dtype)
+        elif mode == 'cluster':
+            centroids = _optics_centroids(moved, I // optics_minsamples_divisor)
         else:
             centroids = fixed
         pcs, evaluation = [], []
@@ -176,7 +214,7 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
         for t in all_prereg_transforms:
             t['is_applied'] = not undo_affine_reg
         corresponding_pcs = torch.cat(pcs, 1)
-        corresponding_fixed_pc = centroids.reshape(-1, 3)
+        corresponding_fixed_pc = torch.cat(list(centroids))   # a list in 'cluster' mode: the objects differ in their counts
         labels = torch.cat([torch.full((len(centroids[obj]),), obj + 1, dtype=torch.int64, device=dev) for obj in range(O)])
         evaluation = {k: torch.stack([e[j] for e in evaluation], 1) for j, k in enumerate(('mean', 'std', 'hd', 'cf'))}
     if as_numpy:

@@ -1025,6 +1025,30 @@ int fsg_kmeans_step_f32(const float *points, float *centroids, int32_t *labels, 
 int fsg_kmeans_assign_f32(const float *points, const float *centroids, int32_t *labels, int B, int n, int K, void *workspace,
                           size_t workspace_bytes, int32_t *counts, double *stats, int32_t *info, fsg_stream_t stream);
 
+/* OPTICS reachability ordering (Ankerst et al., SIGMOD 1999) on 3-D points, batched and bit-reproducible (csrc/optics.hip).
+ * Serves the 'cluster' mode of the reference's data_set_correspondences, shape_model/generate_corresponding_points.py:50-62,
+ * which runs sklearn.cluster.OPTICS on the pooled clouds of one object at a time on the CPU.  B independent items:
+ *   points (B, n, 3) fp32, max_eps (B) fp64 (each > 0 or +inf), ordering (B, n) int32, core2 / reach2 (B, n) fp64, pred (B, n)
+ *   int32, all DEVICE and contiguous; coordinates finite (not checked: the loop count is n whatever the data, and every cell
+ *   index is clamped into its table).  2 <= min_samples <= min(n, 64), n <= 262144, B <= 65535.  workspace:
+ *   fsg_optics_workspace_bytes(B, n, min_samples) bytes (37120 + 44 n per item, rounded up to 16), 16-byte aligned.  NULL
+ *   pointers, bad shapes and a short or misaligned workspace are FSG_ERR_ARG before any launch.
+ * The rule (ours; sklearn's without its np.around(.., 15) and on squared distances):
+ *   d2(i, j) = ((dx dx + dy dy) + dz dz) in fp64 in that order, dx = (double) x_i - (double) x_j; e2 = eps eps in fp64;
+ *   N(i) = { j : d2(i, j) <= e2 }, i included; core2(i) = the min_samples-th smallest d2 over N(i) (i itself is the first, 0),
+ *   +inf if N(i) is smaller.  reach2 = +inf, pred = -1; n times: p = the unprocessed point with the smallest (reach2, index),
+ *   the LOWEST index on ties, +inf included; p is appended to `ordering`; if core2(p) < inf every unprocessed q in N(p) with
+ *   v = max(core2(p), d2(p, q)) < reach2(q) gets reach2(q) = v, pred(q) = p.
+ * core2, reach2 and pred are indexed by point; they are the SQUARES (no device square root takes part).  Three launches (cell
+ * grid and stable sort; core distances; one workgroup per item for the ordering), no atomics, nothing read on the host,
+ * capturable in a graph; the same inputs give the same bits on every run, alone or in a batch.  The cell grid only restricts
+ * the pairs that are looked at; no result depends on it. */
+#define FSG_OPTICS_MAX_POINTS 262144    /* n: 16 bytes of LDS per 64 points beside the 37 KiB cell table (static_assert) */
+#define FSG_OPTICS_MAX_MIN_SAMPLES 64   /* the core distance takes min_samples passes over the neighbourhood; I // 16 <= 64 */
+size_t fsg_optics_workspace_bytes(int B, int n, int min_samples);
+int fsg_optics_f32(const float *points, const double *max_eps, int B, int n, int min_samples, int32_t *ordering, double *core2,
+                   double *reach2, int32_t *pred, void *workspace, size_t workspace_bytes, fsg_stream_t stream);
+
 /* Weighted sample elimination (Yuksel, "Sample Elimination for Generating Poisson Disk Sample Sets", 2015), batched and
  * bit-reproducible (csrc/poisson_disk.hip).  Serves TriangleMesh.sample_points_poisson_disk, which the reference takes from
  * open3d on the host, one mesh at a time (shape_model/point_cloud_registration.py:224, :338).  B independent items:

@@ -1895,3 +1895,108 @@ if "tps" in which:
     out_path = os.environ.get("FSG_TPS_BENCH_OUT", os.path.join(ROOT, "profiles", "tps_bench.jsonl"))
     with open(out_path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+if "optics" in which:
+    # OPTICS (csrc/optics.hip) at the reference's size: three pooled sheets of 100 instances x 1024 points (n = 102 400),
+    # min_samples 6, max_eps = 5 % of the coordinate range.  Whole call (wall, synchronised), the host extraction (xi labels and
+    # cluster means, shape_model/optics.py), peak extra memory, cluster and noise counts; beside it sklearn.cluster.OPTICS on
+    # the host for ONE item of 32 x 256 = 8 192 points, and for one 102 400-point item only with FSG_OPTICS_HOST_LARGE=1.  The
+    # times of the three launches come from torch's profiler, last, so that a failure there loses nothing.  Writes
+    # profiles/optics_bench.jsonl.
+    import json
+    import time
+    import numpy as np
+    import optics_oracle as oo
+    from fissure_segmentation_amd.shape_model.optics import cluster_means, optics_xi_labels
+    lines = []
+    out_path = os.environ.get("FSG_OPTICS_BENCH_OUT", os.path.join(ROOT, "profiles", "optics_bench.jsonl"))
+
+    def flush_lines():
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(json.dumps(r) for r in lines) + "\n")
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            keep = fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+            del keep
+        return round(statistics.median(ts), 1)
+
+    def extract(pts_host, out, k):
+        """host part: square roots, xi labels and fp64 means per item -> (seconds, clusters, noise points)"""
+        order, _, reach2, pred = [t.cpu().numpy() for t in out]
+        t0 = time.perf_counter()
+        clusters, noise = [], []
+        for b in range(len(pts_host)):
+            labels = optics_xi_labels(np.sqrt(reach2[b]), pred[b], order[b], k)
+            cluster_means(pts_host[b], labels)
+            clusters.append(int(labels.max()) + 1)
+            noise.append(int((labels < 0).sum()))
+        return time.perf_counter() - t0, clusters, noise
+
+    def stages(fn):
+        """device time of the three launches of one call, by kernel name, in microseconds"""
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        got = {}
+        for ev in prof.events():
+            for key in ("optics_cells", "optics_core", "optics_order"):
+                if key in ev.name:
+                    t = getattr(ev, "device_time_total", None)
+                    got[key] = got.get(key, 0.0) + float(t if t is not None else getattr(ev, "cuda_time_total", 0.0))
+        return {k: round(v, 1) for k, v in got.items()}
+
+    k = 6
+    records = []
+    for (B, I, P) in [(1, 32, 256), (3, 100, 1024)]:
+        n = I * P
+        host = np.stack([oo.pooled(I, P, 60 + b) for b in range(B)])
+        eps = [oo.heuristic_eps(h) for h in host]
+        pts = torch.from_numpy(host).to(dev)
+        e = torch.tensor(eps, dtype=torch.float64, device=dev)
+        run = lambda pts=pts, e=e: F.optics(pts, k, e, return_squared=True)   # noqa: E731  (bound now: `stages` calls it later)
+        out = run()
+        torch.cuda.synchronize()
+        call_us = wall(run, reps=3)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = run()
+        torch.cuda.synchronize()
+        peak = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+        del keep
+        host_s, clusters, noise = extract(host, out, k)
+        rec = dict(kernel="optics", B=B, n=n, min_samples=k, max_eps=[round(x, 4) for x in eps], call_us=call_us,
+                   call_us_per_point_of_one_item=round(call_us / n, 3), host_extraction_us=round(host_s * 1e6, 1),
+                   peak_extra_MiB=peak, clusters=clusters, noise=noise, stage_us="not measured")
+        if (n == 8192 or os.environ.get("FSG_OPTICS_HOST_LARGE") == "1"):
+            try:
+                from sklearn.cluster import OPTICS
+                t0 = time.perf_counter()
+                sk = OPTICS(min_samples=k, max_eps=eps[0]).fit(host[0].astype(np.float64))
+                rec["sklearn_fit_us_item0"] = round((time.perf_counter() - t0) * 1e6, 1)
+                ours = optics_xi_labels(np.sqrt(out[2][0].cpu().numpy()), out[3][0].cpu().numpy(), out[0][0].cpu().numpy(), k)
+                rec["sklearn_same_ordering_item0"] = bool(np.array_equal(sk.ordering_, out[0][0].cpu().numpy()))
+                rec["sklearn_same_labels_item0"] = bool(np.array_equal(sk.labels_, ours))
+            except ImportError:
+                rec["sklearn"] = "not installed"
+        lines.append(rec)
+        records.append((rec, run, n))
+        print("OPTICS " + json.dumps(rec), flush=True)
+        flush_lines()
+    for rec, run, n in records:
+        try:
+            st = stages(run)
+            if st:
+                rec["stage_us"] = st
+                if "optics_order" in st:
+                    rec["ordering_us_per_step"] = round(st["optics_order"] / n, 3)
+        except Exception as ex:   # the profiler is an extra: the record keeps "not measured"
+            print("OPTICS profiler failed:", repr(ex), flush=True)
+        print("OPTICS " + json.dumps(rec), flush=True)
+        flush_lines()
