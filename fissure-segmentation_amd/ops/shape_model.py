@@ -1,4 +1,5 @@
-"""Shape-model ops: DG-SSM decode, the CPD E-step, k-means, thin-plate splines, weighted sample elimination, the OPTICS ordering."""
+"""Shape-model ops: DG-SSM decode, the CPD E-step, k-means, thin-plate splines, weighted sample elimination, the OPTICS ordering,
+the batched fp64 Cholesky solver and CPD's symmetric positive definite M-step system."""
 import torch
 
 from .. import _lib
@@ -492,3 +493,132 @@ def optics(points, min_samples, max_eps=float("inf"), return_squared=False):
     if squeeze:
         out = [t[0] for t in out]
     return tuple(out)
+
+
+# ------------------------------------------------------------------ batched fp64 Cholesky (csrc/cholesky.hip) and CPD's SPD system
+CHOL_BLOCK = _lib.CHOL_BLOCK
+CHOL_MAX_N = _lib.CHOL_MAX_N
+CHOL_MAX_BATCH = _lib.CHOL_MAX_BATCH
+CHOL_MAX_RHS = _lib.CHOL_MAX_RHS
+
+
+def _chol_matrix(A, name, who):
+    """(n,n) or (B,n,n) fp64 -> (B,n,n), and whether the batch axis was added"""
+    if not torch.is_tensor(A) or A.dtype != torch.float64 or A.dim() not in (2, 3) or A.shape[-1] != A.shape[-2]:
+        got = f"{tuple(A.shape)} {A.dtype}" if torch.is_tensor(A) else type(A).__name__
+        raise ValueError(f"{who}: {name} must be an fp64 (n, n) or (batch, n, n) tensor, got {got}")
+    squeeze = A.dim() == 2
+    A = A[None] if squeeze else A
+    if not 1 <= A.shape[1] <= CHOL_MAX_N or A.shape[0] > CHOL_MAX_BATCH:
+        raise ValueError(f"{who}: {name} is {tuple(A.shape)}, the kernels serve 1 <= n <= {CHOL_MAX_N} and at most {CHOL_MAX_BATCH} items")
+    return A, squeeze
+
+
+def _chol_rhs(rhs, B, n, squeeze, who):
+    """(B,n,r) or (B,n) fp64 (without the batch axis when the matrix came without) -> (B,n,r), and whether r was added"""
+    if not torch.is_tensor(rhs) or rhs.dtype != torch.float64:
+        raise ValueError(f"{who}: the right-hand sides must be an fp64 tensor, got "
+                         f"{rhs.dtype if torch.is_tensor(rhs) else type(rhs).__name__}")
+    r = rhs[None] if squeeze else rhs
+    vector = r.dim() == 2
+    r = r[:, :, None] if vector else r
+    if r.dim() != 3 or r.shape[0] != B or r.shape[1] != n:
+        raise ValueError(f"{who}: right-hand sides {tuple(rhs.shape)} do not fit {B} systems of order {n}")
+    if not 1 <= r.shape[2] <= CHOL_MAX_RHS:
+        raise ValueError(f"{who}: r={r.shape[2]} right-hand sides, the kernel serves 1 <= r <= {CHOL_MAX_RHS}")
+    return r, vector
+
+
+def _chol_out(src, out, what, who):
+    """a contiguous tensor holding `src`: `out` itself (checked, filled unless it is `src`) or a fresh copy"""
+    if out is None:
+        return src.clone(memory_format=torch.contiguous_format)
+    if not torch.is_tensor(out) or out.shape != src.shape or out.dtype != src.dtype or out.device != src.device \
+            or not out.is_contiguous():
+        raise ValueError(f"{who}: `out` must be a contiguous {tuple(src.shape)} fp64 tensor on the device of {what}")
+    if out.data_ptr() != src.data_ptr():
+        out.copy_(src)
+    return out
+
+
+def cholesky_factor(A, out=None, overwrite=False):
+    """A (B,n,n) or (n,n) fp64, symmetric positive definite -> (L, info): A = L L^T, L in the lower triangle (fsg_cholesky_f64).
+    Only the lower triangle of A is read; the strict upper triangle of L holds whatever it held in A (torch.linalg.cholesky
+    zeroes it).  info (B) int32 stays on the device: 0, or j when the leading minor of order j is not positive (a NaN pivot
+    counts); L of such an item is unspecified from column j on.  A is left alone unless `overwrite=True` (A must then be
+    contiguous) or `out=` names the tensor to factor in.  An evaluation primitive, not differentiable."""
+    A3, squeeze = _chol_matrix(A, "A", "cholesky_factor")
+    _need_gpu(A3)
+    with torch.no_grad():
+        if overwrite:
+            if out is not None or not A3.is_contiguous():
+                raise ValueError("cholesky_factor: overwrite=True factors A in place: A must be contiguous, and `out` makes no sense")
+            L = A3.detach()
+        else:
+            L = _chol_out(A3.detach(), out[None] if (squeeze and torch.is_tensor(out) and out.dim() == 2) else out, "A",
+                          "cholesky_factor")
+        B, n, _ = L.shape
+        info = torch.empty(B, dtype=torch.int32, device=L.device)
+        launch(L.device, "fsg_cholesky_f64", _p(L), B, n, _p(info))
+    return (L[0] if squeeze else L), info
+
+
+def cholesky_solve(L, rhs, out=None, overwrite=False):
+    """L (B,n,n) or (n,n) from `cholesky_factor`, rhs (B,n,r) or (B,n) fp64 with r <= CHOL_MAX_RHS -> X of the shape of rhs with
+    L L^T X = rhs (fsg_cholesky_solve_f64).  The strict upper triangle of L is not read.  rhs is left alone unless
+    `overwrite=True` (contiguous rhs, solved in place) or `out=`.  Not differentiable."""
+    L3, squeeze = _chol_matrix(L, "L", "cholesky_solve")
+    B, n, _ = L3.shape
+    r3, vector = _chol_rhs(rhs, B, n, squeeze, "cholesky_solve")
+    _need_gpu(L3, r3)
+    if L3.device != r3.device:
+        raise ValueError(f"cholesky_solve: L is on {L3.device}, the right-hand sides on {r3.device}")
+    with torch.no_grad():
+        if overwrite:
+            if out is not None or not r3.is_contiguous():
+                raise ValueError("cholesky_solve: overwrite=True solves in place: rhs must be contiguous, and `out` makes no sense")
+            X = r3.detach()
+        else:
+            X = _chol_out(r3.detach(), out.reshape(r3.shape) if (torch.is_tensor(out) and out.is_contiguous()
+                                                                  and out.numel() == r3.numel()) else out, "rhs", "cholesky_solve")
+        launch(X.device, "fsg_cholesky_solve_f64", _p(L3.detach().contiguous()), _p(X), B, n, X.shape[2])
+    X = X[:, :, 0] if vector else X
+    return X[0] if squeeze else X
+
+
+def spd_solve(A, rhs, overwrite=False):
+    """-> (X, info) with A X = rhs for symmetric positive definite A (B,n,n) fp64: `cholesky_factor`, then `cholesky_solve`.
+    X of an item whose info is not 0 is unspecified.  `overwrite=True` lets both calls work in place (A becomes L, rhs X)."""
+    L, info = cholesky_factor(A, overwrite=overwrite)
+    return cholesky_solve(L, rhs, overwrite=overwrite), info
+
+
+def cpd_spd_system(G, P1, PX, Y, sigma2, alpha):
+    """The M-step system of deformable CPD in its symmetric positive definite form (fsg_cpd_spd_system_f64), one pass:
+    G (B,M,M), P1 (B,M), PX (B,M,3), Y (B,M,3), sigma2 (B) on the device, all fp64, and the number alpha -> (S, rhs, d) with
+    d = sqrt(P1), S = diag(d) G diag(d) + alpha sigma2 I (LOWER triangle only; the rest of S is uninitialised) and
+    rhs = (PX - P1 Y) / d, 0 where d = 0.  With S V = rhs, W = d V solves (diag(P1) G + alpha sigma2 I) W = PX - P1 Y.  A row
+    with P1 = 0 gets exactly alpha sigma2 on the diagonal and a zero right-hand side, so its W is 0, as in the unsymmetric
+    system.  Not differentiable."""
+    ts = (G, P1, PX, Y, sigma2)
+    if not all(torch.is_tensor(t) and t.dtype == torch.float64 for t in ts):
+        raise ValueError("cpd_spd_system: G, P1, PX, Y and sigma2 must be fp64 tensors")
+    if G.dim() != 3 or G.shape[1] != G.shape[2]:
+        raise ValueError(f"cpd_spd_system: G must be (B, M, M), got {tuple(G.shape)}")
+    B, M, _ = G.shape
+    if tuple(P1.shape) != (B, M) or tuple(PX.shape) != (B, M, 3) or tuple(Y.shape) != (B, M, 3) or sigma2.numel() != B:
+        raise ValueError(f"cpd_spd_system: expected P1 ({B},{M}), PX and Y ({B},{M},3) and one sigma2 per item, got "
+                         f"{tuple(P1.shape)}, {tuple(PX.shape)}, {tuple(Y.shape)}, {tuple(sigma2.shape)}")
+    if not 1 <= M <= CHOL_MAX_N or B > CHOL_MAX_BATCH:
+        raise ValueError(f"cpd_spd_system: the kernel serves 1 <= M <= {CHOL_MAX_N} and at most {CHOL_MAX_BATCH} items")
+    _need_gpu(*ts)
+    if len({t.device for t in ts}) != 1:
+        raise ValueError("cpd_spd_system: the tensors are on different devices")
+    with torch.no_grad():
+        Gc, p1, px, yc, s2 = (t.detach().contiguous() for t in ts)
+        S = torch.empty(B, M, M, dtype=torch.float64, device=G.device)
+        rhs = torch.empty(B, M, 3, dtype=torch.float64, device=G.device)
+        d = torch.empty(B, M, dtype=torch.float64, device=G.device)
+        launch(G.device, "fsg_cpd_spd_system_f64", _p(Gc), _p(p1), _p(px), _p(yc), _p(s2.reshape(B)), float(alpha), B, M, _p(S),
+               _p(rhs), _p(d))
+    return S, rhs, d

@@ -6,8 +6,12 @@ sampled at the fixed points).
 
 Here a registration object takes a whole batch: X (N,3) or (B,N,3) fixed, Y (M,3) or (B,M,3) moving.  The E-step -- the dense
 (M, N) responsibilities and their three reductions -- is one fused HIP entry point, fp32 in and out (functional.cpd_estep), that never
-stores the matrix; the M-step's 3 x 3 SVDs and M x M solves are torch.linalg in fp64 (the system's condition number grows like
-M / (alpha sigma^2)).  sigma^2, the per-item `active` flag and the iteration counts stay on the device: an item that has met
+stores the matrix; the M-step's 3 x 3 SVDs are torch.linalg in fp64, and so is the deformable M x M solve by default (the
+system's condition number grows like M / (alpha sigma^2)).  `solver='cholesky'` takes the deformable solve to this package's own
+kernels instead: A = diag(P1) G + alpha sigma^2 I is similar to the symmetric positive definite S = D G D + alpha sigma^2 I,
+D = diag(sqrt(P1)); one kernel writes S, the scaled right-hand side and D (functional.cpd_spd_system), a blocked fp64 Cholesky on
+the matrix pipe factors and solves it (functional.spd_solve), and W = D V.  A row with P1 = 0 decouples (W = 0 there, as in A).
+Same mathematics, other rounding: the two solvers end a run about 1e-10 units apart in fp64 arithmetic.  sigma^2, the per-item `active` flag and the iteration counts stay on the device: an item that has met
 its stopping rule is frozen, and the host looks at one "any active" word every `CHECK_EVERY` iterations.
 
 Defaults and stopping rules are pycpd's: sigma^2 starts at sum |x - y|^2 / (3 N M); the rigid run stops when the objective q
@@ -51,6 +55,7 @@ from ..metrics import _device, _mesh_arrays
 
 INTERPOLATION_MODES = ['knn', 'tps']
 CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
+SOLVERS = ['lu', 'cholesky']   # the deformable M-step's M x M solve: torch.linalg.solve_ex | csrc/cholesky.hip
 TPS_STEP, TPS_LAMBDA = 4, 0.1   # point_cloud_registration.py:129: the lattice has a quarter of the resolution; the ridge of the fit
 
 
@@ -222,7 +227,11 @@ class _Registration:
                 if it and it % CHECK_EVERY == 0 and not bool(self._active.any()):   # the only synchronisation of the loop
                     break
                 self._maximization(*self._expectation())
+            self._check_run()
             return self._out(self._TY), self.get_registration_parameters()
+
+    def _check_run(self):
+        """what a subclass has to look at once the loop is through (the one place it may read the device)"""
 
     # ---- results
     def _out(self, t):
@@ -294,9 +303,14 @@ class RigidRegistration(_Registration):
 class DeformableRegistration(_Registration):
     """Non-rigid CPD (Myronenko & Song fig. 4): `register()` -> (TY, (G, W)) with TY = Y + G @ W,
     G[i,j] = exp(-|y_i - y_j|^2 / (2 beta^2)).  `alpha` weighs the smoothness of the displacement field against the point
-    fit, `beta` is the width of the kernel that defines smoothness.  G and the solve are fp64."""
+    fit, `beta` is the width of the kernel that defines smoothness.  G and the solve are fp64.  `solver`: 'lu' (default) solves
+    the M x M system with torch.linalg.solve_ex; 'cholesky' solves its symmetric positive definite form on the kernels of
+    csrc/cholesky.hip (module docstring) and raises RuntimeError at the end of `register()` if a system was rejected."""
 
-    def __init__(self, X, Y, alpha, beta, max_iterations=100, tolerance=1e-3, w=0., sigma2=None):
+    def __init__(self, X, Y, alpha, beta, max_iterations=100, tolerance=1e-3, w=0., sigma2=None, solver='lu'):
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        self.solver = solver
         super().__init__(X, Y, max_iterations=max_iterations, tolerance=tolerance, w=w, sigma2=sigma2)
         for name, v in (("alpha", alpha), ("beta", beta)):
             if not isinstance(v, numbers.Real) or not v > 0:
@@ -311,12 +325,19 @@ class DeformableRegistration(_Registration):
         self._G = torch.exp(d.mul_(-1 / (2 * self.beta ** 2)))
         self._W = torch.zeros(self.B, self.M, 3, dtype=torch.float64, device=dev)
         self._eye = torch.eye(self.M, dtype=torch.float64, device=dev)
+        self._info = torch.zeros(self.B, dtype=torch.int32, device=dev)   # 'cholesky': the largest status over the iterations
         self._Xsq = self._X.square().sum(2)
 
     def _maximization(self, P1, Pt1, PX, Np):
         Y, G = self._Y, self._G
-        A = P1[:, :, None] * G + (self.alpha * self._sigma2)[:, None, None] * self._eye
-        W = torch.linalg.solve_ex(A, PX - P1[:, :, None] * Y)[0]   # no status read-back: the loop stays asynchronous
+        if self.solver == 'cholesky':
+            S, rhs, d = F_hip.cpd_spd_system(G, P1, PX, Y, self._sigma2, self.alpha)
+            V, info = F_hip.spd_solve(S, rhs, overwrite=True)
+            self._info = torch.maximum(self._info, info)              # stays on the device: the loop stays asynchronous
+            W = d[:, :, None] * V
+        else:
+            A = P1[:, :, None] * G + (self.alpha * self._sigma2)[:, None, None] * self._eye
+            W = torch.linalg.solve_ex(A, PX - P1[:, :, None] * Y)[0]   # no status read-back: the loop stays asynchronous
         TY = Y + G @ W
         xPx = (Pt1 * self._Xsq).sum(1)
         yPy = (P1 * TY.square().sum(2)).sum(1)
@@ -327,6 +348,13 @@ class DeformableRegistration(_Registration):
         self._W, self._TY = self._keep(W, self._W), self._keep(TY, self._TY)
         self._finish_iteration(sigma2, diff)
 
+    def _check_run(self):
+        if self.solver == 'cholesky':
+            bad = self._info.nonzero().flatten().tolist()
+            if bad:
+                raise RuntimeError(f"DeformableRegistration(solver='cholesky'): the M-step system of item(s) {bad} was not positive "
+                                   f"definite in some iteration (status {self._info[bad].tolist()}); solver='lu' takes such input")
+
     def get_registration_parameters(self):
         return self._out(self._G), self._out(self._W)
 
@@ -335,10 +363,11 @@ class DeformableRegistration(_Registration):
         return self._out(self._G @ self._W)
 
 
-def register_cpd_deformable(fixed_pc_np, moving_pc_np_prereg):
+def register_cpd_deformable(fixed_pc_np, moving_pc_np_prereg, solver='lu'):
     """point_cloud_registration.py:101-116 (assumes a rigid / affine pre-registration): deformable CPD with alpha = 0.01,
-    beta = 10 -> (deformed cloud, its displacements G @ W).  Batched inputs register every pair at once."""
-    deformable = DeformableRegistration(X=fixed_pc_np, Y=moving_pc_np_prereg, alpha=0.01, beta=10)
+    beta = 10 -> (deformed cloud, its displacements G @ W).  Batched inputs register every pair at once.  `solver`: as in
+    DeformableRegistration."""
+    deformable = DeformableRegistration(X=fixed_pc_np, Y=moving_pc_np_prereg, alpha=0.01, beta=10, solver=solver)
     deformed, _ = deformable.register()
     return deformed, deformable.displacements()
 
@@ -471,7 +500,7 @@ def _fixed_clouds(fixed_pcs):
 
 
 def register_all(fixed_pcs, all_moving_meshes, ids=None, base_dir=None, n_sample_points=1024, show=False, generator=None,
-                 pair_batch=32):
+                 pair_batch=32, solver='lu'):
     """point_cloud_registration.py:191-297.  fixed_pcs: one (P,3) cloud per object (a sequence or an (objects, P, 3) array);
     all_moving_meshes[instance][object]: a mesh in any form `metrics._mesh_arrays` takes (a (verts, faces) pair, an open3d
     TriangleMesh); surplus objects of an instance are dropped as in the reference.  Steps:
@@ -479,7 +508,8 @@ def register_all(fixed_pcs, all_moving_meshes, ids=None, base_dir=None, n_sample
          instances in one call, objects in order, all drawing from `generator`;
       2. ONE batched RigidRegistration of the concatenated objects (fixed: shared, moving: one row per instance);
       3. the result is split per object and registered with `register_cpd_deformable`, `pair_batch` (instance, object) pairs
-         at a time in instance-major order (the M x M fp64 systems of a chunk set the memory);
+         at a time in instance-major order (the M x M fp64 systems of a chunk set the memory), with the M-step `solver` of
+         DeformableRegistration ('lu' | 'cholesky');
       4. `evaluate_registration` of every deformed cloud (as fp32, like the reference) against its fixed cloud within
          `correspondence_distance_heuristic` of that fixed cloud.
     -> dict: `displacements`, `moved_pcs`, `moving_pcs` (instances, objects, P, 3) fp64; `transforms`, one dict per instance
@@ -501,6 +531,8 @@ def register_all(fixed_pcs, all_moving_meshes, ids=None, base_dir=None, n_sample
         raise ValueError(f"register_all: {len(ids)} ids for {I} instances")
     if isinstance(pair_batch, bool) or not isinstance(pair_batch, int) or pair_batch < 1:
         raise ValueError(f"register_all: pair_batch must be a positive integer, got {pair_batch!r}")
+    if solver not in SOLVERS:
+        raise ValueError(f"register_all: solver must be one of {SOLVERS}, got {solver!r}")
     if not as_numpy:
         F_hip._need_gpu(*clouds)
     dev = _device() if as_numpy else clouds[0].device
@@ -522,7 +554,8 @@ def register_all(fixed_pcs, all_moving_meshes, ids=None, base_dir=None, n_sample
         Y = prereg.reshape(I * O, P, 3)
         moved, disp = [], []
         for p0 in range(0, I * O, pair_batch):
-            deformed, d = register_cpd_deformable(X[p0:p0 + pair_batch].contiguous(), Y[p0:p0 + pair_batch].contiguous())
+            deformed, d = register_cpd_deformable(X[p0:p0 + pair_batch].contiguous(), Y[p0:p0 + pair_batch].contiguous(),
+                                                  solver=solver)
             moved.append(deformed)
             disp.append(d)
         moved, disp = torch.cat(moved), torch.cat(disp)

@@ -1551,6 +1551,33 @@ int fsg_tps_eval_f32(const float *query, const float *control, const double *the
 int fsg_tps_grid_sample_f32(const float *grid, const float *control, const double *theta, int B, int Q, int n, int C, int D, int H,
                             int W, int D1, int H1, int W1, float *out, fsg_stream_t stream);
 
+/* Batched fp64 Cholesky factorisation and solve, and the symmetric positive definite form of deformable CPD's M-step
+ * (csrc/cholesky.hip).  Serves the M x M solve of pycpd's DeformableRegistration.update_transform behind the reference's
+ * shape_model/point_cloud_registration.py:101-116.  B independent items, DEVICE pointers, row-major contiguous fp64.
+ * fsg_cholesky_f64: A (B, n, n) -> L with A = L L^T, in place, lower: only the lower triangle is read and written, the strict
+ *   upper triangle is left as it is.  info (B) int32 DEVICE: 0 = factored; j = the leading minor of order j is not positive
+ *   (LAPACK potrf's convention, 1-based), tested as !(pivot > 0), so a NaN pivot is caught.  The kernels always run to the end:
+ *   the contents of a failed item are unspecified from column j on, the other items do not see the failure.  A left-looking
+ *   sweep over panels of FSG_CHOL_BLOCK columns on v_mfma_f64_16x16x4_f64, one launch per panel and one for the diagonal blocks
+ *   (n / FSG_CHOL_BLOCK + 1 launches, rounded up), no workspace.
+ * fsg_cholesky_solve_f64: L as written above (its strict upper triangle is not read), X (B, n, r) the right-hand sides on entry
+ *   and the solutions of L L^T x = b on exit, 1 <= r <= FSG_CHOL_MAX_RHS.  One workgroup per item, blocked forward and back
+ *   substitution.  An item whose info is not 0 yields unspecified values, never a fault.
+ * fsg_cpd_spd_system_f64: G (B, M, M), P1 (B, M), PX (B, M, 3), Y (B, M, 3), sigma2 (B) DEVICE, alpha -> d (B, M) = sqrt(P1);
+ *   S (B, M, M), lower triangle only: S_ij = (d_i G_ij) d_j + (i == j) alpha sigma2; rhs (B, M, 3):
+ *   rhs_i = d_i > 0 ? (PX_i - P1_i Y_i) / d_i : 0.  With S V = rhs, W = d V solves (diag(P1) G + alpha sigma2 I) W = PX - P1 Y;
+ *   a row with P1 = 0 has exactly alpha sigma2 on the diagonal of S, zeros beside it, and rhs 0.  1 <= M <= FSG_CHOL_MAX_N.
+ * Fixed summation orders, no atomics, nothing read on the host: the same inputs give the same bits, alone or in a batch, and
+ * every entry can be captured in a graph.  Bad arguments are FSG_ERR_ARG. */
+#define FSG_CHOL_BLOCK 64       /* columns of a panel */
+#define FSG_CHOL_MAX_N 8192     /* n, M */
+#define FSG_CHOL_MAX_BATCH 65535 /* B */
+#define FSG_CHOL_MAX_RHS 8      /* r */
+int fsg_cholesky_f64(double *A, int B, int n, int32_t *info, fsg_stream_t stream);
+int fsg_cholesky_solve_f64(const double *L, double *X, int B, int n, int r, fsg_stream_t stream);
+int fsg_cpd_spd_system_f64(const double *G, const double *P1, const double *PX, const double *Y, const double *sigma2, double alpha,
+                           int B, int M, double *S, double *rhs, double *d, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2000,3 +2000,104 @@ if "optics" in which:
             print("OPTICS profiler failed:", repr(ex), flush=True)
         print("OPTICS " + json.dumps(rec), flush=True)
         flush_lines()
+if "chol" in which:
+    # Batched fp64 Cholesky (csrc/cholesky.hip): factor + solve (r = 3) beside torch.linalg.solve_ex and torch.linalg.cholesky_ex +
+    # torch.cholesky_solve on the same matrices; the CPD assembly kernel beside its torch composition; the whole 100-iteration
+    # deformable run at B = 32, M = N = 1024 under both solvers; peak extra memory of each.  HIP-event medians, the sides of a
+    # comparison alternating in one run.  Writes profiles/cholesky_bench.jsonl.
+    import json
+    import chol_oracle as co
+    import cpd_oracle
+    from fissure_segmentation_amd.shape_model import point_cloud_registration as pcr
+    lines = []
+    out_path = os.environ.get("FSG_CHOL_BENCH_OUT", os.path.join(ROOT, "profiles", "cholesky_bench.jsonl"))
+
+    def emit_line(rec):
+        lines.append(json.dumps(rec))
+        print("CHOL " + lines[-1], flush=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    def alternating(sides, iters, warm=1):
+        """{name: fn} -> {name: median microseconds}, one call of every side per round"""
+        for _ in range(warm):
+            for fn in sides.values():
+                fn()
+        torch.cuda.synchronize()
+        ts = {name: [] for name in sides}
+        for _ in range(iters):
+            for name, fn in sides.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record(); fn(); e.record(); torch.cuda.synchronize()
+                ts[name].append(s.elapsed_time(e) * 1e3)
+        return {name: round(statistics.median(v), 1) for name, v in ts.items()}
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        keep = fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        del keep
+        return round(peak / 2 ** 20, 1)
+
+    with torch.no_grad():
+        for (B, n) in [(1, 1024), (32, 1024), (32, 256), (8, 2048)]:
+            g = torch.Generator(device=dev).manual_seed(n + B)
+            Q = torch.randn(B, n, n + 8, generator=g, dtype=torch.float64, device=dev)
+            A = Q @ Q.transpose(1, 2) / n + 0.01 * torch.eye(n, dtype=torch.float64, device=dev)
+            A = torch.tril(A) + torch.tril(A, -1).transpose(1, 2)
+            b = torch.randn(B, n, 3, generator=g, dtype=torch.float64, device=dev)
+            del Q
+            sides = {"ours_factor_plus_solve_us": lambda: F.spd_solve(A, b),
+                     "torch_solve_ex_us": lambda: torch.linalg.solve_ex(A, b),
+                     "torch_cholesky_ex_plus_cholesky_solve_us": lambda: torch.cholesky_solve(b, torch.linalg.cholesky_ex(A)[0])}
+            rec = dict(kernel="cholesky", B=B, n=n, r=3, **alternating(sides, iters=7))
+            L, info = F.cholesky_factor(A)
+            rec.update(alternating({"ours_factor_us": lambda: F.cholesky_factor(A), "ours_solve_us": lambda: F.cholesky_solve(L, b)}, iters=7))
+            X, Xt = F.cholesky_solve(L, b), torch.linalg.solve_ex(A, b)[0]
+            rec["info_clean"] = not bool(info.any())
+            rec["ours_vs_solve_ex_rel"] = float((X - Xt).abs().max() / Xt.abs().max())
+            rec["speedup_vs_solve_ex"] = round(rec["torch_solve_ex_us"] / rec["ours_factor_plus_solve_us"], 2)
+            rec["speedup_vs_torch_cholesky"] = round(rec["torch_cholesky_ex_plus_cholesky_solve_us"] / rec["ours_factor_plus_solve_us"], 2)
+            rec["factor_GFLOPs"] = round(B * n ** 3 / 3 / rec["ours_factor_us"] / 1e3, 1)
+            for name, fn in sides.items():
+                rec[name.replace("_us", "_peak_extra_MiB")] = peak_extra(fn)
+            emit_line(rec)
+            del A, b, L, X, Xt
+
+        # the assembly kernel beside its torch composition, on a CPD state of the workload's shape
+        B, M, N = 32, 1024, 1024
+        pairs = [cpd_oracle.sheet_pair(N=N, M=M, seed=s) for s in range(B)]
+        Xc, Yc = torch.stack([p[0] for p in pairs]).to(dev), torch.stack([p[1] for p in pairs]).to(dev)
+        reg = pcr.DeformableRegistration(Xc, Yc, alpha=co.ALPHA, beta=co.BETA, max_iterations=1, tolerance=0)
+        reg.register()
+        G, sigma2 = reg._G, reg._sigma2
+        P1, _, PX, _ = reg._expectation()
+        eye = torch.eye(M, dtype=torch.float64, device=dev)
+
+        def composition():
+            d = P1.sqrt()
+            S = d[:, :, None] * G * d[:, None, :] + (co.ALPHA * sigma2)[:, None, None] * eye
+            num = PX - P1[:, :, None] * Yc
+            return S, torch.where(d[:, :, None] > 0, num / d[:, :, None], torch.zeros_like(num)), d
+
+        sides = {"ours_us": lambda: F.cpd_spd_system(G, P1, PX, Yc, sigma2, co.ALPHA), "torch_composition_us": composition}
+        rec = dict(kernel="cpd_spd_system", B=B, M=M, **alternating(sides, iters=9))
+        rec["ours_peak_extra_MiB"], rec["torch_composition_peak_extra_MiB"] = peak_extra(sides["ours_us"]), peak_extra(composition)
+        rec["speedup"] = round(rec["torch_composition_us"] / rec["ours_us"], 2)
+        emit_line(rec)
+        del reg, G, P1, PX, eye
+
+    # the whole run: 100 iterations (tolerance 0), both solvers in one process, alternating
+    def run(solver):
+        reg = pcr.DeformableRegistration(Xc, Yc, alpha=co.ALPHA, beta=co.BETA, max_iterations=100, tolerance=0, solver=solver)
+        return reg.register()[0]
+
+    rounds = int(os.environ.get("FSG_CHOL_BENCH_ROUNDS", "2"))
+    t = alternating({"cholesky_us": lambda: run('cholesky'), "lu_us": lambda: run('lu')}, iters=rounds, warm=0)
+    rec = dict(kernel="cpd_deformable_100_iterations", B=B, M=M, N=N, rounds=rounds, **t)
+    rec["speedup"] = round(t["lu_us"] / t["cholesky_us"], 2)
+    rec["cholesky_peak_extra_MiB"], rec["lu_peak_extra_MiB"] = peak_extra(lambda: run('cholesky')), peak_extra(lambda: run('lu'))
+    emit_line(rec)
