@@ -25,7 +25,8 @@ from .ops.packed import knn_segment, fps
 from .ops.random_walk import random_walk_solve, random_walk_fill, lobes_to_fissures_labels
 from .ops.seg_cnn import MBCONV_MAX_CIN, MBCONV_MAX_CMID, MBCONV_MAX_COUT, mbconv3d, patch_accumulate, patch_finalize
 from .ops.shape_model import (SSM_MAX_MODES, ssm_decode_affine, cpd_estep, KMEANS_CHECK_EVERY, kmeans_step, kmeans,
-                              TPS_MAX_CHANNELS, tps_system, tps_fit, tps_eval, tps_grid_sample, sample_elimination, optics,
+                              TPS_MAX_CHANNELS, TPS_SOLVERS, tps_system, tps_fit, tps_nullspace_system, tps_nullspace_fit, tps_eval,
+                              tps_grid_sample, sample_elimination, optics,
                               CHOL_BLOCK, CHOL_MAX_N, CHOL_MAX_BATCH, CHOL_MAX_RHS, cholesky_factor, cholesky_solve, spd_solve,
                               cpd_spd_system)
 from .ops.spatial import BSPLINE_PAD, ELASTIC_MAX_SIGMA, bspline_prefilter, elastic_field, _patch3, spatial_transform

@@ -286,19 +286,44 @@ def tps_system(control, lambd=0.):
     return A[0] if squeeze else A
 
 
-def tps_fit(control, values, lambd=0., fit_batch=32):
-    """TPS.fit for a batch: control (B,n,3), values (B,n,C) (or (n,3), (n,C)) -> theta (B,n+4,C) fp64, the n spline weights and
-    the four affine rows.  The systems come from `tps_system`, the solve is torch's batched fp64 linalg.solve, `fit_batch`
-    systems at a time (100 systems of 1028^2 in fp64 are 0.85 GB).  n >= 4 points not in one plane (or lambd > 0 with
-    distinct points) make the system regular; a singular one raises as linalg.solve does."""
-    c, squeeze = _tps_points(control, "control", "tps_fit")
+TPS_SOLVERS = ('lu', 'nullspace')
+
+
+def _tps_values(control, values, squeeze, who):
+    """values (B,n,C), or (n,C) beside a control (n,3) -> (B,n,C)"""
     if not torch.is_tensor(values) or not values.is_floating_point() or values.dim() != control.dim() \
             or values.shape[:-1] != control.shape[:-1]:
         got = f"{tuple(values.shape)} {values.dtype}" if torch.is_tensor(values) else type(values).__name__
-        raise ValueError(f"tps_fit: values must be floating-point {tuple(control.shape[:-1])} + (C,), got {got}")
+        raise ValueError(f"{who}: values must be floating-point {tuple(control.shape[:-1])} + (C,), got {got}")
     v = values[None] if squeeze else values
     if not 1 <= v.shape[2] <= TPS_MAX_CHANNELS:
-        raise ValueError(f"tps_fit: C={v.shape[2]} channels, the kernels serve 1 <= C <= {TPS_MAX_CHANNELS}")
+        raise ValueError(f"{who}: C={v.shape[2]} channels, the kernels serve 1 <= C <= {TPS_MAX_CHANNELS}")
+    return v
+
+
+def _tps_lu(c, v, lambd):
+    """theta (B,n+4,C) of the saddle systems by torch's batched fp64 linalg.solve"""
+    n = c.shape[1]
+    A = tps_system(c, lambd)
+    rhs = torch.zeros(A.shape[0], n + 4, v.shape[2], dtype=torch.float64, device=c.device)
+    rhs[:, :n] = v
+    return torch.linalg.solve(A, rhs)
+
+
+def tps_fit(control, values, lambd=0., fit_batch=32, solver='lu'):
+    """TPS.fit for a batch: control (B,n,3), values (B,n,C) (or (n,3), (n,C)) -> theta (B,n+4,C) fp64, the n spline weights and
+    the four affine rows, `fit_batch` systems at a time (100 systems of 1028^2 in fp64 are 0.85 GB).  n >= 4 points not in one
+    plane (or lambd > 0 with distinct points) make the system regular.
+    solver='lu': the systems come from `tps_system`, the solve is torch's batched fp64 linalg.solve; a singular one raises as
+    linalg.solve does.
+    solver='nullspace': `tps_nullspace_fit`, whose status is read once per chunk.  Items whose points lie in one plane (status
+    < 0) raise a RuntimeError that names them; items whose reduced system is not positive definite (status > 0: a negative
+    lambd, or lambd = 0 with near-coincident points, which can be regular without being definite) are solved again through
+    the 'lu' route, one at a time, and only those."""
+    if solver not in TPS_SOLVERS:
+        raise ValueError(f"tps_fit: solver must be one of {TPS_SOLVERS}, got {solver!r}")
+    c, squeeze = _tps_points(control, "control", "tps_fit")
+    v = _tps_values(control, values, squeeze, "tps_fit")
     if isinstance(fit_batch, bool) or not isinstance(fit_batch, int) or fit_batch < 1:
         raise ValueError(f"tps_fit: fit_batch must be a positive integer, got {fit_batch!r}")
     _need_gpu(c, v)
@@ -307,11 +332,70 @@ def tps_fit(control, values, lambd=0., fit_batch=32):
     with torch.no_grad():
         theta = torch.empty(B, n + 4, C, dtype=torch.float64, device=c.device)
         for b0 in range(0, B, fit_batch):
-            A = tps_system(c[b0:b0 + fit_batch], lambd)
-            rhs = torch.zeros(A.shape[0], n + 4, C, dtype=torch.float64, device=c.device)
-            rhs[:, :n] = v[b0:b0 + fit_batch]
-            theta[b0:b0 + fit_batch] = torch.linalg.solve(A, rhs)
+            cb, vb = c[b0:b0 + fit_batch], v[b0:b0 + fit_batch]
+            if solver == 'lu':
+                theta[b0:b0 + fit_batch] = _tps_lu(cb, vb, lambd)
+                continue
+            theta[b0:b0 + fit_batch], info = tps_nullspace_fit(cb, vb, lambd)
+            info = info.tolist()   # the one host read of the chunk
+            flat = [b0 + i for i, s in enumerate(info) if s < 0]
+            if flat:
+                raise RuntimeError(f"tps_fit: the control points of item(s) {flat} do not span three dimensions (fewer than 4 "
+                                   f"points, points in one plane, or a NaN): the spline's system is singular")
+            for i, s in enumerate(info):
+                if s > 0:
+                    theta[b0 + i] = _tps_lu(cb[i:i + 1], vb[i:i + 1], lambd)[0]
     return theta[0] if squeeze else theta
+
+
+def tps_nullspace_system(control, lambd=0.):
+    """Steps 1-4 of the null-space route (fsg_tps_ns_system_f64): control (B,n,3) or (n,3) -> (V, tau, R, S, info).  With
+    P = [1 | c] = Q [R; 0]: V (B,n,4) the Householder vectors (LAPACK dgeqr2's convention), tau (B,4), R (B,4,4) upper
+    triangular, S (B,n-4,n-4) = (Q^T (K + lambd I) Q)[4:, 4:] with K as `tps_system` writes it -- LOWER triangle only, the rest
+    is uninitialised; (B,0,0) for n <= 4 -- and info (B) int32 on the device: 0, or -k for the first |R_kk| <= n 2^-52 max |R_jj|
+    (points in one plane, fewer than 4 points, a NaN).  K is never stored.  fp64; not differentiable."""
+    c, squeeze = _tps_points(control, "control", "tps_nullspace_system")
+    _need_gpu(c)
+    B, n, _ = c.shape
+    m = max(n - 4, 0)
+    if m > CHOL_MAX_N or B > CHOL_MAX_BATCH:
+        raise ValueError(f"tps_nullspace_system: {B} x {n} control points, the kernels serve n - 4 <= {CHOL_MAX_N} and at most "
+                         f"{CHOL_MAX_BATCH} items")
+    with torch.no_grad():
+        cc = _f32c(c)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=cc.device)   # noqa: E731
+        V, tau, R, S = new(B, n, 4), new(B, 4), new(B, 4, 4), new(B, m, m)
+        work = new(B * n * _lib.TPS_NS_SYSTEM_WORK_PER_POINT)
+        info = torch.empty(B, dtype=torch.int32, device=cc.device)
+        launch(cc.device, "fsg_tps_ns_system_f64", _p(cc), B, n, float(lambd), _p(V), _p(tau), _p(R), _p(S) if m else None,
+               _p(info), _p(work))
+    out = (V, tau, R, S, info)
+    return tuple(t[0] for t in out) if squeeze else out
+
+
+def tps_nullspace_fit(control, values, lambd=0.):
+    """TPS.fit by the null-space route: control (B,n,3), values (B,n,C) (or (n,3), (n,C)) -> (theta (B,n+4,C) fp64, info).
+    `tps_nullspace_system`, `cholesky_factor` of S in place, then fsg_tps_ns_solve_f64 around `cholesky_solve`.  Nothing is read
+    on the host, so the call can be captured in a graph: info (B) int32 stays on the device -- 0, -k (the rank status above) or
+    j (the reduced system's leading minor of order j is not positive) -- and the theta of an item whose info is not 0 is
+    unspecified.  For n = 4 the reduced system is empty and no factorisation is launched.  Not differentiable."""
+    c, squeeze = _tps_points(control, "control", "tps_nullspace_fit")
+    v = _tps_values(control, values, squeeze, "tps_nullspace_fit")
+    _need_gpu(c, v)
+    _tps_same_device("tps_nullspace_fit", c, v)
+    B, n, C = v.shape
+    with torch.no_grad():
+        cc = _f32c(c)
+        vc = v.detach().to(torch.float64).contiguous()
+        V, tau, R, S, info = tps_nullspace_system(cc, lambd)
+        if n > 4:
+            L, chol = cholesky_factor(S, overwrite=True)
+            info = torch.where(info != 0, info, chol)
+        theta = torch.empty(B, n + 4, C, dtype=torch.float64, device=cc.device)
+        work = torch.empty(B * n * C * _lib.TPS_NS_SOLVE_WORK_PER_VALUE, dtype=torch.float64, device=cc.device)
+        launch(cc.device, "fsg_tps_ns_solve_f64", _p(cc), _p(vc), _p(V), _p(tau), _p(R), _p(L) if n > 4 else None, B, n, C,
+               float(lambd), _p(work), _p(theta))
+    return (theta[0], info[0]) if squeeze else (theta, info)
 
 
 def tps_eval(queries, control, theta):

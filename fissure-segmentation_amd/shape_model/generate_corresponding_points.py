@@ -108,17 +108,19 @@ def _mesh_distances(points, meshes):
 
 
 def object_correspondences(centroids, moved, displacements, moving, meshes, scale, rotation, translation, undo_affine_reg=True,
-                           interpolation_mode='knn', img_shape=None):
+                           interpolation_mode='knn', img_shape=None, tps_solver='lu'):
     """One object, all instances at once: centroids (Q,3) the sampling locations, moved / displacements (I,P,3) the registered
     clouds and their displacements, moving (I,Pm,3) the original clouds, one mesh per instance, the pre-registration as
     scale (I,), rotation (I,3,3), translation (I,3) -> (corresponding points (I,Q,3) in the dtype of the centroids, mean, std,
-    hd, cf (I,) fp32).  GPU tensors.  interpolation_mode 'tps' needs img_shape = (D, H, W)."""
+    hd, cf (I,) fp32).  GPU tensors.  interpolation_mode 'tps' needs img_shape = (D, H, W); tps_solver is the solve of its fit
+    (point_cloud_registration.TPS_SOLVERS)."""
     I = moved.shape[0]
     sample = centroids[None].expand(I, -1, -1).contiguous()
     if interpolation_mode == 'tps':
         if img_shape is None:
             raise NotImplementedError(TPS_NEEDS_SHAPE.format("object_correspondences", "img_shape"))
-        interpolated = interpolate_displacements_tps(moved.float(), displacements.float(), sample.float(), img_shape)
+        interpolated = interpolate_displacements_tps(moved.float(), displacements.float(), sample.float(), img_shape,
+                                                     solver=tps_solver)
     elif interpolation_mode == 'knn':
         interpolated = interpolate_displacements_weighted_knn(moved.float(), displacements.float(), sample.float())
     else:
@@ -161,13 +163,13 @@ def _optics_centroids(moved, min_samples):
 def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_prereg_transforms, all_moved_pcs,
                              all_displacements, fixed_img_shape=None, plot_dir=None,
                              mode='cluster', undo_affine_reg=True, show=True, optics_minsamples_divisor=-1,
-                             interpolation_mode='knn'):
+                             interpolation_mode='knn', tps_solver='lu'):
     """generate_corresponding_points.py:28-178.  fixed_pcs (objects, P, 3); all_moving_meshes[instance][object] a mesh in any
     form `metrics._mesh_arrays` takes; all_moving_pcs, all_moved_pcs, all_displacements (instances, objects, P, 3);
     all_prereg_transforms one dict per instance with 'scale', 'rotation', 'translation' ->
     (corresponding_pcs (instances, sum of points, 3), all_prereg_transforms, corresponding_fixed_pc (sum of points, 3),
     labels (sum of points,), {'mean', 'std', 'hd', 'cf'} each (instances, objects) fp32).  fixed_img_shape = (D, H, W) is read by
-    interpolation_mode='tps' only."""
+    interpolation_mode='tps' only, and so is tps_solver, the solve of the spline's fit (point_cloud_registration.TPS_SOLVERS)."""
     if mode == 'parzen':
         raise NotImplementedError('Parzen mode is unfinished')
     if mode == 'cluster' and (isinstance(optics_minsamples_divisor, bool) or not isinstance(optics_minsamples_divisor, int)
@@ -208,7 +210,7 @@ def data_set_correspondences(fixed_pcs, all_moving_meshes, all_moving_pcs, all_p
         for obj in range(O):
             out = object_correspondences(centroids[obj], moved[:, obj], disp[:, obj], moving[:, obj],
                                          [all_moving_meshes[i][obj] for i in range(I)], scale, rotation, translation,
-                                         undo_affine_reg, interpolation_mode, fixed_img_shape)
+                                         undo_affine_reg, interpolation_mode, fixed_img_shape, tps_solver)
             pcs.append(out[0])
             evaluation.append(out[1:])
         for t in all_prereg_transforms:

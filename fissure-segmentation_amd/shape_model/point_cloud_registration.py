@@ -28,7 +28,9 @@ tensors must be on a GPU and stay there.  A 2-D Y is a batch of one, returned wi
 The thin-plate-spline interpolation (:24-89 `TPS` and `thin_plate_dense`, :119-133 `interpolate_displacements_tps`) is here too.
 The reference fits a spline on the moved cloud, evaluates it on a lattice of a quarter of the image's resolution, upsamples that
 to a dense displacement field of the whole image and reads the sample points out of it with grid_sample.  Here the system matrix
-is one kernel (fp64, functional.tps_system), the solve torch's batched fp64 linalg.solve, and the samples come from one fused
+is one kernel (fp64, functional.tps_system), the solve torch's batched fp64 linalg.solve -- or, with solver='nullspace', this
+package's own: the polynomial block is eliminated by a Householder QR and the rest is a Cholesky factorisation
+(functional.tps_nullspace_fit) --, and the samples come from one fused
 kernel (functional.tps_grid_sample) that evaluates the spline only at the at most 27 lattice nodes a sample depends on: no
 lattice, no field.  `thin_plate_dense` still returns the field for callers that want it.  The reference's conventions are kept,
 odd as they are: step = 4, lambd = 0.1; coordinates and displacements are normalised by [W-1, H-1, D-1] of img_shape = (D, H, W);
@@ -56,6 +58,7 @@ from ..metrics import _device, _mesh_arrays
 INTERPOLATION_MODES = ['knn', 'tps']
 CHECK_EVERY = 5   # iterations between two looks of the host at the "any item still active" word
 SOLVERS = ['lu', 'cholesky']   # the deformable M-step's M x M solve: torch.linalg.solve_ex | csrc/cholesky.hip
+TPS_SOLVERS = ['lu', 'nullspace']   # the spline's solve: torch.linalg.solve | the null-space Cholesky route (csrc/tps_nullspace.hip)
 TPS_STEP, TPS_LAMBDA = 4, 0.1   # point_cloud_registration.py:129: the lattice has a quarter of the resolution; the ridge of the fit
 
 
@@ -67,8 +70,8 @@ class TPS:
     go through them."""
 
     @staticmethod
-    def fit(c, f, lambd=0.):
-        return F_hip.tps_fit(c, f, lambd)
+    def fit(c, f, lambd=0., solver='lu'):
+        return F_hip.tps_fit(c, f, lambd, solver=solver)
 
     @staticmethod
     def d(a, b):
@@ -87,7 +90,7 @@ class TPS:
         return F_hip.tps_eval(x, c, theta)
 
 
-def thin_plate_dense(x1, y1, shape, step, lambd=.0, unroll_step_size=2 ** 12):
+def thin_plate_dense(x1, y1, shape, step, lambd=.0, unroll_step_size=2 ** 12, solver='lu'):
     """point_cloud_registration.py:70-89: the spline through values y1 (B,n,C) at control points x1 (B,n,3) in [-1,1]^3 (x along
     the last axis of `shape`), evaluated on the align_corners=True lattice (D//step, H//step, W//step) of shape = (D,H,W) and
     upsampled trilinearly (align_corners=True) -> the dense field (B,D,H,W,C) fp32.  The lattice nodes are implied (the kernel
@@ -101,17 +104,18 @@ def thin_plate_dense(x1, y1, shape, step, lambd=.0, unroll_step_size=2 ** 12):
         raise ValueError(f"thin_plate_dense: expected x1 (B,n,3) and y1 (B,n,C), got {tuple(x1.shape)} and {tuple(y1.shape)}")
     D1, H1, W1 = D // step, H // step, W // step
     with torch.no_grad():
-        theta = F_hip.tps_fit(x1, y1, lambd)
+        theta = F_hip.tps_fit(x1, y1, lambd, solver=solver)
         y2 = F_hip.tps_eval((D1, H1, W1), x1, theta)
         y2 = y2.view(-1, D1, H1, W1, y2.shape[-1]).permute(0, 4, 1, 2, 3)
         return F.interpolate(y2, (D, H, W), mode='trilinear', align_corners=True).permute(0, 2, 3, 4, 1)
 
 
-def interpolate_displacements_tps(existing_points, values_at_existing_points, interpolation_points, img_shape):
+def interpolate_displacements_tps(existing_points, values_at_existing_points, interpolation_points, img_shape, solver='lu'):
     """point_cloud_registration.py:119-133 for a batch: existing_points and values_at_existing_points (B,n,3),
     interpolation_points (B,Q,3) in voxel units of an image img_shape = (D,H,W) -> displacements (B,Q,3) fp32 (2-D inputs: a
     batch of one, returned 2-D).  The reference's conventions, see the module docstring; any Q, also 1 (the reference's
-    squeeze() breaks there).  A sample outside the volume reads grid_sample's zero padding.  GPU tensors in, GPU tensor out."""
+    squeeze() breaks there).  A sample outside the volume reads grid_sample's zero padding.  GPU tensors in, GPU tensor out.
+    solver (one of TPS_SOLVERS) is handed to functional.tps_fit."""
     e, v, q = existing_points, values_at_existing_points, interpolation_points
     try:
         D, H, W = (int(s) for s in img_shape)
@@ -132,7 +136,7 @@ def interpolate_displacements_tps(existing_points, values_at_existing_points, in
         norm = torch.tensor([W - 1, H - 1, D - 1], dtype=torch.float32, device=e.device)
         normalize = lambda grid: (grid / norm) * 2   # noqa: E731  (no -1 for displacements)
         control = normalize(e) - 1
-        theta = F_hip.tps_fit(control, normalize(v), TPS_LAMBDA)
+        theta = F_hip.tps_fit(control, normalize(v), TPS_LAMBDA, solver=solver)
         sampled = F_hip.tps_grid_sample(normalize(q) - 1, control, theta, size=(W, H, D), step=TPS_STEP)
         return (sampled * torch.tensor([H - 1, W - 1, D - 1], dtype=torch.float32, device=e.device)) / 2
 
@@ -400,10 +404,11 @@ TPS_NEEDS_SHAPE = ("{}(interpolation_mode='tps') without {}: the thin-plate-spli
 
 
 def inverse_transformation_at_sampled_points(deformed_pc_np, moving_displacements, sample_point_cloud, img_shape=None,
-                                             interpolation_mode='knn'):
+                                             interpolation_mode='knn', tps_solver='lu'):
     """point_cloud_registration.py:151-177: the displacements of the moved cloud, interpolated at the sample locations and
     subtracted from them -> the sample points in the moving cloud's space.  numpy in, numpy out (as the reference); GPU
-    tensors in, GPU tensor out.  'knn' needs no image shape; 'tps' needs img_shape = (D, H, W) and raises without it."""
+    tensors in, GPU tensor out.  'knn' needs no image shape; 'tps' needs img_shape = (D, H, W) and raises without it; tps_solver
+    (one of TPS_SOLVERS) is the solve of its fit."""
     if interpolation_mode not in INTERPOLATION_MODES:
         raise ValueError(f"interpolation_mode must be one of {INTERPOLATION_MODES}, got {interpolation_mode!r}")
     if interpolation_mode == 'tps' and img_shape is None:
@@ -416,7 +421,7 @@ def inverse_transformation_at_sampled_points(deformed_pc_np, moving_displacement
     else:
         deformed, disp, sample = deformed_pc_np, moving_displacements, sample_point_cloud
     if interpolation_mode == 'tps':
-        interpolated = interpolate_displacements_tps(deformed, disp, sample, img_shape)
+        interpolated = interpolate_displacements_tps(deformed, disp, sample, img_shape, solver=tps_solver)
     else:
         interpolated = interpolate_displacements_weighted_knn(deformed, disp, sample)
     if as_numpy:

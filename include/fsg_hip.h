@@ -1578,6 +1578,35 @@ int fsg_cholesky_solve_f64(const double *L, double *X, int B, int n, int r, fsg_
 int fsg_cpd_spd_system_f64(const double *G, const double *P1, const double *PX, const double *Y, const double *sigma2, double alpha,
                            int B, int M, double *S, double *rhs, double *d, fsg_stream_t stream);
 
+/* The null-space Cholesky route of the thin-plate-spline fit (csrc/tps_nullspace.hip).  Stands in for the solve of TPS.fit,
+ * shape_model/point_cloud_registration.py:32-52: the saddle point [[K, P], [P^T, 0]] [w; a] = [f; 0], K = u(|c_i - c_j|) +
+ * lambda I exactly as fsg_tps_system_f64 writes it, P = [1 | c] (n x 4).  u is conditionally positive definite of order 2, so
+ * with P = Q [R; 0] the block S = (Q^T K Q)[4:, 4:] of order m = n - 4 is symmetric positive definite for points that are
+ * distinct (or lambda > 0) and not in one plane: w = Q [0; y] with S y = (Q^T f)[4:], and R a = (Q^T (f - K w))[:4].  ours, not
+ * the reference's, which hands the indefinite system to an LU.  B independent items, DEVICE pointers, contiguous rows, fp64
+ * but for control (B, n, 3) fp32; B <= 65535; n >= 1 and n - 4 <= FSG_CHOL_MAX_N; K is never stored.
+ * fsg_tps_ns_system_f64: -> V (B, n, 4) the Householder vectors of P in LAPACK dgeqr2's convention (column k: zeros, a 1 at
+ *   row k, the vector below; beta = -sign(alpha) |x|, tau = (beta - alpha) / beta, tau = 0 where nothing lies below alpha),
+ *   tau (B, 4), R (B, 4, 4) upper triangular with zeros below, S (B, m, m) LOWER triangle only, the form fsg_cholesky_f64
+ *   takes (not touched for n <= 4, where it may be NULL), and the rank status info (B) int32 DEVICE: 0, or -k (1-based) for the
+ *   first |R_kk| that is not above n 2^-52 max_j |R_jj| (points in one plane, fewer than 4 points, a NaN).  The launches:
+ *   the QR (one workgroup per item), X = K V with K on the fly, the dlatrd recurrence X -> W in place with
+ *   Q^T K Q = K - V W^T - W V^T, and S_ij = K_(i+4)(j+4) - sum_k (V_(i+4)k W_(j+4)k + W_(i+4)k V_(j+4)k), one thread per entry.
+ *   work: FSG_TPS_NS_SYSTEM_WORK_PER_POINT B n doubles (it holds W).
+ * fsg_tps_ns_solve_f64: values (B, n, C) fp64, V, tau, R from above, L (B, m, m) the factor fsg_cholesky_f64 made of S (NULL
+ *   allowed for n <= 4: no factorisation exists and fsg_cholesky_solve_f64 is not launched; w = 0) -> theta (B, n + 4, C): the
+ *   n spline weights, then the affine rows.  1 <= C <= FSG_TPS_MAX_CHANNELS.  work: FSG_TPS_NS_SOLVE_WORK_PER_VALUE B n C
+ *   doubles.  The theta of an item whose status or whose factorisation's status is not 0 is unspecified, never a fault; with
+ *   fewer than 4 points its affine rows are NaN.
+ * Fixed summation orders, no atomics, nothing read on the host: the same inputs give the same bits, alone or in a batch, and
+ * both entries can be captured in a graph.  Bad arguments are FSG_ERR_ARG. */
+#define FSG_TPS_NS_SYSTEM_WORK_PER_POINT 4 /* doubles of `work` per control point: W (n, 4) */
+#define FSG_TPS_NS_SOLVE_WORK_PER_VALUE 2  /* doubles of `work` per value: Q^T f (n, C) and y (n - 4, C) */
+int fsg_tps_ns_system_f64(const float *control, int B, int n, double lambd, double *V, double *tau, double *R, double *S,
+                          int32_t *info, double *work, fsg_stream_t stream);
+int fsg_tps_ns_solve_f64(const float *control, const double *values, const double *V, const double *tau, const double *R,
+                         const double *L, int B, int n, int C, double lambd, double *work, double *theta, fsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

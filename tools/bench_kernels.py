@@ -1806,6 +1806,7 @@ if "tps" in which:
     import numpy as np
     import tps_oracle as to
     from fissure_segmentation_amd.shape_model import point_cloud_registration as pcr
+    from fissure_segmentation_amd._launch import _p, launch
     lines = []
 
     def emit_line(rec):
@@ -1875,6 +1876,50 @@ if "tps" in which:
                    grid_sample_peak_extra_MiB=peak_extra(lambda: F.tps_grid_sample(grid, control, theta, size)))
         emit_line(rec)
         del A, rhs
+
+        # the 'nullspace' solver (csrc/tps_nullspace.hip) beside 'lu': the two alternate call by call in this process, HIP-event
+        # medians; the stages of the new route; one pair; peak extra memory; what the thetas and the sampled outputs differ by
+        def alternate(fns, rounds=7, warm=1):
+            """{name: median microseconds}, the calls taking turns"""
+            ts = {k: [] for k in fns}
+            for r in range(warm + rounds):
+                for k, fn in fns.items():
+                    s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    s.record()
+                    keep = fn()
+                    t.record()
+                    torch.cuda.synchronize()
+                    del keep
+                    if r >= warm:
+                        ts[k].append(s.elapsed_time(t) * 1e3)
+            return {k: round(float(np.median(v)), 1) for k, v in ts.items()}
+
+        fit = lambda solver, s=slice(None): F.tps_fit(control[s], values[s], to.LAMBDA, solver=solver)   # noqa: E731
+        interp = lambda solver: pcr.interpolate_displacements_tps(e, v, q, shape, solver=solver)   # noqa: E731
+        fit_us = alternate({k: (lambda k=k: fit(k)) for k in ("lu", "nullspace")})
+        interp_us = alternate({k: (lambda k=k: interp(k)) for k in ("lu", "nullspace")})
+        one_us = alternate({k: (lambda k=k: fit(k, slice(0, 1))) for k in ("lu", "nullspace")})
+        V, tau, R, S, info = F.tps_nullspace_system(control, to.LAMBDA)
+        L, _ = F.cholesky_factor(S)
+        v64 = values.double().contiguous()
+        work = torch.empty(B * n * 3 * fsg._lib.TPS_NS_SOLVE_WORK_PER_VALUE, dtype=torch.float64, device=dev)
+        th_buf = torch.empty(B, n + 4, 3, dtype=torch.float64, device=dev)
+        cc = control.contiguous()
+        stage_us = dict(system_us=us(lambda: F.tps_nullspace_system(control, to.LAMBDA)),
+                        factor_us=us(lambda: F.cholesky_factor(S)),
+                        solve_us=us(lambda: launch(dev, "fsg_tps_ns_solve_f64", _p(cc), _p(v64), _p(V), _p(tau), _p(R), _p(L), B, n, 3,
+                                                   to.LAMBDA, _p(work), _p(th_buf))))
+        th_lu, th_ns = fit("lu"), fit("nullspace")
+        out_lu, out_ns = interp("lu"), interp("nullspace")
+        emit_line(dict(kernel="tps_nullspace", B=B, n=n, Q=Q, img_shape=list(shape),
+                       fit_us=fit_us, interpolate_displacements_tps_us=interp_us, one_pair_fit_us=one_us, **stage_us,
+                       fit_peak_extra_MiB={k: peak_extra(lambda k=k: fit(k)) for k in ("lu", "nullspace")},
+                       status_nonzero=int((info != 0).sum()),
+                       theta_apart=float((th_ns - th_lu).abs().max() / th_lu.abs().max()),
+                       sampled_apart=float((out_ns - out_lu).abs().max() / out_lu.abs().max()),
+                       note="microseconds, medians of HIP-event times, 'lu' and 'nullspace' alternating; factor_us includes the copy "
+                            "of S that cholesky_factor makes without overwrite=True; *_apart relative to the largest entry"))
+        del V, tau, R, S, L, work, th_buf, th_lu, th_ns
         one = lambda: pcr.thin_plate_dense(control[:1], values[:1], size, to.STEP, to.LAMBDA)   # noqa: E731
         lattice_us = us(lambda: F.tps_eval(tuple(s // to.STEP for s in size), control[:1], theta[:1]))
         comp = lambda: dense_composition(control[0], values[0], grid[0])   # noqa: E731
